@@ -36,8 +36,25 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
-FP32_VECTOR_PEAK_TFLOPS = 157.3  # same guide: FP32 vector (= FP32 matrix) peak
+HBM_PEAK_GBS = 8000.0  # MI355X spec: 8.0 TB/s
+FP32_VECTOR_PEAK_TFLOPS = 157.3  # MI355X spec: FP32 vector (= FP32 matrix) peak
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirpath: str, name: str, out: np.ndarray, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: the float32[n_windows, n_features] rows the last timed step handed its caller, as
+    DIR/<name>.npy.  Above `limit` bytes a fixed, seeded sample of whole rows is written instead, and the row indices
+    it kept as DIR/<name>_rows.npy (float64), so that two builds can be compared output for output."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    out = np.ascontiguousarray(out, dtype=np.float32)
+    row_bytes = max(out.shape[1] * out.itemsize, 1)
+    if out.nbytes > limit:
+        keep = max(1, (limit - 8 * out.shape[0]) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], size=keep, replace=False))
+        np.save(d / f"{name}_rows.npy", rows.astype(np.float64))
+        out = out[rows]
+    np.save(d / f"{name}.npy", out)
 
 
 def make_settings():
@@ -365,6 +382,9 @@ def run_config(args, torch, dist, world, rank, dev, dev_index) -> None:
         dist.barrier()
     dt = time.perf_counter() - t0
     dt_own = dt
+    if args.dump_outputs:   # (the stage-timer steps below overwrite `out`)
+        dump_outputs(args.dump_outputs, "features" if world == 1 else f"features_rank{rank}", out.cpu().numpy(),
+                     DUMP_LIMIT_BYTES // world)
     kt = {k: 0.0 for k in names_t}   # per-stage HIP-event times from a few more steps outside the timed region
     n_kt = min(10, args.steps)
     for _ in range(n_kt):
@@ -443,7 +463,12 @@ def main() -> None:
     ap.add_argument("--no-mode-a", action="store_true", help="skip the roofline_modeA measurement (time / oscillatory kernel from HBM)")
     ap.add_argument("--no-preproc", action="store_true", help="skip notch + re-referencing")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32, at most "
+                         "64 MB in all: a seeded sample of rows beyond that); same arguments -> same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     import torch
 
@@ -561,9 +586,13 @@ def main() -> None:
     if with_norm:
         eng.attach_normalizer(dn)
         dt = timed(args.steps)
-        eng.attach_normalizer(None)
     else:
         dt = plain_dt
+    if args.dump_outputs:   # the headline leg's last step (the stage-timer steps below overwrite `out`)
+        dump_outputs(args.dump_outputs, "features" if world == 1 else f"features_rank{rank}", out.cpu().numpy(),
+                     DUMP_LIMIT_BYTES // world)
+    if with_norm:
+        eng.attach_normalizer(None)
     # per-stage HIP-event times (recorded on the launch stream inside libnmx): a few more steps OUTSIDE the timed region --
     # reading an event waits for it, which would serialise the host against every step above.  Normaliser detached: a
     # step is then ONE launch sequence of 1024 hops and a stage's timer brackets the kernel(s) of the whole step (with it
