@@ -27,7 +27,7 @@ import numpy as np
 
 from . import channels as chmod
 from . import fir_design
-from .engine import HotPathEngine
+from .engine import HotPathEngine, parallel_cast, table_empty
 from .processing import DeviceFeatureNormalizer, FeatureNormalizer
 from .settings import NMSettings
 
@@ -36,15 +36,30 @@ PREPROCESSOR_ORDER = ["preprocessing_filter", "notch_filter", "raw_resampling", 
 
 
 class _LazyNanCols:
+    """The NaN policy (stream/data_processor.py:297-306): every key that CONTAINS the new_name of a channel whose window
+    held a NaN := NaN (substring match, as the reference).  A channel's columns are found on first use (256 channels x
+    8 000 keys of substring tests cost 50 ms up front, and a NaN channel is the exception); ``keys`` is the orchestrator's
+    own list, so the columns are looked up again once the plugin keys are appended to it (UserColumns)."""
+
     def __init__(self, keys, ch_names) -> None:
         self._keys, self._ch, self._cache = keys, ch_names, {}
 
     def __getitem__(self, ci: int) -> np.ndarray:
-        cols = self._cache.get(ci)
+        cols = self._cache.get((ci, len(self._keys)))
         if cols is None:
             ch = self._ch[ci]
-            cols = self._cache[ci] = np.array([i for i, k in enumerate(self._keys) if ch in k], dtype=int)
+            cols = self._cache[ci, len(self._keys)] = np.array([i for i, k in enumerate(self._keys) if ch in k], dtype=int)
         return cols
+
+    def apply(self, table: np.ndarray, mask: np.ndarray) -> np.ndarray:
+        """The policy in place on the float64 ``table[n, len(keys)...]``; ``mask[n, channels]``: NaN per hop and channel."""
+        if mask.any():
+            if mask.shape[1] != len(self._ch):
+                # the reference indexes ch_names_used with the mask over ALL rows (:300)
+                raise IndexError("boolean index did not match: NaN handling needs every channel used")
+            for ci in np.where(mask.any(axis=0))[0]:
+                table[np.ix_(mask[:, ci], self[ci])] = np.nan
+        return table
 
 
 class UserColumns:
@@ -106,12 +121,16 @@ class UserColumns:
             out = self.norm.process_batch(out).astype(np.float64)
         return out
 
-    def merge(self, builtin: np.ndarray, user: np.ndarray) -> np.ndarray:
-        out = np.empty((builtin.shape[0], len(self.keys)), np.float64)
-        out[:, :builtin.shape[1]] = builtin
+    def merge(self, table: np.ndarray, user: np.ndarray) -> np.ndarray:
+        """``user`` (from `rows`) into its columns of the float64 ``table``: in place, or in a copy widened to every key
+        when the table holds only the built-in columns."""
+        if table.shape[1] < len(self.keys):
+            wide = np.empty((table.shape[0], len(self.keys)), np.float64)
+            wide[:, :table.shape[1]] = table
+            table = wide
         if user.shape[0]:
-            out[:, self.cols] = user     # after the built-in values: dict.update overwrites a repeated key
-        return out
+            table[:, self.cols] = user     # after the built-in values: dict.update overwrites a repeated key
+        return table
 
 
 class DataProcessor:
@@ -120,14 +139,16 @@ class DataProcessor:
                  device: int = 0, window: int | None = None, lib=None,
                  channel_subset=None, dry_run: bool = False,
                  resample_features_at_new_rate: bool = False, local_inputs: bool = False,
-                 staging_slot: int = 0) -> None:
+                 staging_slot: int = 0, _share: "DataProcessor | None" = None) -> None:
+        """``_share``: the processor this one is the twin of for another window length (`_for_length`): the twin takes
+        its feature normaliser, user features and table of twins instead of building its own."""
         self.settings = NMSettings.load(settings)
         self.channels = chmod.load_channels(channels)
         # (what a twin for another window length is built from: `process` under the reference's own loop, below)
         self._ctor = dict(sfreq=sfreq, line_noise=line_noise, verbose=verbose, device=device, lib=lib,
                           resample_features_at_new_rate=resample_features_at_new_rate, staging_slot=staging_slot)
         self._twin_ok = channel_subset is None and not dry_run and not local_inputs
-        self._by_len, self._active = None, None
+        self._by_len, self._active = (None, None) if _share is None else (_share._by_len, _share._active)
         self.sfreq_features = self.settings.sampling_rate_features_hz
         self._sfreq_raw_orig = sfreq
         self.sfreq_raw = sfreq // 1
@@ -251,34 +272,29 @@ class DataProcessor:
         from . import user_features as _registered
 
         self._user = None
-        if _registered and not dry_run and channel_subset is None:
+        if _share is not None:
+            self._user = _share._user
+        elif _registered and not dry_run and channel_subset is None:
             self._user = UserColumns(st, names, self.sfreq_raw, self.keys, device=device, lib=lib)
         self._user_chunk = 64                          # hops per tapped batch (bounds the [n, C, W] hand-back)
-        self.feature_normalizer = None
-        self.non_psd_indices = None
         self.device_normalizer = None
         self._norm_in_engine = False
-        if st.postprocessing.feature_normalization:
-            fs = st.feature_normalization_settings
-            if not fs.normalize_psd:
-                self.non_psd_indices = np.array([i for i, k in enumerate(self.keys) if "psd" not in k], dtype=int)
-            if fs.normalization_method in DeviceFeatureNormalizer.METHODS and not dry_run:
-                # "mean" / "zscore" (default): one HIP scan per batch of hops; the column mask
-                # carries the "psd" exclusion (stream/data_processor.py:263-290)
+        if st.postprocessing.feature_normalization and not dry_run:
+            if _share is not None:
+                self.device_normalizer = _share.device_normalizer
+            else:
+                FeatureNormalizer(st)   # an unknown method name raises NotImplementedError here, naming it
+                # every method of normalization.py:57-70: one HIP scan per batch of hops; the column mask carries the
+                # "psd" exclusion (stream/data_processor.py:263-290)
                 mask = None
-                if self.non_psd_indices is not None:
-                    mask = np.zeros(len(self.keys), dtype=np.uint8)
-                    mask[self.non_psd_indices] = 1
+                if not st.feature_normalization_settings.normalize_psd:
+                    mask = np.array(["psd" not in k for k in self.keys], dtype=np.uint8)
                 self.device_normalizer = DeviceFeatureNormalizer(st, len(self.keys), colmask=mask,
                                                                  device=device, lib=lib)
+            if _share is None or _share._norm_in_engine:
                 # inside the engine's launch sequence: rows come back normalised (no second round trip)
                 self.engine.attach_normalizer(self.device_normalizer)
                 self._norm_in_engine = True
-            elif not dry_run:   # an unknown method name (every method of normalization.py:57-70 runs on the device): raises, naming it
-                self.feature_normalizer = FeatureNormalizer(st)
-        # NaN policy: columns whose key contains the channel's new_name (substring, as the reference);
-        # built on first use per channel (256 channels x 8 000 keys of substring tests cost 50 ms up front,
-        # and a NaN channel is the exception)
         self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
         self.cnt_samples = 0
         self.settings_token = None
@@ -321,23 +337,19 @@ class DataProcessor:
         self.cnt_samples = 0
 
     # ------------------------------------------------------------------------------------
-    def _postprocess_row(self, row: np.ndarray, nan_rows: np.ndarray) -> np.ndarray:
+    def _finish(self, out: np.ndarray, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
+        """Engine rows ``float32[n, F]`` in hop order -> the float64 table: the normaliser (unless it ran inside the
+        engine), the cast, the user columns, the NaN policy (last: the plugin keys follow it too)."""
         if self.device_normalizer is not None and not self._norm_in_engine:
-            row = self.device_normalizer.process(row)
-        if self.feature_normalizer is not None:
-            if self.non_psd_indices is not None:
-                row = row.copy()
-                row[self.non_psd_indices] = self.feature_normalizer.process(row[self.non_psd_indices])
-            else:
-                row = self.feature_normalizer.process(row)
-        if nan_rows.any():
-            if len(nan_rows) != len(self.ch_names_used):
-                # the reference indexes ch_names_used with the mask over ALL rows (:300)
-                raise IndexError("boolean index did not match: NaN handling needs every channel used")
-            row = row.copy()
-            for ci in np.where(nan_rows)[0]:
-                row[self._nan_cols[ci]] = np.nan
-        return row
+            out = self.device_normalizer.process_batch(out)
+        if len(out) == 1:   # (one hop, `process`: the pooled table and the threaded cast cost more than they save)
+            table = out.astype(np.float64)
+        else:
+            table = table_empty(out.shape)
+            parallel_cast(table, out, None, self.engine.lib)
+        if user is not None:
+            table = self._user.merge(table, user)
+        return self._nan_cols.apply(table, mask)
 
     # -- user-registered features (features/feature_processor.py:52-53,80-82) ----------------------
     @property
@@ -348,19 +360,9 @@ class DataProcessor:
     def user_keys(self):
         return self._user.user_keys if self._user is not None else None
 
-    def _user_rows(self, windows) -> np.ndarray:
-        first = self._user.user_keys is None
-        out = self._user.rows(windows)
-        if first and self._user.user_keys is not None:
-            self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
-        return out
-
     def _host_windows(self, data: np.ndarray, starts) -> "list[np.ndarray]":
         W = self.engine.W_in
         return [np.nan_to_num(np.asarray(data[:, int(s):int(s) + W], dtype=np.float64)) for s in starts]
-
-    def _with_user_columns(self, rows: np.ndarray, user: np.ndarray) -> np.ndarray:
-        return self._user.merge(rows, user)
 
     def process_batch_tapped(self, data: np.ndarray, starts: np.ndarray):
         """One batch through the engine AND the windows its features read: (float32 rows -- normalised when the
@@ -384,7 +386,7 @@ class DataProcessor:
             o, m, wins = self.process_batch_tapped(data, starts[i:i + self._user_chunk])
             outs.append(o)
             masks.append(m)
-            users.append(self._user_rows(wins))
+            users.append(self._user.rows(wins))
         return np.concatenate(outs), np.concatenate(masks), np.concatenate(users)
 
     def _row_dict(self, row: np.ndarray) -> dict:
@@ -414,14 +416,8 @@ class DataProcessor:
         if p is None:
             if not self._twin_ok:
                 raise ValueError(f"expected windows of {self.engine.W_in} samples, got {n_samples}")
-            p = DataProcessor(settings=self.settings, channels=self.channels, window=n_samples, **self._ctor)
-            if self._norm_in_engine:
-                p.device_normalizer = self.device_normalizer
-                p.engine.attach_normalizer(self.device_normalizer)
-            p.feature_normalizer = self.feature_normalizer
-            p._user = self._user
-            p._by_len, p._active = self._by_len, self._active
-            self._by_len[n_samples] = p
+            p = self._by_len[n_samples] = DataProcessor(settings=self.settings, channels=self.channels, window=n_samples,
+                                                        _share=self, **self._ctor)
         cur = self._active[0]
         if cur is not p:
             state = cur.engine.export_state()
@@ -439,19 +435,11 @@ class DataProcessor:
                 return p.process(data)
         start_time = time()
         if self._user is not None:
-            data = np.asarray(data)
-            out, mask, user = self._process_batch_user(data, np.zeros(1, np.int64))
-            rows = self._finish_rows(out, mask, self._norm_in_engine)
-            row = self._with_user_columns(rows, user)[0]
-            if mask[0].any():
-                row = self._apply_nan_policy(row[None], mask)[0]
-            if self.verbose:
-                from . import logger
-
-                logger.info("Last batch took: %.3f seconds to process", time() - start_time)
-            return self._row_dict(row)
-        out, mask = self.engine.process_window(data, want_nan_mask=True)
-        row = self._postprocess_row(out.astype(np.float64), mask)
+            out, mask, user = self._process_batch_user(np.asarray(data), np.zeros(1, np.int64))
+        else:
+            out, mask = self.engine.process_window(data, want_nan_mask=True)
+            out, mask, user = out[None], mask[None], None
+        row = self._finish(out, mask, user)[0]   # (a table of one hop)
         if self.verbose:
             from . import logger
 
@@ -463,15 +451,12 @@ class DataProcessor:
         applied hop by hop because the normaliser is sequential).  ``spare_cols``: the table MAY come back with that
         many extra columns behind the features (HotPathEngine.process_batch_f64) -- the caller checks the shape."""
         if self._user is not None:
-            out, mask, user = self._process_batch_user(data, starts)
-            rows = self._with_user_columns(self._finish_rows(out, mask, self._norm_in_engine), user)
-            return self._apply_nan_policy(rows, mask) if mask.any() else rows
-        if self.feature_normalizer is None and (self.device_normalizer is None or self._norm_in_engine):
+            return self._finish(*self._process_batch_user(data, starts))
+        if self.device_normalizer is None or self._norm_in_engine:
             # nothing left to do on the host but the NaN policy: conversions pipelined against the device
             rows, mask = self.engine.process_batch_f64(data, starts, want_nan_mask=True, spare_cols=spare_cols)
-            return self._apply_nan_policy(rows, mask) if mask.any() else rows
-        out, mask = self.engine.process_batch(data, starts, want_nan_mask=True, staged_output=True)
-        return self.postprocess_batch(out, mask, normalised=self._norm_in_engine)
+            return self._nan_cols.apply(rows, mask)
+        return self._finish(*self.engine.process_batch(data, starts, want_nan_mask=True, staged_output=True))
 
     # -- ragged window lengths (a non-integer number of samples per segment): `Stream.run` cuts the hops into
     # consecutive runs of one length, one processor per length; what carries over from hop to hop travels between them
@@ -490,54 +475,31 @@ class DataProcessor:
         self.engine.import_state(state)
 
     def ragged_run(self, data: np.ndarray, starts: np.ndarray):
-        """One run of equal-length hops -> (float32 engine rows, NaN mask, [pre-processed windows] or None)."""
-        eng = self.engine
-        if self._user is not None and not eng.preprocessing_is_identity:
-            o, m, pre = eng.process_batch(data, starts, want_nan_mask=True, tap=True)
-            return o, m, [pre[j].astype(np.float64) for j in range(len(starts))]
-        o, m = eng.process_batch(data, starts, want_nan_mask=True)
-        return o, m, (self._host_windows(data, starts) if self._user is not None else None)
+        """One run of equal-length hops -> (float32 engine rows, NaN mask, pre-processed windows or None)."""
+        if self._user is not None:
+            return self.process_batch_tapped(data, starts)
+        return (*self.engine.process_batch(data, starts, want_nan_mask=True), None)
 
     def ragged_finish(self, runs) -> np.ndarray:
         """The runs of `ragged_run` in hop order -> the float64 table (normaliser, user columns, NaN policy)."""
-        raw = np.concatenate([r[0] for r in runs])
-        masks = np.concatenate([r[1] for r in runs])
-        if self._user is None:
-            return self.postprocess_batch(raw, masks)
-        wins = [w for r in runs for w in r[2]]
-        user = self._user_rows(wins)   # one set of instances sees every hop in order, like the reference
-        rows = self._with_user_columns(self._finish_rows(raw, masks, False), user)
-        return self._apply_nan_policy(rows, masks) if masks.any() else rows
+        # one set of user-feature instances sees every hop in order, like the reference
+        user = self._user.rows([w for r in runs for w in r[2]]) if self._user is not None else None
+        return self._finish(np.concatenate([r[0] for r in runs]), np.concatenate([r[1] for r in runs]), user)
 
-    def _finish_rows(self, out: np.ndarray, mask: np.ndarray, normalised: bool) -> np.ndarray:
-        """Built-in columns: normalisation (unless it ran inside the engine) and the cast to float64; the NaN policy
-        is applied by the caller once the user columns are in place."""
-        return self.postprocess_batch(out, np.zeros_like(mask), normalised=normalised)
 
-    def postprocess_batch(self, out: np.ndarray, mask: np.ndarray, normalised: bool = False) -> np.ndarray:
-        """Normalisation + NaN policy for engine rows ``out[n, F]`` (hop order); ``normalised``: the
-        attached device normaliser already ran inside the engine."""
-        from .engine import parallel_cast, table_empty
-
-        if self.device_normalizer is not None and not normalised:
-            out = self.device_normalizer.process_batch(out)
-        o64 = table_empty(out.shape)
-        parallel_cast(o64, out, None, self.engine.lib)
-        out = o64
-        if self.feature_normalizer is None and not mask.any():
-            return out
-        if self.feature_normalizer is None:
-            return self._apply_nan_policy(out, mask)
-        dn, self.device_normalizer = self.device_normalizer, None   # already applied above
-        try:
-            return np.stack([self._postprocess_row(out[i], mask[i]) for i in range(len(out))])
-        finally:
-            self.device_normalizer = dn
-
-    def _apply_nan_policy(self, rows: np.ndarray, mask: np.ndarray) -> np.ndarray:
-        """Every key that contains the name of a channel whose window held a NaN := NaN (:297-306)."""
-        if mask.shape[1] != len(self.ch_names_used):
-            raise IndexError("boolean index did not match: NaN handling needs every channel used")
-        for ci in np.where(mask.any(axis=0))[0]:
-            rows[np.ix_(mask[:, ci], self._nan_cols[ci])] = np.nan
-        return rows
+def _ragged_runs(procs: dict, lens: np.ndarray, run) -> list:
+    """Ragged window lengths (a non-integer number of samples per segment): the hops in order as consecutive runs of one
+    length, ``run(processor, a, b)`` computing hops [a, b) on ``procs[length]``.  What carries over from hop to hop (burst
+    history, Kalman filters, raw-normaliser history) travels from processor to processor where the length changes
+    (``ragged_*`` of DataProcessor / MultiDeviceProcessor).  -> the results of ``run`` in hop order."""
+    for p in procs.values():
+        p.ragged_prepare()
+    cuts = [0] + [i for i in range(1, len(lens)) if lens[i] != lens[i - 1]] + [len(lens)]
+    state, runs = None, []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        p = procs[int(lens[a])]
+        if state is not None:
+            p.ragged_set_state(state)
+        runs.append(run(p, a, b))
+        state = p.ragged_state()
+    return runs

@@ -24,7 +24,7 @@ import os
 import numpy as np
 
 from . import channels as chmod
-from .data_processor import DataProcessor, UserColumns, _LazyNanCols
+from .data_processor import DataProcessor, UserColumns, _LazyNanCols, _ragged_runs
 from .engine import table_empty
 from .generator import window_schedule
 from .settings import NMSettings
@@ -147,42 +147,31 @@ class ShardedStream:
             full[:, rows] = m.astype(bool)
         return full
 
+    def _local_x(self, data: np.ndarray, group=None) -> np.ndarray:
+        """With ``local_input``: the rows the engine reads -- this rank's input rows, then the hi / lo rows of every
+        all-reduced group sum it needs."""
+        if data.shape[0] != len(self.local_rows):
+            raise ValueError(f"local_input: expected the {len(self.local_rows)} rows ShardedStream.local_rows, "
+                             f"got {data.shape[0]}")
+        sums = self.group_sums(data, group)
+        return np.concatenate([np.asarray(data, np.float32)] + [chmod.split_hi_lo(v) for v in sums], axis=0)
+
+    def _local_table(self, dp, out: np.ndarray, mask: np.ndarray, group=None) -> np.ndarray:
+        """With ``local_input``: the engine rows -> the float64 table, the NaN policy seeing the mask of every rank."""
+        return dp._finish(out, self._gather_mask(mask, len(self.channels), group))
+
     def _run_ragged(self, data, starts, lens, times, group):
-        """Ragged window lengths (a non-integer number of samples per segment): one processor per length, the hops in
-        order as runs of one length, this rank's state (burst histories, Kalman filters, raw-normaliser histories)
-        handed from processor to processor where the length changes (DataProcessor.ragged_*, as Stream.run does)."""
+        """Ragged window lengths (a non-integer number of samples per segment): one processor per length, this rank's
+        state handed from processor to processor where the length changes (data_processor._ragged_runs, as Stream.run)."""
         procs = {int(w): self._processor(int(w)) for w in sorted(set(lens.tolist()))}
-        for p in procs.values():
-            p.ragged_prepare()
         dp0 = procs[min(procs)]
-        x = None
-        if self.local_input:
-            if data.shape[0] != len(self.local_rows):
-                raise ValueError(f"local_input: expected the {len(self.local_rows)} rows ShardedStream.local_rows, "
-                                 f"got {data.shape[0]}")
-            sums = self.group_sums(data, group)
-            x = np.concatenate([np.asarray(data, np.float32)] + [chmod.split_hi_lo(v) for v in sums], axis=0)
-        cuts = [0] + [i for i in range(1, len(lens)) if lens[i] != lens[i - 1]] + [len(lens)]
-        state, runs = None, []
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            p = procs[int(lens[a])]
-            if state is not None:
-                p.ragged_set_state(state)
-            if x is None:
-                runs.append(p.ragged_run(data, starts[a:b]))
-            else:
-                o, m = p.engine.process_batch(x, starts[a:b], want_nan_mask=True)
-                runs.append((o, m, None))
-            state = p.ragged_state()
-        if x is None:
+        if not self.local_input:
+            runs = _ragged_runs(procs, lens, lambda p, a, b: p.ragged_run(data, starts[a:b]))
             return list(dp0.keys), dp0.ragged_finish(runs), times
-        out = np.concatenate([r[0] for r in runs])
-        mask_all = self._gather_mask(np.concatenate([r[1] for r in runs]), len(self.channels), group)
-        if mask_all.any() and mask_all.shape[1] != len(dp0.ch_names_used):
-            raise IndexError("boolean index did not match: NaN handling needs every channel used")
-        rows = dp0.postprocess_batch(out, mask_all if mask_all.any() else np.zeros((len(out), len(dp0.ch_names_used)), bool),
-                                     normalised=False)
-        return list(dp0.keys), rows, times
+        x = self._local_x(data, group)
+        runs = _ragged_runs(procs, lens, lambda p, a, b: p.engine.process_batch(x, starts[a:b], want_nan_mask=True))
+        out, mask = np.concatenate([o for o, _ in runs]), np.concatenate([m for _, m in runs])
+        return list(dp0.keys), self._local_table(dp0, out, mask, group), times
 
     def run(self, data: np.ndarray, group=None):
         """-> (local_keys, float64[n_windows, n_local], time_ms) for this rank's channels.
@@ -197,20 +186,11 @@ class ShardedStream:
         if not self.local_input:
             rows = dp.process_batch(data, starts) if len(starts) else np.empty((0, len(dp.keys)))
             return list(dp.keys), rows, times
-        if data.shape[0] != len(self.local_rows):
-            raise ValueError(f"local_input: expected the {len(self.local_rows)} rows ShardedStream.local_rows, "
-                             f"got {data.shape[0]}")
-        sums = self.group_sums(data, group)
-        x = np.concatenate([np.asarray(data, np.float32)] + [chmod.split_hi_lo(v) for v in sums], axis=0)
+        x = self._local_x(data, group)
         if not len(starts):
             return list(dp.keys), np.empty((0, len(dp.keys))), times
         out, mask = dp.engine.process_batch(x, starts, want_nan_mask=True)
-        mask_all = self._gather_mask(mask, len(self.channels), group)
-        if mask_all.any() and mask_all.shape[1] != len(dp.ch_names_used):
-            raise IndexError("boolean index did not match: NaN handling needs every channel used")
-        rows = dp.postprocess_batch(out, mask_all if mask_all.any() else np.zeros((len(out), len(dp.ch_names_used)), bool),
-                                    normalised=dp._norm_in_engine)
-        return list(dp.keys), rows, times
+        return list(dp.keys), self._local_table(dp, out, mask, group), times
 
 
 class MultiDeviceProcessor:
@@ -302,6 +282,7 @@ class MultiDeviceProcessor:
         if len(self.devices) > 2 and not os.environ.get("NMX_HOST_THREADS"):
             self.stage_threads = int(max(16, min(64, 8 * len(self.devices), (os.cpu_count() or 32) // 2)))
         self.pipeline_min = (64, 1 << 20)   # hops, samples: below, staging and widening are not worth their threads
+        self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
 
     @property
     def engine(self):
@@ -320,6 +301,15 @@ class MultiDeviceProcessor:
             p.reset()
         if self._user is not None:
             self._user.reset()
+
+    def _finish(self, outs, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
+        """The parts' float32 rows (hop order) -> the float64 table: every part normalises and widens its own columns
+        (the normaliser is per column), then the joined table takes the user columns and the NaN policy."""
+        zero = np.zeros_like(mask)
+        table = self._merge([p._finish(o, zero) for p, o in zip(self.parts, outs)])
+        if user is not None:
+            table = self._user.merge(table, user)
+        return self._nan_cols.apply(table, mask)
 
     def _merge(self, rows) -> np.ndarray:
         """The parts' tables side by side -> the global column order (a gather with one precomputed permutation, row
@@ -543,8 +533,7 @@ class MultiDeviceProcessor:
     def process_batch(self, data: np.ndarray, starts: np.ndarray, spare_cols: int = 0) -> np.ndarray:
         """``spare_cols``: as DataProcessor.process_batch (extra columns behind the features, pipelined path only)."""
         starts = np.asarray(starts, dtype=np.int64)
-        if self._user is None and all(p.feature_normalizer is None and (p.device_normalizer is None or p._norm_in_engine)
-                                      for p in self.parts):
+        if self._user is None and all(p.device_normalizer is None or p._norm_in_engine for p in self.parts):
             # nothing between the engines' rows and the table but the widening and the NaN policy
             if (len(starts) >= self.pipeline_min[0] and np.size(data) >= self.pipeline_min[1]
                     and os.environ.get("NMX_PIPELINE", "1") != "0"):
@@ -553,32 +542,16 @@ class MultiDeviceProcessor:
                 got = self._run_parts(data, starts, False, staged=True)
                 table = self._merge_widen([o for o, _, _ in got])
                 mask = got[0][1]   # over ALL incoming rows, the same for every part
-            if mask.any():     # every key that contains the name of a channel whose window held a NaN := NaN (:297-306)
-                if mask.shape[1] != len(self.ch_names_used):
-                    raise IndexError("boolean index did not match: NaN handling needs every channel used")
-                nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
-                for ci in np.where(mask.any(axis=0))[0]:
-                    table[np.ix_(mask[:, ci], nan_cols[ci])] = np.nan
-            return table
+            return self._nan_cols.apply(table, mask)
         if self._user is None:
             got = self._run_parts(data, starts, False)
-            rows = [p.postprocess_batch(o, m, normalised=p._norm_in_engine) for p, (o, m, _) in zip(self.parts, got)]
-            return self._merge(rows)
+            return self._finish([o for o, _, _ in got], got[0][1])
         tables = []
         for i in range(0, len(starts), self._user_chunk):
-            st_ = starts[i:i + self._user_chunk]
-            got = self._run_parts(data, st_, True)
+            got = self._run_parts(data, starts[i:i + self._user_chunk], True)
             # contiguous channel blocks in device order: the joined window is the single-device one
             user = self._user.rows(np.concatenate([w for _, _, w in got], axis=1))
-            builtin = [p.postprocess_batch(o, m, normalised=p._norm_in_engine) for p, (o, m, _) in zip(self.parts, got)]
-            table = self._merge(builtin)
-            table[:, self._user.cols] = user
-            mask = got[0][1]   # replicated input: every part saw every incoming row
-            if mask.any():     # the plugin keys follow the substring NaN policy too (stream/data_processor.py:297-306)
-                nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
-                for ci in np.where(mask.any(axis=0))[0]:
-                    table[np.ix_(mask[:, ci], nan_cols[ci])] = np.nan
-            tables.append(table)
+            tables.append(self._finish([o for o, _, _ in got], got[0][1], user))
         return np.concatenate(tables) if tables else np.empty((0, len(self.keys)))
 
     # -- ragged window lengths: the protocol of DataProcessor.ragged_* over the parts --------------------------------
@@ -598,33 +571,14 @@ class MultiDeviceProcessor:
 
     def ragged_run(self, data: np.ndarray, starts: np.ndarray):
         got = self._run_parts(data, np.asarray(starts, dtype=np.int64), self._user is not None)
-        wins = None
-        if self._user is not None:   # contiguous channel blocks in device order: the joined window is the single-device one
-            joined = np.concatenate([w for _, _, w in got], axis=1)
-            wins = [joined[j] for j in range(joined.shape[0])]
+        # contiguous channel blocks in device order: the joined window is the single-device one
+        wins = np.concatenate([w for _, _, w in got], axis=1) if self._user is not None else None
         return [o for o, _, _ in got], got[0][1], wins
 
     def ragged_finish(self, runs) -> np.ndarray:
-        masks = np.concatenate([r[1] for r in runs])
-        zero = np.zeros_like(masks)
-        # every part normalises its own columns over ALL hops (the normaliser is per column)
-        rows = [p.postprocess_batch(np.concatenate([r[0][i] for r in runs]), zero, normalised=False)
-                for i, p in enumerate(self.parts)]
-        table = self._merge(rows)
-        if self._user is not None:
-            user = self._user.rows([w for r in runs for w in r[2]])
-            if table.shape[1] != len(self.keys):   # the first call appended the plugin keys
-                wide = np.full((table.shape[0], len(self.keys)), np.nan)
-                wide[:, :table.shape[1]] = table
-                table = wide
-            table[:, self._user.cols] = user
-        if masks.any():
-            nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
-            if masks.shape[1] != len(self.ch_names_used):
-                raise IndexError("boolean index did not match: NaN handling needs every channel used")
-            for ci in np.where(masks.any(axis=0))[0]:
-                table[np.ix_(masks[:, ci], nan_cols[ci])] = np.nan
-        return table
+        user = self._user.rows([w for r in runs for w in r[2]]) if self._user is not None else None
+        return self._finish([np.concatenate([r[0][i] for r in runs]) for i in range(len(self.parts))],
+                            np.concatenate([r[1] for r in runs]), user)
 
     def process(self, data: np.ndarray) -> dict:
         if self._user is not None or self.local_input:

@@ -14,7 +14,7 @@ from pathlib import Path
 import numpy as np
 
 from . import channels as chmod
-from .data_processor import DataProcessor
+from .data_processor import DataProcessor, _ragged_runs
 from .generator import window_schedule
 from .settings import NMSettings
 
@@ -197,16 +197,7 @@ class Stream:
                 # and the Kalman filters of the band powers (bandpower.py:147-163) carry over from hop to hop whatever
                 # the window length, so the state travels from processor to processor where the length changes
                 # (DataProcessor.ragged_* / MultiDeviceProcessor.ragged_*: one state blob per device there)
-                for p in procs.values():
-                    p.ragged_prepare()
-                cuts = [0] + [i for i in range(1, len(lens)) if lens[i] != lens[i - 1]] + [len(lens)]
-                state, runs = None, []
-                for a, b in zip(cuts[:-1], cuts[1:]):
-                    p = procs[int(lens[a])]
-                    if state is not None:
-                        p.ragged_set_state(state)
-                    runs.append(p.ragged_run(data, starts[a:b]))
-                    state = p.ragged_state()
+                runs = _ragged_runs(procs, lens, lambda p, a, b: p.ragged_run(data, starts[a:b]))
                 rows = dp0.ragged_finish(runs)
             keys = list(dp0.keys)   # after the first hop: user-feature keys are known once calc_feature has run
         last = starts + lens - 1   # the targets' column: the last sample of every window (stream/stream.py:319-329)
