@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 11
+#define NMX_ABI_VERSION 12
 
 /* error codes */
 #define NMX_OK 0
@@ -54,6 +54,7 @@ extern "C" {
 #define NMX_F_SHARPWAVE (1u << 6)  /* features/sharpwaves.py:100-465  */
 #define NMX_F_BURSTS (1u << 7)     /* features/bursts.py:60-298       */
 #define NMX_F_LINELENGTH (1u << 8) /* features/linelength.py:11-21    */
+#define NMX_F_COHERENCE (1u << 9)  /* features/coherence.py (pairs of channels) */
 
 /* estimator bits (oscillatory: mean/median/std/max, features/oscillatory.py:29-34) */
 #define NMX_EST_MEAN 1u
@@ -197,6 +198,28 @@ typedef struct {
    * it as window / sfreq.  It differs from window / sfreq when raw_resampling changes the window length
    * while the features are still built with the RAW rate (stream/data_processor.py:55,68,80). */
   double segment_length_s;
+
+  /* Coherence between channel pairs (features/coherence.py: Welch / CSD with a periodic Hann window, noverlap =
+   * nperseg / 2, constant detrend; coh = |Pxy|^2 / (Pxx Pyy), icoh = Im Pxy / sqrt(Pxx Pyy)).  Used when NMX_F_COHERENCE
+   * is set and coh_n_pairs > 0; all zero = off.  Stateless.
+   *   coh_pairs      [coh_n_pairs][2] indices of the feature channels (seed, target); copied at plan creation
+   *   coh_nperseg    segment length, already clamped to the window (scipy's nperseg > len(x) rule), 2 .. 4096
+   *   coh_bin_lo/hi  band b uses the one-sided bins [lo, hi) -- the host resolves the reference's strict edges
+   *                  (f > lo & f < hi) on scipy's float64 grid
+   *   coh_features   bit 0 mean_fband, bit 1 max_fband, bit 2 max_allfbands
+   *   coh_methods    bit 0 coh, bit 1 icoh (coh is required: the reference cannot run without it)
+   *   coh_df         frequency of bin k = k * coh_df (the max_allfbands output)
+   *   coh_cols       a = pair, b = method (coh, icoh); inside a method: band b's enabled (mean, max) slots at
+   *                  b * n_band_features + j, then max_allfbands at coh_n_bands * n_band_features */
+  int32_t coh_n_pairs;
+  const int32_t* coh_pairs;
+  int32_t coh_nperseg;
+  int32_t coh_n_bands;
+  int32_t coh_bin_lo[NMX_MAX_BANDS], coh_bin_hi[NMX_MAX_BANDS];
+  uint32_t coh_features;
+  uint32_t coh_methods;
+  double coh_df;
+  nmx_cols coh_cols;
 } nmx_plan_desc;
 
 typedef struct nmx_plan nmx_plan;
@@ -288,11 +311,11 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
 /* Timing of the last nmx_process_batch, measured with HIP events on the launch stream:
  * which = 0 whole batch, 1 pre-processing, 2 time/oscillatory kernel, 3 FIR-bank kernel,
  * 4 bursts kernels, 5 sharp-wave kernel, 6 second FIR-bank launch (the filters whose taps are too long for the
- * M = 1536 channel-pair kernel; 0 when there is none).  Blocks until the events have completed. */
+ * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
 /* Names of the kernels the first launch sequence of the last nmx_process_batch ran in stage `which`
- * (1..6 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
+ * (1..7 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
  * (template arguments included).  Which variant runs depends on the shape, the batch size and the tuning
  * knobs, so measurement code names the kernel from here instead of hard-coding it.  NUL-terminated,
  * truncated to n - 1 characters. */

@@ -12,14 +12,14 @@ import ctypes as C
 import os
 from pathlib import Path
 
-NMX_ABI_VERSION = 11
+NMX_ABI_VERSION = 12
 NMX_MAX_BANDS = 16
 NMX_MAX_FILTERS = 24
 NMX_MAX_SW_COMBOS = 48
 
 # feature bits (FeatureSelector order, stream/settings.py:41-55)
-F_HJORTH, F_RAW, F_BANDPOWER, F_STFT, F_FFT, F_WELCH, F_SHARPWAVE, F_BURSTS, F_LINELENGTH = (
-    1 << i for i in range(9))
+F_HJORTH, F_RAW, F_BANDPOWER, F_STFT, F_FFT, F_WELCH, F_SHARPWAVE, F_BURSTS, F_LINELENGTH, F_COHERENCE = (
+    1 << i for i in range(10))
 EST_BITS = {"mean": 1, "median": 2, "std": 4, "max": 8}
 SW_FEATURES = ["peak_left", "peak_right", "num_peaks", "trough", "width", "prominence",
                "interval", "decay_time", "rise_time", "sharpness", "rise_steepness",
@@ -70,6 +70,9 @@ class PlanDesc(C.Structure):
         ("raw_norm_method", C.c_int32), ("raw_norm_n", C.c_int32), ("raw_norm_add", C.c_int32),
         ("raw_norm_clip", C.c_float),
         ("segment_length_s", C.c_double),
+        ("coh_n_pairs", C.c_int32), ("coh_pairs", C.POINTER(C.c_int32)), ("coh_nperseg", C.c_int32),
+        ("coh_n_bands", C.c_int32), ("coh_bin_lo", C.c_int32 * NMX_MAX_BANDS), ("coh_bin_hi", C.c_int32 * NMX_MAX_BANDS),
+        ("coh_features", C.c_uint32), ("coh_methods", C.c_uint32), ("coh_df", C.c_double), ("coh_cols", Cols),
     ]
 
 

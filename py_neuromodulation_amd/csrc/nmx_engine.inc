@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/nmx.h"
+#include "nmx_k_coh.h"   // coherence kernel + its be_launch_coh (HIP launcher, or the emulator's loop)
 
 static thread_local std::string g_nmx_err;
 static int nmx_fail(int code, const std::string& msg) {
@@ -96,6 +97,8 @@ struct Plan {
   bool have_bursts = false;
   NmxSharpArgs sharp{};
   bool have_sharp = false;
+  NmxCohArgs coh{};        // coherence between channel pairs (nmx_k_coh.h)
+  bool have_coh = false;
   float* d_R = nullptr;
   bool car = false;      // R = (d - o) I + o 11^T: column-sum kernel instead of the dense product
   float car_diag = 0.f, car_off = 0.f;
@@ -137,7 +140,7 @@ struct Plan {
   int nt_resample = 256;
   double* d_kf = nullptr;
   size_t kf_bytes = 0;
-  be_timer_t timers[7];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split)
+  be_timer_t timers[8];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence
   std::string kernels[8];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
   nmx_norm* norm = nullptr; // attached feature normaliser (not owned): applied to every chunk's rows on the device
   // offset split (nmx_engine_dc.inc): x = u + d per input row, the constants carried in float64 on the host

@@ -160,7 +160,7 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   P->thr_fill = env_int("NMX_THR_FILL", 1) != 0;
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
-  if ((rc = build_timeosc(*P)) || (rc = build_bank(*P)) || (rc = build_notch(*P)) ||
+  if ((rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) || (rc = build_notch(*P)) ||
       (rc = build_bursts(*P)) || (rc = build_sharp(*P)) || (rc = build_kalman(*P)) || (rc = build_resample(*P)) ||
       (rc = build_prefilters(*P)) || (rc = build_rawnorm(*P)) || (rc = dc_build(*P))) {
     std::string keep = g_nmx_err;

@@ -302,3 +302,64 @@ int build_timeosc(Plan& P) {
   return 0;
 }
 
+
+// ---- coherence between channel pairs (nmx_k_coh.h) --------------------------------------------------------------------
+int build_coh(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  if (!(d.features & NMX_F_COHERENCE) || d.coh_n_pairs <= 0) return 0;
+  const int W = d.window, n = d.coh_nperseg, C = d.n_channels;
+  NMX_REQUIRE(d.coh_pairs, "coherence: coh_pairs is NULL");
+  NMX_REQUIRE(n >= 2 && n <= W && n <= NMX_COH_MAX_N,
+              "coherence: nperseg (clamped to the window) must lie in [2, 4096]");
+  NMX_REQUIRE(d.coh_methods & 1u, "coherence: method coh must be enabled (the reference fails without it)");
+  NMX_REQUIRE(d.coh_n_bands >= 0 && d.coh_n_bands <= NMX_MAX_BANDS_DEV, "coherence: too many bands");
+  NmxCohArgs& A = P.coh;
+  A = NmxCohArgs{};
+  A.n = n;
+  A.step = n - n / 2;
+  A.nseg = (W - n) / A.step + 1;
+  A.nfreq = n / 2 + 1;
+  A.W = W;
+  A.n_outputs = d.n_outputs;
+  A.n_pairs = d.coh_n_pairs;
+  A.n_bands = d.coh_n_bands;
+  for (int b = 0; b < d.coh_n_bands; ++b) {
+    NMX_REQUIRE(0 <= d.coh_bin_lo[b] && d.coh_bin_lo[b] <= d.coh_bin_hi[b] && d.coh_bin_hi[b] <= A.nfreq,
+                "coherence: band bin range outside the frequency grid");
+    A.bin_lo[b] = d.coh_bin_lo[b];
+    A.bin_hi[b] = d.coh_bin_hi[b];
+  }
+  A.feats = d.coh_features & 7u;
+  A.methods = d.coh_methods & 3u;
+  A.df = d.coh_df;
+  A.cols = cv(d.coh_cols);
+  // every column the plan writes must lie inside the row
+  const int nfb = (int)(A.feats & 1u) + (int)((A.feats >> 1) & 1u);
+  const int slots = d.coh_n_bands * nfb + ((A.feats & 4u) ? 1 : 0);
+  const int n_meth = (A.methods & 2u) ? 2 : 1;
+  if (slots > 0) {
+    const long long last = (long long)A.cols.base + (long long)(A.n_pairs - 1) * A.cols.a_stride +
+                           (long long)(n_meth - 1) * A.cols.b_stride + (slots - 1);
+    NMX_REQUIRE(A.cols.base >= 0 && A.cols.a_stride >= 0 && A.cols.b_stride >= 0 && last < d.n_outputs,
+                "coherence: output columns outside the row");
+  }
+  std::vector<int> pairs(2 * (size_t)A.n_pairs);
+  for (int i = 0; i < 2 * A.n_pairs; ++i) {
+    NMX_REQUIRE(d.coh_pairs[i] >= 0 && d.coh_pairs[i] < C, "coherence: pair channel index out of range");
+    pairs[i] = d.coh_pairs[i];
+  }
+  int rc = build_fft(P, n, &A.fft);
+  if (rc) return rc;
+  std::vector<float> win(n);
+  for (int i = 0; i < n; ++i) win[i] = (float)(0.5 - 0.5 * std::cos(2.0 * kPi * (double)i / (double)n));   // periodic Hann
+  A.win = (const float*)upload(P, win.data(), win.size() * sizeof(float));
+  A.pairs = (const int*)upload(P, pairs.data(), pairs.size() * sizeof(int));
+  if (!A.win || !A.pairs) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+  A.off_a = 0;
+  A.off_b = 2 * n;
+  A.off_acc = 4 * n;
+  A.off_red = A.off_acc + 4 * al4(A.nfreq);
+  A.lds_floats = A.off_red + 64 + 2 * 128 + 16;
+  P.have_coh = true;
+  return 0;
+}

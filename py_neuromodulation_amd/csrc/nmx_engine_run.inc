@@ -313,6 +313,15 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     if (tev) be_timer_stop(P.timers[2], s);
     if (redo) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }   // (windows the kernel flagged: NaN / infinity on load; outside the stage's timer and kernel list)
   }
+  if (P.have_coh) {   // coherence between channel pairs: stateless, on the main stream behind the time / oscillatory kernel
+    NmxCohArgs A = P.coh;
+    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
+    A.out = d_out; A.clean_on_load = clean;
+    if (tev) be_timer_start(P.timers[7], s);
+    be_stage(7);
+    be_launch_coh(A, nw * A.n_pairs, s);
+    if (tev) be_timer_stop(P.timers[7], s);
+  }
   if (!sharp_side && (rc = launch_sharp(s))) return rc;
   // (no join on the main stream: the chunk is finished by chunk_finalize below, on its own stream)
   be_event_record(P.ev_main[par], s);
@@ -727,7 +736,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
 
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms) {
   Plan* P = (Plan*)plan;
-  if (!P || !ms || which < 0 || which > 6) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !ms || which < 0 || which > 7) return nmx_fail(NMX_E_INVALID, "bad argument");
   be_set_device(P->device);
   *ms = be_timer_elapsed(P->timers[which]);
   return 0;
@@ -853,7 +862,7 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
-  if (!P || !buf || n < 1 || which < 1 || which > 6) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !buf || n < 1 || which < 1 || which > 7) return nmx_fail(NMX_E_INVALID, "bad argument");
   const std::string& k = P->kernels[which];
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
   memcpy(buf, k.data(), m);

@@ -220,6 +220,11 @@ class DataProcessor:
         self.local_groups = []      # local_inputs: member rows (global) of every group sum it expects
         if channel_subset is not None:
             subset = list(channel_subset)
+            if ("coherence" in st.features.get_enabled() and st.coherence_settings.channels
+                    and sorted(subset) != list(range(len(self.ch_names_used)))):
+                # a pair may join channels of two shards; the plan of one shard sees its own channels only
+                raise NotImplementedError("coherence needs both channels of every pair in one plan: it is not supported "
+                                          "with channels sharded over several devices (use one device)")
             if full is None:
                 full = np.eye(n_all)
             full = full[subset]

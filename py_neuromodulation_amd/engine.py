@@ -30,8 +30,9 @@ from .settings import validation_error
 _FEATURE_BITS = {"raw_hjorth": _lib.F_HJORTH, "return_raw": _lib.F_RAW,
                  "bandpass_filter": _lib.F_BANDPOWER, "stft": _lib.F_STFT, "fft": _lib.F_FFT,
                  "welch": _lib.F_WELCH, "sharpwave_analysis": _lib.F_SHARPWAVE,
-                 "bursts": _lib.F_BURSTS, "linelength": _lib.F_LINELENGTH}
-_OUT_OF_SCOPE = {"fooof", "nolds", "coherence", "mne_connectivity", "bispectrum"}
+                 "bursts": _lib.F_BURSTS, "linelength": _lib.F_LINELENGTH, "coherence": _lib.F_COHERENCE}
+_OUT_OF_SCOPE = {"fooof", "nolds", "mne_connectivity", "bispectrum"}
+COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel
 _BURST_SLOTS = [("duration", ["duration_mean", "duration_max"]),
                 ("amplitude", ["amplitude_mean", "amplitude_max"]),
                 ("burst_rate_per_s", ["burst_rate_per_s"]), ("in_burst", ["in_burst"])]
@@ -373,6 +374,7 @@ class HotPathEngine:
         if len(self._pre_taps) > 4:
             raise ValueError("at most 4 preprocessing_filter stages")
         self.keys: list[str] = []
+        self.coh_pairs: list[tuple[int, int]] = []   # coherence: (seed, target) channel indices of the emitted pairs
         self.desc = self._build(ref_matrix, notch_taps, device, bank_taps, sharpwave_taps)
         self.n_outputs = len(self.keys)
         self.C_in = int(self.desc.n_channels_in)
@@ -573,6 +575,8 @@ class HotPathEngine:
                 col += C_ * len(names) * len(slots)
             elif f == "sharpwave_analysis":
                 col = self._sharpwave(d, filters, col, sharpwave_taps)
+            elif f == "coherence":
+                col = self._coherence(d, col)
         d.features = feats
         d.n_outputs = col
         if len(filters) > _lib.NMX_MAX_FILTERS:
@@ -663,6 +667,89 @@ class HotPathEngine:
                         self.keys += [s.format(ch=ch, fn=fn) + "_analyze_" + p for p in pols]
             col += C_ * NF * len(slots) * npol
         return col
+
+    def _coherence(self, d: PlanDesc, col: int) -> int:
+        """features/coherence.py: the reference's construction-time checks (Coherence.test_settings), the pairs resolved
+        by name prefix, bins of scipy's float64 grid with strict band edges, keys pair by pair."""
+        st, sfreq = self.settings, self.sfreq
+        cs = st.coherence_settings
+        pairs = [list(p) for p in cs.channels]
+        for ch_coh in [ch for p in pairs for ch in p]:
+            hits = sum(ch.startswith(ch_coh) for ch in self.ch_names)
+            if hits == 0:
+                raise RuntimeError(f"Coherence selected channel {ch_coh} does not match any channel name: \n"
+                                   f"  - settings.coherence_settings.channels: {cs.channels}\n"
+                                   f"  - ch_names: {self.ch_names} \n")
+            if hits > 1:
+                raise RuntimeError(f"Coherence selected channel {ch_coh} is ambigous and matches more than one channel "
+                                   f"name: \n  - settings.coherence_settings.channels: {cs.channels}\n"
+                                   f"  - ch_names: {self.ch_names} \n")
+        band_names = [str(b).replace(" ", "_") for b in cs.frequency_bands]
+        ranges = st.frequency_ranges_hz
+        if not all(b in ranges for b in band_names):
+            raise AssertionError("coherence selected frequency bands don't match the ones specified in "
+                                 f"s['frequency_ranges_hz'] coherence frequency bands: {band_names} specified "
+                                 f"frequency_ranges_hz: {ranges}")
+        if not all(ranges[b][0] < sfreq / 2 and ranges[b][1] < sfreq / 2 for b in band_names):
+            raise AssertionError("the coherence frequency band ranges need to be smaller than the Nyquist frequency "
+                                 f"got sfreq = {sfreq} and fband ranges {band_names}")
+        if len(band_names) > _lib.NMX_MAX_BANDS:
+            raise ValueError(f"at most {_lib.NMX_MAX_BANDS} coherence frequency bands are supported")
+        feats = _enabled(cs.features)
+        use_coh, use_icoh = bool(cs.method.coh), bool(cs.method.icoh)
+        nfb = ("mean_fband" in feats) + ("max_fband" in feats)
+        slots = len(band_names) * nfb + ("max_allfbands" in feats)
+        if not pairs or slots == 0:
+            return col   # (no pair, or nothing to compute: the reference emits no key either)
+        if not use_coh:
+            # get_coh reads the coh values for every method (coherence.py:104-117): the reference raises
+            # UnboundLocalError on its first window
+            raise ValueError("coherence_settings.method.coh = False: the reference cannot run this setting "
+                             "(CoherenceObject.get_coh fails with UnboundLocalError on its first window)")
+        n = min(int(cs.nperseg), self.W)   # scipy.signal.welch: nperseg > len(x) -> len(x)
+        if n < 2 or n > COH_MAX_NPERSEG:
+            raise ValueError(f"coherence: nperseg {n} (after the clamp to the {self.W}-sample window) must lie in "
+                             f"[2, {COH_MAX_NPERSEG}]")
+        freqs = np.fft.rfftfreq(n, 1 / sfreq)
+        for b, name in enumerate(band_names):
+            lo, hi = float(ranges[name][0]), float(ranges[name][1])
+            idx = np.where((freqs > lo) & (freqs < hi))[0]
+            if not idx.size and "max_fband" in feats:   # np.max over an empty band (coherence.py:136)
+                raise ValueError("zero-size array to reduction operation maximum which has no identity "
+                                 f"(coherence: band {name} holds no bin of the {len(freqs)}-bin grid)")
+            d.coh_bin_lo[b] = int(idx[0]) if idx.size else 0
+            d.coh_bin_hi[b] = int(idx[-1]) + 1 if idx.size else 0
+        # a pair listed twice writes the same keys with the same values (they keep their first position)
+        seen, index = set(), []
+        methods = ["coh"] + (["icoh"] if use_icoh else [])   # icoh off: the coh keys are written twice
+        for c1, c2 in pairs:
+            if (c1, c2) in seen:
+                continue
+            seen.add((c1, c2))
+            i1 = next(i for i, ch in enumerate(self.ch_names) if ch.startswith(c1))
+            i2 = next(i for i, ch in enumerate(self.ch_names) if ch.startswith(c2))
+            index += [i1, i2]
+            for m in methods:
+                for name in band_names:
+                    if "mean_fband" in feats:
+                        self.keys.append(f"{m}_{c1}_to_{c2}_mean_fband_{name}")
+                    if "max_fband" in feats:
+                        self.keys.append(f"{m}_{c1}_to_{c2}_max_fband_{name}")
+                if "max_allfbands" in feats:
+                    self.keys.append(f"{m}_{c1}_to_{c2}_max_allfbands_{band_names[-1]}")
+        n_pairs = len(index) // 2
+        idx_arr = np.ascontiguousarray(index, dtype=np.int32)
+        self._keep.append(idx_arr)
+        d.coh_n_pairs = n_pairs
+        d.coh_pairs = idx_arr.ctypes.data_as(C.POINTER(C.c_int32))
+        d.coh_nperseg = n
+        d.coh_n_bands = len(band_names)
+        d.coh_features = sum(1 << i for i, f in enumerate(["mean_fband", "max_fband", "max_allfbands"]) if f in feats)
+        d.coh_methods = 1 | (2 if use_icoh else 0)
+        d.coh_df = float(freqs[1] if len(freqs) > 1 else 0.0)
+        d.coh_cols = _cols(col, 0, len(methods) * slots, slots)
+        self.coh_pairs = [(int(index[2 * i]), int(index[2 * i + 1])) for i in range(n_pairs)]
+        return col + n_pairs * len(methods) * slots
 
     # ------------------------------------------------------------------------------------
     def close(self) -> None:
@@ -1029,8 +1116,8 @@ class HotPathEngine:
 
     def kernels(self, which: int) -> str:
         """Kernels the last batch launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
-        5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel),
-        named as rocprofv3 prints them."""
+        5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
+        7 coherence), named as rocprofv3 prints them."""
         buf = C.create_string_buffer(512)
         self.lib.check(self.lib.lib.nmx_last_kernels(self._plan, which, buf, 512))
         return buf.value.decode()

@@ -22,7 +22,7 @@ from .engine import MAX_PLAN_WINDOW, HotPathEngine, long_segments
 FEATURE_DICT = {  # features/feature_processor.py:10-25 (hot-path subset)
     "raw_hjorth": "Hjorth", "return_raw": "Raw", "bandpass_filter": "BandPower", "stft": "STFT",
     "fft": "FFT", "welch": "Welch", "sharpwave_analysis": "SharpwaveAnalyzer", "bursts": "Bursts",
-    "linelength": "LineLength",
+    "linelength": "LineLength", "coherence": "Coherence",
 }
 
 
@@ -122,6 +122,11 @@ class Bursts(_EngineFeature):
 class SharpwaveAnalyzer(_EngineFeature):
     """features/sharpwaves.py:100-465"""
     feature_name = "sharpwave_analysis"
+
+
+class Coherence(_EngineFeature):
+    """features/coherence.py:151-253: coh / icoh between the channel pairs of ``coherence_settings.channels``"""
+    feature_name = "coherence"
 
 
 class HotPathFeatures(_EngineFeature):

@@ -237,6 +237,10 @@ def _default_dict() -> dict:
             "estimator": {"mean": ["interval"], "median": [], "max": ["prominence", "sharpness"],
                           "min": [], "var": []},
             "apply_estimator_between_peaks_and_troughs": True},
+        # default_settings.yaml:188-199 (the YAML's nperseg 128 is in force, not the pydantic class default of 256)
+        "coherence_settings": {"channels": [], "frequency_bands": ["high_beta"],
+                               "features": {"mean_fband": True, "max_fband": True, "max_allfbands": True},
+                               "method": {"coh": True, "icoh": True}, "nperseg": 128},
     }
 
 
@@ -268,10 +272,42 @@ def _build(key: str, v: Any) -> Any:
         return {str(k).replace(" ", "_"): int(x) for k, x in v.items()}
     if key == "features" and isinstance(v, dict) and set(v) <= {"mean", "median", "std", "max"}:
         return BoolSelector(**{k: bool(v.get(k, False)) for k in ("mean", "median", "std", "max")})
+    if key == "coherence_settings" and isinstance(v, dict):
+        return CoherenceSettings(**v)
     if isinstance(v, dict):
         cls = FeatureSelector if key == "features" else BoolSelector if key in _SELECTOR_KEYS else _Node
         return cls(**{k: _build(k, x) for k, x in v.items()})
     return copy.deepcopy(v)
+
+
+class CoherenceSettings(_Node):
+    """features/coherence.py:39-49.  ``features`` and ``method`` are switch sets (``get_enabled()``) also when a plain dict
+    is assigned at run time, as the reference's own tests/test_coherence.py does; band names get underscores for spaces
+    (the reference's field validator)."""
+
+    _SWITCHES = {"features": ("mean_fband", "max_fband", "max_allfbands"), "method": ("coh", "icoh")}
+
+    def __setattr__(self, key, value) -> None:
+        if key in self._SWITCHES and isinstance(value, dict):
+            value = BoolSelector(**{k: bool(v) for k, v in value.items()})
+        elif key == "frequency_bands" and isinstance(value, (list, tuple)):
+            value = [str(f).replace(" ", "_") for f in value]
+        elif key == "channels" and isinstance(value, (list, tuple)):
+            value = [list(p) if isinstance(p, (list, tuple)) else p for p in value]
+        super().__setattr__(key, value)
+
+    def errors(self) -> list[str]:
+        """What the reference's pydantic model rejects: pairs of exactly two strings, nperseg >= 1, at least one band."""
+        out = []
+        for p in self.channels:
+            if not (isinstance(p, list) and len(p) == 2 and all(isinstance(c, str) for c in p)):
+                out.append(f"coherence_settings.channels: every entry must be a list of two channel names, got {p!r}")
+        n = self.nperseg
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            out.append(f"coherence_settings.nperseg must be an int >= 1, got {n!r}")
+        if len(self.frequency_bands) < 1:
+            out.append("coherence_settings.frequency_bands needs at least one band")
+        return out
 
 
 class NMSettings(_Node):
@@ -372,6 +408,7 @@ class NMSettings(_Node):
                 errors.append(f"Add estimator key for {f}")
         if self.bursts_settings.threshold < 0 or self.bursts_settings.time_duration_s < 0:
             errors.append("bursts_settings threshold / time_duration_s must be >= 0")
+        errors += self.coherence_settings.errors()
         if errors:
             raise SettingsError("; ".join(errors))
 
