@@ -42,6 +42,23 @@ struct Buf {
   size_t cap = 0;
 };
 
+// A FIR stage -- a preprocessing_filter stage, the notch or the band-pass bank -- with its kernels decided at plan time
+// (nmx_engine_plan_fir.inc: build_fir_stage, launch_fir_stage).  One launch of its one-wave kernels: the filters of
+// `mask` with the channel-pair tables of nmx_k_bank_w64c/d/e.h (hc = nullptr: one channel per transform).
+struct FirLaunch {
+  unsigned mask = 0;
+  const float* hc = nullptr;
+  const float* twc = nullptr;
+  int pair_m = 0;
+  int stage = 3;       // timer / kernel-name stage it reports under (6: the bank's second launch)
+};
+struct FirStage {
+  NmxBankArgs a{};     // argument template (per-call fields are patched in by the caller)
+  bool w64 = false;    // one-wave kernels (M = 2048 / 4096) ...
+  NmxBankW64Args w{};  // ... and their template
+  std::vector<FirLaunch> launches;   // (the LDS kernels: one entry, for its stage)
+};
+
 struct Plan {
   nmx_plan_desc d;
   std::vector<std::vector<double>> taps;   // deep copies
@@ -73,22 +90,12 @@ struct Plan {
   // kernel argument templates (per-call fields are patched in process_batch)
   NmxTimeOscArgs to{};
   bool have_to = false;
-  NmxBankArgs bank{};
+  FirStage bank;                      // band-pass bank: feeds bursts and sharp waves
   bool have_bank = false;
-  NmxBankArgs notch{};
+  FirStage notch;
   bool have_notch = false;
-  NmxBankW64Args bankw{}, notchw{};   // fast single-wave path (M == 2048)
-  bool bank_w64 = false, notch_w64 = false;
-  bool bank_w64x2 = false;            // M = 4096 one-wave path (nmx_k_bank_w64x2.h); implies bank_w64
-  bool bank_w64c = false;             // M = 1536 channel-pair path (nmx_k_bank_w64c.h) for the filters of w64c_mask; implies bank_w64
-  bool bank_timer_closed = false;     // this chunk's stage-3 timer was stopped between the two bank launches
-  unsigned w64c_mask = 0;
-  int w64c_m = 1536;                  // 1536 (nmx_k_bank_w64c.h) or 1024 (nmx_k_bank_w64d.h: every selected filter fits 1024)
-  const float* w64c_hc = nullptr;
-  const float* w64c_twc = nullptr;
-  bool bank_w64e = false;             // M = 2048 channel-pair path (nmx_k_bank_w64e.h) for the filters the M = 1536 kernel leaves
-  const float* w64e_hc_bank = nullptr;
-  const float* w64e_tw = nullptr;     // its twiddles (shared with the notch)
+  std::vector<FirStage> pre;          // preprocessing_filter stages (one filter each)
+  const float* w64e_tw = nullptr;     // twiddles of the M = 2048 channel-pair kernel (nmx_k_bank_w64e.h): notch and bank
   NmxHilbertArgs hil{};
   const float* w500_tab = nullptr;
   int nt_hilbert = 128;
@@ -133,9 +140,6 @@ struct Plan {
   long long rn_hops = 0;
   size_t rn_ring_bytes = 0, rn_cnt_bytes = 0, rn_len_bytes = 0;
   std::vector<std::vector<double>> pre_taps;
-  std::vector<NmxBankArgs> pf;          // preprocessing_filter stages (one single-filter bank each)
-  std::vector<NmxBankW64Args> pfw;
-  std::vector<char> pf_w64;
   int w_in = 0;           // samples per incoming window (raw_window when resampling, else window)
   int nt_resample = 256;
   double* d_kf = nullptr;

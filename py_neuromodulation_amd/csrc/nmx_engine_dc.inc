@@ -61,8 +61,8 @@ static void dc_recompute(Plan& P, be_stream_t s) {
 }
 
 static int dc_build(Plan& P) {
-  P.dc_ok = env_int("NMX_DC_SPLIT", 1) != 0 && !P.have_resample && !P.have_rawnorm && P.pf.empty() &&
-            (!P.have_notch || P.notch.pad_half <= P.notch.n_edge);
+  P.dc_ok = env_int("NMX_DC_SPLIT", 1) != 0 && !P.have_resample && !P.have_rawnorm && P.pre.empty() &&
+            (!P.have_notch || P.notch.a.pad_half <= P.notch.a.n_edge);
   P.dc_auto = env_int("NMX_DC_AUTO", 1) != 0;
   P.dc_gain = 1.0;
   if (P.have_notch) {

@@ -1,8 +1,7 @@
 // nmx_engine_plan_fir.inc -- plan building, part 2: FIR work -- tap spectra, the one-wave kernels' tables (M = 1024 /
 // 1536 / 2048 / 4096), partitioned overlap-save mode, band-pass bank, notch, Hilbert.  Included by nmx_engine.inc.
-// real spectrum of circularly centred symmetric taps, pre-scaled by 1/M
-int filter_spectrum(Plan& P, const double* h, int L, int M, const float** out,
-                    std::vector<float>* host_copy = nullptr) {
+// real spectrum H[0 .. M / 2] of circularly centred symmetric taps, pre-scaled by 1/M
+int host_spectrum(const double* h, int L, int M, std::vector<float>* out) {
   NMX_REQUIRE(L >= 1 && (L & 1), "FIR taps must have odd length (zero-phase)");
   const int half = (L - 1) / 2;
   double amax = 0;
@@ -11,7 +10,8 @@ int filter_spectrum(Plan& P, const double* h, int L, int M, const float** out,
     NMX_REQUIRE(std::fabs(h[half + j] - h[half - j]) <= 1e-9 * amax + 1e-300,
                 "FIR taps must be symmetric (linear phase)");
   const int Mh = M / 2;
-  std::vector<float> H(Mh + 1);
+  std::vector<float>& H = *out;
+  H.assign(Mh + 1, 0.f);
   // cos(2 pi j k / M) via a table of cos(2 pi i / M), index (j * k) mod M
   std::vector<double> ct(M);
   for (int i = 0; i < M; ++i) ct[i] = std::cos(2.0 * kPi * i / M);
@@ -25,9 +25,14 @@ int filter_spectrum(Plan& P, const double* h, int L, int M, const float** out,
     }
     H[k] = (float)(acc / M);
   }
-  *out = (const float*)upload(P, H.data(), H.size() * sizeof(float));
+  return 0;
+}
+// ... uploaded to `out`; the host copy stays in `H`
+int filter_spectrum(Plan& P, const double* h, int L, int M, const float** out, std::vector<float>* H) {
+  int rc = host_spectrum(h, L, M, H);
+  if (rc) return rc;
+  *out = (const float*)upload(P, H->data(), H->size() * sizeof(float));
   if (!*out) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  if (host_copy) *host_copy = H;
   return 0;
 }
 
@@ -106,36 +111,40 @@ int build_w64x2(Plan& P, const NmxBankArgs& A, const std::vector<std::vector<flo
   return 0;
 }
 
-// M = 1536 channel-pair path (nmx_k_bank_w64c.h): the REAL spectrum of every filter at M = 1536 in the register order
-// of the transform's output (k of lane qa + 8 u, register 8 g + qb: u + 8 g + 24 (qa + 8 qb)), two registers per
-// 8-byte entry; pass-A twiddles exp(-2 pi i l ka / 1536) by [register 8 r + p: ka = 3 p + r][lane]; exp(-2 pi i a b / 64)
-int build_w64c(Plan& P, const NmxBankArgs& A, unsigned mask, int M) {
-  P.w64c_m = M;
+// Channel-pair tables of one launch (nmx_k_bank_w64c.h: M = 1536, nmx_k_bank_w64d.h: M = 1024, nmx_k_bank_w64e.h:
+// M = 2048): the REAL spectra H[fi][0 .. M / 2] of the filters of `mask`, in the register order of the transform's output
+// (M = 1536 / 2048: k of lane qa + 8 u, register 8 g + qb is u + 8 g + (M / 64) (qa + 8 qb); M = 1024: natural order,
+// k = lane + 64 reg), two registers per 8-byte entry.  Twiddles: pass A exp(-2 pi i l ka / M) by [register 8 r + p:
+// ka = R p + r][lane] with R = 3 (M = 1024 / 1536: the M = 1024 kernel reads twl instead) or 4, then exp(-2 pi i a b / 64);
+// the M = 2048 ones are shared by every use.
+int build_pair_tables(Plan& P, int M, unsigned mask, const std::vector<std::vector<float>>& H, FirLaunch* L) {
   std::vector<float> hc;
   int n_sel = 0;
-  for (int fi = 0; fi < A.n_filters; ++fi) {
+  for (int fi = 0; fi < (int)H.size(); ++fi) {
     if (!((mask >> fi) & 1u)) continue;
     const int i = n_sel++;
     hc.resize((size_t)n_sel * M);
-    const int L = P.d.filters[fi].n_taps, half = (L - 1) / 2, uh = std::min(half, A.W - 1);
-    const float* dev = nullptr;
-    std::vector<float> H;
-    int rc = filter_spectrum(P, P.taps[fi].data() + (half - uh), 2 * uh + 1, M, &dev, &H);
-    if (rc) return rc;
     for (int pr = 0; pr < M / 128; ++pr)
       for (int lane = 0; lane < 64; ++lane)
         for (int e = 0; e < 2; ++e) {
           const int reg = 2 * pr + e, qa = lane & 7, u = lane >> 3, g = reg >> 3, qb = reg & 7;
-          // M = 1536: the transform's output order; M = 1024 (nmx_k_bank_w64d.h): natural order, k = lane + 64 reg
-          const int k = M == 1536 ? u + 8 * g + 24 * (qa + 8 * qb) : lane + 64 * reg;
-          hc[(size_t)i * M + (size_t)(pr * 64 + lane) * 2 + e] = H[k <= M / 2 ? k : M - k];
+          const int k = M == 1024 ? lane + 64 * reg : u + 8 * g + M / 64 * (qa + 8 * qb);
+          hc[(size_t)i * M + (size_t)(pr * 64 + lane) * 2 + e] = H[fi][k <= M / 2 ? k : M - k];
         }
   }
-  P.w64c_hc = (const float*)upload(P, hc.data(), hc.size() * sizeof(float));
-  std::vector<float> tw(2 * 24 * 64 + 2 * 64);
-  for (int reg = 0; reg < 24; ++reg)
+  L->mask = mask;
+  L->pair_m = M;
+  L->hc = (const float*)upload(P, hc.data(), hc.size() * sizeof(float));
+  if (!L->hc) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+  if (M == 2048 && P.w64e_tw) {
+    L->twc = P.w64e_tw;
+    return 0;
+  }
+  const int n_reg = M == 2048 ? 32 : 24, R = n_reg / 8;
+  std::vector<float> tw(2 * n_reg * 64 + 2 * 64);
+  for (int reg = 0; reg < n_reg; ++reg)
     for (int l = 0; l < 64; ++l) {
-      const int ka = 3 * (reg & 7) + (reg >> 3);
+      const int ka = R * (reg & 7) + (reg >> 3);
       const double a = -2.0 * kPi * (double)(l * ka) / (double)M;
       tw[2 * (reg * 64 + l)] = (float)std::cos(a);
       tw[2 * (reg * 64 + l) + 1] = (float)std::sin(a);
@@ -143,111 +152,68 @@ int build_w64c(Plan& P, const NmxBankArgs& A, unsigned mask, int M) {
   for (int a = 0; a < 8; ++a)
     for (int b = 0; b < 8; ++b) {
       const double th = -2.0 * kPi * (double)(a * b) / 64.0;
-      tw[2 * 24 * 64 + 2 * (a * 8 + b)] = (float)std::cos(th);
-      tw[2 * 24 * 64 + 2 * (a * 8 + b) + 1] = (float)std::sin(th);
+      tw[2 * n_reg * 64 + 2 * (a * 8 + b)] = (float)std::cos(th);
+      tw[2 * n_reg * 64 + 2 * (a * 8 + b) + 1] = (float)std::sin(th);
     }
-  P.w64c_twc = (const float*)upload(P, tw.data(), tw.size() * sizeof(float));
-  if (!P.w64c_hc || !P.w64c_twc) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  P.w64c_mask = mask;
+  L->twc = (const float*)upload(P, tw.data(), tw.size() * sizeof(float));
+  if (!L->twc) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+  if (M == 2048) P.w64e_tw = L->twc;
   return 0;
 }
 
-// M = 2048 channel-pair path (nmx_k_bank_w64e.h): the REAL spectrum (M = 2048, from the float tables of build_bank /
-// build_notch) of the filters of `mask` in the register order of that transform's output (k of lane qa + 8 u, register
-// 8 g + qb: u + 8 g + 32 (qa + 8 qb)), two registers per 8-byte entry; the twiddles are shared by every use
-int build_w64e(Plan& P, int n_filters, unsigned mask, const std::vector<std::vector<float>>& Hhost, const float** hc_out) {
-  const int M = 2048;
-  std::vector<float> hc;
-  int n_sel = 0;
-  for (int fi = 0; fi < n_filters; ++fi) {
-    if (!((mask >> fi) & 1u)) continue;
-    const int i = n_sel++;
-    hc.resize((size_t)n_sel * M);
-    const std::vector<float>& H = Hhost[fi];   // H[0 .. M / 2]
-    for (int pr = 0; pr < 16; ++pr)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 2; ++e) {
-          const int reg = 2 * pr + e, qa = lane & 7, u = lane >> 3, g = reg >> 3, qb = reg & 7;
-          const int k = u + 8 * g + 32 * (qa + 8 * qb);
-          hc[(size_t)i * M + (size_t)(pr * 64 + lane) * 2 + e] = H[k <= M / 2 ? k : M - k];
-        }
-  }
-  *hc_out = (const float*)upload(P, hc.data(), hc.size() * sizeof(float));
-  if (!*hc_out) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  if (!P.w64e_tw) {
-    std::vector<float> tw(2 * 32 * 64 + 2 * 64);
-    for (int reg = 0; reg < 32; ++reg)
-      for (int l = 0; l < 64; ++l) {
-        const int ka = 4 * (reg & 7) + (reg >> 3);
-        const double a = -2.0 * kPi * (double)(l * ka) / (double)M;
-        tw[2 * (reg * 64 + l)] = (float)std::cos(a);
-        tw[2 * (reg * 64 + l) + 1] = (float)std::sin(a);
-      }
-    for (int a = 0; a < 8; ++a)
-      for (int b = 0; b < 8; ++b) {
-        const double th = -2.0 * kPi * (double)(a * b) / 64.0;
-        tw[2 * 32 * 64 + 2 * (a * 8 + b)] = (float)std::cos(th);
-        tw[2 * 32 * 64 + 2 * (a * 8 + b) + 1] = (float)std::sin(th);
-      }
-    P.w64e_tw = (const float*)upload(P, tw.data(), tw.size() * sizeof(float));
-    if (!P.w64e_tw) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  }
-  return 0;
-}
-
-// copy of a w64 bank restricted to the filters of `mask`
-static NmxBankW64Args bank_subset_mask(const NmxBankW64Args& A, unsigned mask) {
-  NmxBankW64Args B = A;
+// the one-wave arguments of launch L: the filters of L.mask (in their order) and L's pair tables
+static NmxBankW64Args fir_launch_args(const NmxBankW64Args& W, const FirLaunch& L) {
+  NmxBankW64Args B = W;
   int n = 0;
-  for (int i = 0; i < A.b.n_filters; ++i) {
-    if (!((mask >> i) & 1u)) continue;
-    B.b.f[n] = A.b.f[i];
-    B.Hs[n] = A.Hs[i];
-    B.Hd[n] = A.Hd[i];
+  for (int i = 0; i < W.b.n_filters; ++i) {
+    if (!((L.mask >> i) & 1u)) continue;
+    B.b.f[n] = W.b.f[i];
+    B.Hs[n] = W.Hs[i];
+    B.Hd[n] = W.Hd[i];
     ++n;
   }
   B.b.n_filters = n;
+  B.hc = L.hc;
+  B.twc = L.twc;
+  B.pair_m = L.pair_m;
   return B;
 }
-// The filters of a w64 bank in two launches: the channel-pair kernel over the filters it can take (stage 3), the
-// M = 2048 kernel over the others (stage 6: with the default settings the two 1651-tap sharp-wave filters, whose "same"
-// convolution needs M >= 1825).
-// do the kernels bank_launch_all would launch take the carried offset on load (NmxBankArgs::dcf)?
-static bool bank_w64_takes_dc(Plan& P, const NmxBankW64Args& AW, int n_items) {
-  if (!P.bank_w64c) {
-    NmxBankW64Args E = AW;
-    if (P.bank_w64e) { E.hc = P.w64e_hc_bank; E.twc = P.w64e_tw; E.pair_m = 2048; }
-    return be_bank_w64_takes_dc(E, n_items);
-  }
-  NmxBankW64Args Cc = bank_subset_mask(AW, P.w64c_mask);
-  Cc.hc = P.w64c_hc; Cc.twc = P.w64c_twc; Cc.pair_m = P.w64c_m;
-  if (!be_bank_w64_takes_dc(Cc, n_items)) return false;
-  NmxBankW64Args R = bank_subset_mask(AW, ~P.w64c_mask);
-  if (R.b.n_filters == 0) return true;
-  if (P.bank_w64e) { R.hc = P.w64e_hc_bank; R.twc = P.w64e_tw; R.pair_m = 2048; }
-  return be_bank_w64_takes_dc(R, n_items);
+
+// do the kernels launch_fir_stage would launch take the carried offset on load (NmxBankArgs::dcf)?
+static bool fir_stage_takes_dc(const FirStage& S, int n_items) {
+  if (!S.w64) return true;
+  NmxBankW64Args W = S.w;
+  W.b = S.a;
+  for (const FirLaunch& L : S.launches)
+    if (!be_bank_w64_takes_dc(fir_launch_args(W, L), n_items)) return false;
+  return true;
 }
 
-static void bank_launch_all(Plan& P, const NmxBankW64Args& AW, int n_items, be_stream_t s, bool timed = false) {
-  if (!P.bank_w64c) {
-    NmxBankW64Args E = AW;
-    if (P.bank_w64e) { E.hc = P.w64e_hc_bank; E.twc = P.w64e_tw; E.pair_m = 2048; }   // every filter on the M = 2048 pair kernel
-    be_launch_bank_w64(E, n_items, (size_t)AW.lds_floats * 4, s);
-    return;
+// Launches FIR stage S over n_items (window, channel) items; A = S.a with the per-call fields patched in (A.yb_out: the
+// band series for the stand-alone Hilbert kernel).  The bank's filters may take two launches: the channel-pair kernel over
+// those it can take, the M = 2048 kernel over the others (stage 6: with the default settings the two 1651-tap sharp-wave
+// filters, whose "same" convolution needs M >= 1825).  `timed`: each launch's stage timer runs around it.
+static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, int n_items, be_stream_t s, bool timed = false) {
+  const int first = S.launches[0].stage;
+  int cur = first;
+  if (timed) be_timer_start(P.timers[cur], s);
+  if (!S.w64) {
+    be_launch_bank(A, n_items, P.nt_bank, (size_t)A.lds_floats * 4, s);
+  } else {
+    NmxBankW64Args W = S.w;
+    W.b = A;
+    W.yb_out = A.yb_out;   // (the one-wave kernels take the band series through their own field)
+    W.b.yb_out = nullptr;
+    for (const FirLaunch& L : S.launches) {
+      if (L.stage != cur) {
+        if (timed) { be_timer_stop(P.timers[cur], s); be_timer_start(P.timers[L.stage], s); }
+        be_stage(cur = L.stage);
+      }
+      be_launch_bank_w64(fir_launch_args(W, L), n_items, (size_t)W.lds_floats * 4, s);
+    }
+    if (cur != first) be_stage(first);
   }
-  NmxBankW64Args Cc = bank_subset_mask(AW, P.w64c_mask);
-  Cc.hc = P.w64c_hc;
-  Cc.twc = P.w64c_twc;
-  Cc.pair_m = P.w64c_m;
-  be_launch_bank_w64(Cc, n_items, (size_t)AW.lds_floats * 4, s);
-  NmxBankW64Args R = bank_subset_mask(AW, ~P.w64c_mask);
-  if (R.b.n_filters == 0) return;
-  if (P.bank_w64e) { R.hc = P.w64e_hc_bank; R.twc = P.w64e_tw; R.pair_m = 2048; }   // (tables in the subset's filter order)
-  if (timed) { be_timer_stop(P.timers[3], s); be_timer_start(P.timers[6], s); P.bank_timer_closed = true; }
-  be_stage(6);
-  be_launch_bank_w64(R, n_items, (size_t)AW.lds_floats * 4, s);
-  be_stage(3);
-  if (timed) be_timer_stop(P.timers[6], s);
+  if (timed) be_timer_stop(P.timers[cur], s);
 }
 
 int build_hilbert(Plan& P) {
@@ -389,51 +355,68 @@ int bank_lds(NmxBankArgs& A, bool with_hilbert) {
   return 0;
 }
 
+// What the kinds of FIR stage decide differently (build_fir_stage)
+struct FirRules {
+  int reach;      // the "same" convolution of a window needs M >= W + reach
+  int w64_lo;     // the one-wave M = 2048 kernels for W + reach in (w64_lo, 2048]
+  bool w64x2;     // the M = 4096 one-wave kernel for W + reach in (2048, 4096] (device only)
+  bool hilbert;   // the LDS bank kernel also holds the Hilbert transform's buffers
+  int stage;      // timer / kernel-name stage of its launches
+};
+
+// The decisions every FIR stage makes: kernel family, convolution length M, tap spectra and the kernels' tables.  The
+// caller has filled S->a but for those (W, pad mode, epilogue; per filter all but H, f[i].half = half-length of the live
+// taps[i]).  Hhost: the filters' real spectra at M (none in partitioned mode).
+int build_fir_stage(Plan& P, const std::vector<const double*>& taps, const FirRules& r, FirStage* S,
+                    std::vector<std::vector<float>>* Hhost = nullptr) {
+  NmxBankArgs& A = S->a;
+  A.n_filters = (int)taps.size();
+  S->launches = {FirLaunch{(1u << A.n_filters) - 1u, nullptr, nullptr, 0, r.stage}};
+  const int need = A.W + r.reach;
+  const bool on = env_int("NMX_BANK_W64", 1) == 1;
+  const bool w64 = on && need > r.w64_lo && need <= 2048;
+  bool w64x2 = false;
+#ifndef NMX_HOST_EMU   // (device only: unpaired LDS reads and explicit operand modifiers)
+  w64x2 = r.w64x2 && on && env_int("NMX_BANK_W64X2", 1) == 1 && need > 2048 && need <= 4096;
+#endif
+  A.M = w64 ? 2048 : w64x2 ? 4096 : choose_M(need);
+  if (!w64 && !w64x2 && (!bank_fits_lds(A.M, A.W, r.hilbert) || env_int("NMX_BANK_PARTITIONED", 0) == 1))
+    return bank_partitioned_setup(P, A, taps);
+  std::vector<std::vector<float>> local;
+  std::vector<std::vector<float>>& H = Hhost ? *Hhost : local;
+  H.assign(taps.size(), {});
+  int rc;
+  if ((rc = build_fft(P, A.M / 2, &A.fft))) return rc;
+  for (size_t i = 0; i < taps.size(); ++i)
+    if ((rc = filter_spectrum(P, taps[i], 2 * A.f[i].half + 1, A.M, &A.f[i].H, &H[i]))) return rc;
+  if ((rc = bank_lds(A, r.hilbert))) return rc;
+  S->w64 = w64 || w64x2;
+  if (w64x2) return build_w64x2(P, A, H, &S->w);
+  return w64 ? build_w64(P, A, H, &S->w) : 0;
+}
+
 int build_bank(Plan& P) {
   const nmx_plan_desc& d = P.d;
   if (d.n_filters == 0) return 0;
   NMX_REQUIRE(d.n_filters <= NMX_MAX_FILTERS_DEV, "too many filters");
-  NmxBankArgs& A = P.bank;
+  FirStage& S = P.bank;
+  NmxBankArgs& A = S.a;
   A.n_outputs = d.n_outputs;
   A.n_channels = d.n_channels;
   A.W = d.window;
-  int maxhalf = 0;
-  for (int i = 0; i < d.n_filters; ++i) {
-    NMX_REQUIRE(d.filters[i].n_taps & 1, "FIR taps must have odd length");
-    maxhalf = std::max(maxhalf, (d.filters[i].n_taps - 1) / 2);
-  }
-  // only taps within W-1 of the centre can touch the window (SURVEY A.4)
-  maxhalf = std::min(maxhalf, d.window - 1);
-  A.M = choose_M(d.window + maxhalf);
-  const char* env_m = nullptr;   // (a forced convolution length was a round-1 knob)
-  // fast single-wave path: M = 2048 (n = 1024 = 64 lanes x 16 points)
-  const bool w64 = env_int("NMX_BANK_W64", 1) == 1 && !env_m && d.window + maxhalf <= 2048 &&
-                   d.window + maxhalf > 512;   // (513 .. 1024: the one-wave 1024-point path still beats the multi-wave LDS Stockham of half the length, measured on BASELINE config 5)
-  if (w64) A.M = 2048;
-  bool w64x2 = false;
-#ifndef NMX_HOST_EMU   // (device only: unpaired LDS reads and explicit operand modifiers)
-  w64x2 = env_int("NMX_BANK_W64X2", 1) == 1 && env_int("NMX_BANK_W64", 1) == 1 && !env_m && d.window + maxhalf > 2048 &&
-          d.window + maxhalf <= 4096 && (d.window & 3) == 0 && !(d.bp_features & 6u);
-  if (w64x2) A.M = 4096;
-#endif
   A.pad_mode = 0;
+  int reach = 0;
   bool hil = false;
-  for (int i = 0; i < d.n_filters; ++i) hil |= d.filters[i].burst_index >= 0;
-  const bool part = !w64 && !w64x2 && (!bank_fits_lds(A.M, d.window, hil) || env_int("NMX_BANK_PARTITIONED", 0) == 1);
-  int rc = 0;
-  if (!part && (rc = build_fft(P, A.M / 2, &A.fft))) return rc;
-  A.n_filters = d.n_filters;
-  std::vector<std::vector<float>> Hhost;
   std::vector<const double*> live;
   for (int i = 0; i < d.n_filters; ++i) {
     const nmx_filter_desc& f = d.filters[i];
+    NMX_REQUIRE(f.n_taps & 1, "FIR taps must have odd length");
+    // only taps within W-1 of the centre can touch the window (SURVEY A.4)
+    const int half = (f.n_taps - 1) / 2, uh = std::min(half, d.window - 1);
+    live.push_back(P.taps[i].data() + (half - uh));
+    reach = std::max(reach, uh);
+    hil |= f.burst_index >= 0;
     NmxFilterDev& F = A.f[i];
-    // truncate to the live centre part when the taps are longer than 2 W - 1
-    const int L = f.n_taps, half = (L - 1) / 2, uh = std::min(half, d.window - 1);
-    const double* h = P.taps[i].data() + (half - uh);
-    live.push_back(h);
-    Hhost.emplace_back();
-    if (!part && (rc = filter_spectrum(P, h, 2 * uh + 1, A.M, &F.H, &Hhost.back()))) return rc;
     F.half = uh;
     F.bp_seglen = f.bp_seglen;
     F.bp_band = f.bp_band_index;
@@ -443,7 +426,6 @@ int build_bank(Plan& P) {
     NMX_REQUIRE(f.bp_seglen >= 0 && f.bp_seglen <= d.window, "band-pass segment longer than the window");
     NMX_REQUIRE(f.bp_seglen == 0 || f.bp_seglen >= 3 || !(d.bp_features & 6u), "segment too short");
     NMX_REQUIRE(f.burst_index < d.n_burst_bands && f.sw_index < d.n_sw_filters, "filter index out of range");
-    if (f.burst_index >= 0) hil = true;
   }
   A.bp_features = d.bp_features;
   A.bp_log = d.bp_log_transform;
@@ -451,58 +433,52 @@ int build_bank(Plan& P) {
   A.bp_cols = cv(d.bp_cols);
   A.n_burst_bands = d.n_burst_bands;
   A.n_sw_filters = d.n_sw_filters;
-  if (part) {   // burst bands leave as series; the stand-alone Hilbert kernel follows (run_chunk)
-    if ((rc = bank_partitioned_setup(P, A, live))) return rc;
-    if (hil && (rc = build_hilbert(P))) return rc;
-    P.have_bank = true;
-    return 0;
-  }
-  if (hil) {
+  // one-wave M = 2048 from W + reach = 513 on (513 .. 1024: the one-wave 1024-point path still beats the multi-wave LDS
+  // Stockham of half the length, measured on BASELINE config 5)
+  const bool fits_x2 = (d.window & 3) == 0 && !(d.bp_features & 6u);
+  std::vector<std::vector<float>> H;
+  int rc = build_fir_stage(P, live, FirRules{reach, 512, fits_x2, hil, 3}, &S, &H);
+  if (rc) return rc;
+  if (hil && !A.partitioned) {
     A.hil_full = d.window & 1;
     if ((rc = build_fft(P, A.hil_full ? d.window : d.window / 2, &A.hil_r))) return rc;
     if ((rc = build_fft(P, d.window, &A.hil_c))) return rc;
   }
-  if ((rc = bank_lds(A, hil))) return rc;
-  if (w64) {
-    if ((rc = build_w64(P, A, Hhost, &P.bankw))) return rc;
-    if (hil && (rc = build_hilbert(P))) return rc;
-    P.bank_w64 = true;
+  // the one-wave and partitioned kernels leave burst bands as series: the stand-alone Hilbert kernel follows (run_chunk)
+  if (hil && (S.w64 || A.partitioned) && (rc = build_hilbert(P))) return rc;
 #ifndef NMX_HOST_EMU   // (device only, like the M = 4096 path)
-    // M = 1536, two channels per transform, for every filter with W + (L - 1) / 2 <= 1536 (the default band-pass
-    // taps: 999); longer ones (the default sharp-wave taps: 1651) stay on the M = 2048 kernel
-    if (env_int("NMX_BANK_W64C", 1) == 1 && d.window <= 1024 && !(d.bp_features & 6u)) {
-      unsigned mask = 0;
-      int n_sel = 0;
-      int need = 0;
-      for (int i = 0; i < d.n_filters && i < 32; ++i)
+  if (S.w64 && A.M == 2048 && d.window <= 1024 && !(d.bp_features & 6u)) {
+    // M = 1536, two channels per transform, for every filter with W + (L - 1) / 2 <= 1536 (the default band-pass taps:
+    // 999), M = 1024 when all of them fit it; longer ones (the default sharp-wave taps: 1651) go to a second launch: the
+    // M = 2048 channel-pair kernel (nmx_k_bank_w64e.h), or the one-channel M = 2048 kernels
+    const unsigned all = S.launches[0].mask;
+    S.launches.clear();
+    unsigned mask = 0;
+    if (env_int("NMX_BANK_W64C", 1) == 1) {
+      int n_sel = 0, need = 0;
+      for (int i = 0; i < d.n_filters; ++i)
         if (d.window + A.f[i].half <= 1536) { mask |= 1u << i; ++n_sel; need = std::max(need, d.window + A.f[i].half); }
       // (a second launch repeats the forward transform: not for one filter out of many)
       if ((n_sel >= 2 || n_sel == d.n_filters) && n_sel >= 1 && n_sel <= 11) {
         // short windows (the taps that touch them end at 2 W - 1): the 1024-point channel-pair kernel
         const int M = (need <= 1024 && (d.window & 1) == 0 && env_int("NMX_BANK_W64D", 1) == 1) ? 1024 : 1536;
-        if ((rc = build_w64c(P, A, mask, M))) return rc;
-        P.bank_w64c = true;
+        std::vector<std::vector<float>> HM(d.n_filters);
+        for (int i = 0; i < d.n_filters; ++i)
+          if (((mask >> i) & 1u) && (rc = host_spectrum(live[i], 2 * A.f[i].half + 1, M, &HM[i]))) return rc;
+        S.launches.emplace_back();
+        if ((rc = build_pair_tables(P, M, mask, HM, &S.launches.back()))) return rc;
+      } else {
+        mask = 0;
       }
     }
-    // M = 2048, two channels per transform (nmx_k_bank_w64e.h), for what the M = 1536 kernel left: with the default
-    // settings the two 1651-tap sharp-wave filters
-    if (env_int("NMX_BANK_W64E", 1) == 1 && d.window <= 1024 && !(d.bp_features & 6u) && d.n_filters <= 31) {
-      const unsigned all = (1u << d.n_filters) - 1u, rest = P.bank_w64c ? (all & ~P.w64c_mask) : all;
-      int n_rest = 0;
-      for (int i = 0; i < d.n_filters; ++i) n_rest += (rest >> i) & 1u;
-      if (n_rest >= 1 && n_rest <= 8) {
-        if ((rc = build_w64e(P, d.n_filters, rest, Hhost, &P.w64e_hc_bank))) return rc;
-        P.bank_w64e = true;
-      }
+    FirLaunch rest{all & ~mask, nullptr, nullptr, 0, mask ? 6 : 3};
+    if (rest.mask) {
+      if (env_int("NMX_BANK_W64E", 1) == 1 && __builtin_popcount(rest.mask) <= 8 &&
+          (rc = build_pair_tables(P, 2048, rest.mask, H, &rest))) return rc;
+      S.launches.push_back(rest);
     }
+  }
 #endif
-  }
-  if (w64x2) {
-    if ((rc = build_w64x2(P, A, Hhost, &P.bankw))) return rc;
-    if (hil && (rc = build_hilbert(P))) return rc;
-    P.bank_w64 = true;
-    P.bank_w64x2 = true;
-  }
   P.have_bank = true;
   return 0;
 }
@@ -510,7 +486,8 @@ int build_bank(Plan& P) {
 int build_notch(Plan& P) {
   const nmx_plan_desc& d = P.d;
   if (!d.notch_taps) return 0;
-  NmxBankArgs& A = P.notch;
+  FirStage& S = P.notch;
+  NmxBankArgs& A = S.a;
   A.n_outputs = d.n_outputs;
   A.n_channels = d.n_channels;
   A.W = P.w_in;
@@ -518,19 +495,9 @@ int build_notch(Plan& P) {
   NMX_REQUIRE(L & 1, "notch taps must have odd length");
   if (L == 1) return nmx_fail(NMX_E_INVALID, "single-tap notch is not supported");
   const int half = (L - 1) / 2;
-  A.pad_mode = 1;
+  A.pad_mode = 1;   // odd reflection: every tap reaches into the window
   A.n_edge = std::max(std::min(L, P.w_in) - 1, 0);
   A.pad_half = half;
-  A.M = choose_M(P.w_in + 2 * half);
-  const bool w64 = env_int("NMX_BANK_W64", 1) == 1 && P.w_in + 2 * half <= 2048 &&
-                   P.w_in + 2 * half > 1024;
-  if (w64) A.M = 2048;
-  const bool part = !w64 && (!bank_fits_lds(A.M, P.w_in, false) || env_int("NMX_BANK_PARTITIONED", 0) == 1);
-  int rc = 0;
-  if (!part && (rc = build_fft(P, A.M / 2, &A.fft))) return rc;
-  A.n_filters = 1;
-  NmxFilterDev& F = A.f[0];
-  std::vector<std::vector<float>> Hhost(1);
   // residual form (NmxBankArgs::residual): the kernels convolve with g = delta - h and store x - g * x_ext
   A.residual = env_int("NMX_NOTCH_RESIDUAL", 1) != 0;
   P.notch_taps_used = P.notch_taps;   // (P.notch_taps stays h: the offset split reads its DC gain, nmx_engine_dc.inc)
@@ -538,33 +505,20 @@ int build_notch(Plan& P) {
     for (double& t : P.notch_taps_used) t = -t;
     P.notch_taps_used[(size_t)half] += 1.0;
   }
-  if (!part && (rc = filter_spectrum(P, P.notch_taps_used.data(), L, A.M, &F.H, &Hhost[0]))) return rc;
+  NmxFilterDev& F = A.f[0];
   F.half = half;
   F.bp_seglen = 0;
   F.burst_index = -1;
   F.sw_index = -1;
   F.store_raw = 1;
-  if (part) {
-    if ((rc = bank_partitioned_setup(P, A, {P.notch_taps_used.data()}))) return rc;
-    P.have_notch = true;
-    return 0;
-  }
-  if ((rc = bank_lds(A, false))) return rc;
-  if (w64) {
-    if ((rc = build_w64(P, A, Hhost, &P.notchw))) return rc;
-    P.notch_w64 = true;
+  std::vector<std::vector<float>> H;
+  int rc = build_fir_stage(P, {P.notch_taps_used.data()}, FirRules{2 * half, 1024, false, false, 1}, &S, &H);
+  if (rc) return rc;
 #ifndef NMX_HOST_EMU
-    // two channels per 2048-point complex transform (nmx_k_bank_w64e.h, PAD = 1)
-    if (env_int("NMX_BANK_W64E", 1) == 1 && P.w_in <= 1024) {
-      const float* hc = nullptr;
-      if ((rc = build_w64e(P, 1, 1u, Hhost, &hc))) return rc;
-      P.notchw.hc = hc;
-      P.notchw.twc = P.w64e_tw;
-      P.notchw.pair_m = 2048;
-    }
+  // two channels per 2048-point complex transform (nmx_k_bank_w64e.h, PAD = 1)
+  if (S.w64 && env_int("NMX_BANK_W64E", 1) == 1 && P.w_in <= 1024 &&
+      (rc = build_pair_tables(P, 2048, 1u, H, &S.launches[0]))) return rc;
 #endif
-  }
   P.have_notch = true;
   return 0;
 }
-

@@ -89,46 +89,25 @@ static int run_rawnorm(Plan& P, const float*& src, long long& ch_stride, long lo
 // preprocessing_filter stages: zero-padded "same" FIR on the incoming window, series out
 int build_prefilters(Plan& P) {
   const nmx_plan_desc& d = P.d;
-  const int W = P.w_in;
-  P.pf.resize(d.n_pre_filters);
-  P.pfw.resize(d.n_pre_filters);
-  P.pf_w64.assign(d.n_pre_filters, 0);
+  P.pre.assign(d.n_pre_filters, FirStage{});
   for (int i = 0; i < d.n_pre_filters; ++i) {
-    NmxBankArgs A{};
+    NmxBankArgs& A = P.pre[i].a;
     A.n_outputs = d.n_outputs;
     A.n_channels = d.n_channels;
-    A.W = W;
+    A.W = P.w_in;
+    A.pad_mode = 0;
+    A.n_sw_filters = 1;
     const int L = d.n_pre_taps[i];
     NMX_REQUIRE(L & 1, "pre-filter taps must have odd length");
-    const int half = (L - 1) / 2, uh = std::min(half, W - 1);
-    A.M = choose_M(W + uh);
-    const bool w64 = env_int("NMX_BANK_W64", 1) == 1 && W + uh <= 2048 && W + uh > 1024;
-    if (w64) A.M = 2048;
-    A.pad_mode = 0;
-    const bool part = !w64 && (!bank_fits_lds(A.M, W, false) || env_int("NMX_BANK_PARTITIONED", 0) == 1);
-    int rc = 0;
-    if (!part && (rc = build_fft(P, A.M / 2, &A.fft))) return rc;
-    A.n_filters = 1;
-    A.n_sw_filters = 1;
+    const int half = (L - 1) / 2, uh = std::min(half, A.W - 1);
     NmxFilterDev& F = A.f[0];
-    std::vector<std::vector<float>> Hhost(1);
-    if (!part && (rc = filter_spectrum(P, P.pre_taps[i].data() + (half - uh), 2 * uh + 1, A.M, &F.H, &Hhost[0]))) return rc;
     F.half = uh;
     F.bp_seglen = 0;
     F.burst_index = -1;
     F.sw_index = 0;
     F.store_raw = 0;
-    if (part) {
-      if ((rc = bank_partitioned_setup(P, A, {P.pre_taps[i].data() + (half - uh)}))) return rc;
-      P.pf[i] = A;
-      continue;
-    }
-    if ((rc = bank_lds(A, false))) return rc;
-    if (w64) {
-      if ((rc = build_w64(P, A, Hhost, &P.pfw[i]))) return rc;
-      P.pf_w64[i] = 1;
-    }
-    P.pf[i] = A;
+    int rc = build_fir_stage(P, {P.pre_taps[i].data() + (half - uh)}, FirRules{uh, 1024, false, false, 1}, &P.pre[i]);
+    if (rc) return rc;
   }
   return 0;
 }

@@ -1,6 +1,50 @@
 // nmx_engine_run.inc -- C ABI, part 2: the launch sequence of one chunk (run_chunk), nmx_process_batch / _window,
 // nmx_preprocess_window, nmx_filter_window, timers and kernel names.  Included by nmx_engine.inc.
 // -----------------------------------------------------------------------------------------
+// The pre-processing behind a re-reference / offset shift, of a chunk (nw hops) or of one window (nw = 1, win_stride = 0):
+// preprocessing_filter stages -> notch -> resampler (after the notch like the reference, data_preprocessor.py:9-15,68-71)
+// -> raw normaliser (the last pre-processor; its input already nan_to_num'ed).  src / strides / starts / clean follow the
+// output of each stage that runs.
+static int run_prep_stages(Plan& P, const float*& src, long long& ch_stride, long long& win_stride,
+                           const long long*& starts, int nw, int& clean, be_stream_t s) {
+  const int C = P.d.n_channels, W = P.d.window, Wi = P.w_in;
+  int rc;
+  auto take = [&](const void* y, int w) {   // the next stage reads y, [nw][C][w]
+    src = (const float*)y;
+    ch_stride = w; win_stride = (long long)C * w; starts = nullptr; clean = 0;
+  };
+  for (size_t i = 0; i < P.pre.size(); ++i) {   // preprocessing_filter: FIR stages one after the other
+    Buf& dst = P.x_pf[i & 1];
+    if ((rc = ensure(dst, (size_t)nw * C * Wi * sizeof(float)))) return rc;
+    NmxBankArgs A = P.pre[i].a;
+    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
+    A.out = nullptr; A.sw_out = (float*)dst.p;
+    launch_fir_stage(P, P.pre[i], A, nw * C, s);
+    take(dst.p, Wi);
+  }
+  if (P.have_notch) {
+    if ((rc = ensure(P.y_notch, (size_t)nw * C * Wi * sizeof(float)))) return rc;
+    NmxBankArgs A = P.notch.a;
+    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
+    A.out = nullptr; A.y_out = (float*)P.y_notch.p;
+    launch_fir_stage(P, P.notch, A, nw * C, s);
+    take(P.y_notch.p, Wi);
+  }
+  if (P.have_resample) {
+    if ((rc = ensure(P.x_rs, (size_t)nw * C * W * sizeof(float)))) return rc;
+    NmxResampleArgs A = P.rs;
+    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
+    A.y = (float*)P.x_rs.p;
+    be_launch_resample(A, nw * C, P.nt_resample, (size_t)A.lds_floats * 4, s);
+    take(P.x_rs.p, W);
+  }
+  if (P.have_rawnorm) {
+    if ((rc = run_rawnorm(P, src, ch_stride, win_stride, starts, nw, clean, s))) return rc;
+    clean = 0;
+  }
+  return 0;
+}
+
 // d_x / ldx address the recording with ABSOLUTE sample indices (the windows' starts); only the samples
 // [lo, hi) that the windows of this chunk touch are read (d_x may point lo samples before a buffer that
 // holds just that range).
@@ -10,7 +54,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
                      float* d_pre = nullptr, const int64_t* h_starts = nullptr) {
   const long long n_range = hi - lo;
   const nmx_plan_desc& d = P.d;
-  const int C = d.n_channels, W = d.window, Wi = P.w_in;
+  const int C = d.n_channels, W = d.window;
   int rc;
   // The tensors the SIDE streams read (envelopes, thresholds, sharp-wave series and flags) exist twice: this chunk's main
   // stream does not wait for the previous chunk's threshold walk / run statistics / sharp waves -- its re-reference,
@@ -70,55 +114,8 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       if ((long long)(h_starts[i] - h_starts[i - 1]) != hop) hop = -1;
     if (hop >= 0) { src += h_starts[0]; win_stride = hop; starts = nullptr; }
   }
-  for (size_t i = 0; i < P.pf.size(); ++i) {   // preprocessing_filter: FIR stages one after the other
-    Buf& dst = P.x_pf[i & 1];
-    if ((rc = ensure(dst, (size_t)nw * C * Wi * sizeof(float)))) return rc;
-    NmxBankArgs A = P.pf[i];
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
-    A.out = nullptr; A.sw_out = (float*)dst.p;
-    if (P.pf_w64[i]) {
-      NmxBankW64Args AW = P.pfw[i];
-      AW.b = A;
-      AW.yb_out = nullptr;
-      be_launch_bank_w64(AW, nw * C, (size_t)AW.lds_floats * 4, s);
-    } else {
-      be_launch_bank(A, nw * C, P.nt_bank, (size_t)A.lds_floats * 4, s);
-    }
-    src = (const float*)dst.p;
-    ch_stride = Wi; win_stride = (long long)C * Wi; starts = nullptr; clean = 0;
-    raw_live = false;
-  }
-  if (P.have_notch) {
-    if ((rc = ensure(P.y_notch, (size_t)nw * C * Wi * sizeof(float)))) return rc;
-    NmxBankArgs A = P.notch;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
-    A.out = nullptr; A.y_out = (float*)P.y_notch.p;
-    if (P.notch_w64) {
-      NmxBankW64Args AW = P.notchw;
-      AW.b = A;
-      be_launch_bank_w64(AW, nw * C, (size_t)AW.lds_floats * 4, s);
-    } else {
-      be_launch_bank(A, nw * C, P.nt_bank, (size_t)A.lds_floats * 4, s);
-    }
-    src = (const float*)P.y_notch.p;
-    ch_stride = Wi; win_stride = (long long)C * Wi; starts = nullptr; clean = 0;
-    raw_live = false;
-  }
-  if (P.have_resample) {   // after the notch like the reference (data_preprocessor.py:9-15,68-71)
-    if ((rc = ensure(P.x_rs, (size_t)nw * C * W * sizeof(float)))) return rc;
-    NmxResampleArgs A = P.rs;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
-    A.y = (float*)P.x_rs.p;
-    be_launch_resample(A, nw * C, P.nt_resample, (size_t)A.lds_floats * 4, s);
-    src = (const float*)P.x_rs.p;
-    ch_stride = W; win_stride = (long long)C * W; starts = nullptr; clean = 0;
-    raw_live = false;
-  }
-  if (P.have_rawnorm) {   // last pre-processor (data_preprocessor.py:9-15); input already nan_to_num'ed
-    if ((rc = run_rawnorm(P, src, ch_stride, win_stride, starts, nw, clean, s))) return rc;
-    clean = 0;
-    raw_live = false;
-  }
+  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, nw, clean, s))) return rc;
+  if (!P.pre.empty() || P.have_notch || P.have_resample || P.have_rawnorm) raw_live = false;
   if (d_pre) {   // user-registered host features read what the device features read
     NmxTapArgs T{};
     T.x = src; T.ch_stride = ch_stride; T.win_stride = win_stride; T.starts = starts;
@@ -152,11 +149,11 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   // code -- to a second side stream, next to Hilbert and the time / oscillatory kernel (VALU bound).
   be_stage(3);
   if (P.have_bank) {
-    NmxBankArgs A = P.bank;
+    NmxBankArgs A = P.bank.a;
     A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
     A.out = d_out; A.clean_on_load = clean;
     A.dcf = dcf;
-    if (dcf && P.bank_w64 && !bank_w64_takes_dc(P, P.bankw, nw * C)) {
+    if (dcf && !fir_stage_takes_dc(P.bank, nw * C)) {
       if ((rc = with_dc())) return rc;
       A.x = src_dc; A.ch_stride = W; A.win_stride = (long long)C * W; A.starts = nullptr; A.clean_on_load = 0; A.dcf = nullptr;
     }
@@ -168,24 +165,11 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       if ((rc = ensure(B_swy, (size_t)nw * C * d.n_sw_filters * W * sizeof(float)))) return rc;
       A.sw_out = (float*)B_swy.p;
     }
-    if (tev) be_timer_start(P.timers[3], s);
-    if (P.bank_w64) {
-      NmxBankW64Args AW = P.bankw;
-      AW.b = A;
-      if (P.have_bursts) {
-        if ((rc = ensure(P.yb, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
-        AW.yb_out = (float*)P.yb.p;
-      }
-      bank_launch_all(P, AW, nw * C, s, tev);
-    } else {
-      if (A.partitioned && P.have_bursts) {
-        if ((rc = ensure(P.yb, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
-        A.yb_out = (float*)P.yb.p;
-      }
-      be_launch_bank(A, nw * C, P.nt_bank, (size_t)A.lds_floats * 4, s);
+    if (P.have_bursts && (P.bank.w64 || A.partitioned)) {   // band series for the stand-alone Hilbert kernel
+      if ((rc = ensure(P.yb, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
+      A.yb_out = (float*)P.yb.p;
     }
-    if (tev && !P.bank_timer_closed) be_timer_stop(P.timers[3], s);
-    P.bank_timer_closed = false;
+    launch_fir_stage(P, P.bank, A, nw * C, s, tev);
     if (P.have_kalman) {   // sequential over the hops of the chunk; chunks run in order on `s`
       NmxKalmanArgs K = P.kal;
       K.out = d_out; K.n_windows = nw;
@@ -226,7 +210,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       be_stream_wait(sb, P.ev_fork);
     }
     if (tev) be_timer_start(P.timers[4], sb);
-    if (P.bank_w64 || P.bank.partitioned) {
+    if (P.bank.w64 || P.bank.a.partitioned) {
       NmxHilbertArgs H = P.hil;
       H.y = (const float*)P.yb.p; H.env = (float*)B_env.p;
       be_launch_hilbert(H, (long long)nw * C * d.n_burst_bands, P.nt_hilbert, (size_t)H.lds_floats * 4, sb);
@@ -412,7 +396,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   // features of chunk k - 1 travel back.  Device buffers: one chunk = NMX_CHUNK_WINDOWS hops.
   // (a plan without a hand-off tensor -- time / oscillatory features straight from the recording -- has nothing a chunk
   // would bound: device-resident batches go out as ONE launch of up to 16 chunks' worth of hops)
-  const bool no_handoff = !P.have_bank && !P.have_notch && !P.d_R && !P.have_resample && !P.have_rawnorm && P.pf.empty();
+  const bool no_handoff = !P.have_bank && !P.have_notch && !P.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
   // (an attached normaliser needs a chunk's rows complete, and hop order: it runs on the finalize stream under the NEXT
   // chunk's kernels, so only the last chunk's pass is exposed -- against that, shorter chunks cost the main kernels 0.16 ms
   // per 1024 hops at 256.  Round 6, scans + cells at ~75 us per pass, headline step with / without the z-score:
@@ -605,7 +589,7 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   Plan& P = *Pp;
   const nmx_plan_desc& d = P.d;
   const int Cin = d.n_channels_in, C = d.n_channels, Wo = d.window;
-  int W = P.w_in;   // incoming samples per window; becomes Wo after the resampler
+  const int W = P.w_in;   // incoming samples per window
   int rc = be_set_device(P.device);
   if (rc) return rc;
   be_stream_t s = P.stream;
@@ -621,6 +605,8 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   if ((rc = ensure(P.x_in, xf.size() * sizeof(float)))) return rc;
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
   const float* src = (const float*)P.x_in.p;
+  long long ch_stride = W, win_stride = 0;
+  const long long* starts = nullptr;
   int clean = 1;
   if (P.d_R) {
     if ((rc = ensure(P.x_ref, (size_t)C * W * sizeof(float)))) return rc;
@@ -638,59 +624,12 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
       clean = 0;
     }
   }
-  for (size_t i = 0; i < P.pf.size(); ++i) {
-    Buf& dst = P.x_pf[i & 1];
-    if ((rc = ensure(dst, (size_t)C * W * sizeof(float)))) return rc;
-    NmxBankArgs A = P.pf[i];
-    A.x = src; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr; A.clean_on_load = clean;
-    A.out = nullptr; A.sw_out = (float*)dst.p;
-    if (P.pf_w64[i]) {
-      NmxBankW64Args AW = P.pfw[i];
-      AW.b = A;
-      AW.yb_out = nullptr;
-      be_launch_bank_w64(AW, C, (size_t)AW.lds_floats * 4, s);
-    } else {
-      be_launch_bank(A, C, P.nt_bank, (size_t)A.lds_floats * 4, s);
-    }
-    src = (const float*)dst.p;
-    clean = 0;
-  }
-  if (P.have_notch) {
-    if ((rc = ensure(P.y_notch, (size_t)C * W * sizeof(float)))) return rc;
-    NmxBankArgs A = P.notch;
-    A.x = src; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr; A.clean_on_load = clean;
-    A.out = nullptr; A.y_out = (float*)P.y_notch.p;
-    if (P.notch_w64) {
-      NmxBankW64Args AW = P.notchw;
-      AW.b = A;
-      be_launch_bank_w64(AW, C, (size_t)AW.lds_floats * 4, s);
-    } else {
-      be_launch_bank(A, C, P.nt_bank, (size_t)A.lds_floats * 4, s);
-    }
-    src = (const float*)P.y_notch.p;
-    clean = 0;
-  }
-  if (P.have_resample) {
-    if ((rc = ensure(P.x_rs, (size_t)C * Wo * sizeof(float)))) return rc;
-    NmxResampleArgs A = P.rs;
-    A.x = src; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr; A.clean_on_load = clean;
-    A.y = (float*)P.x_rs.p;
-    be_launch_resample(A, C, P.nt_resample, (size_t)A.lds_floats * 4, s);
-    src = (const float*)P.x_rs.p;
-    clean = 0;
-  }
-  W = Wo;
-  if (P.have_rawnorm) {
-    long long cs = W, ws = 0;
-    const long long* st0 = nullptr;
-    if ((rc = run_rawnorm(P, src, cs, ws, st0, 1, clean, s))) return rc;
-    clean = 0;
-  }
+  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, 1, clean, s))) return rc;
   be_d2h_async(yf.data(), src, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
-    for (int i = 0; i < W; ++i) {
-      float v = yf[(size_t)c * W + i];
+    for (int i = 0; i < Wo; ++i) {
+      float v = yf[(size_t)c * Wo + i];
       if (clean) v = (v != v) ? 0.f : v;
       y[(size_t)c * ldy + i] = (double)v + (P.dc_active ? P.dc_pre_h[c] : 0.0);
     }
@@ -713,21 +652,14 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   if ((rc = ensure(P.x_in, xf.size() * sizeof(float)))) return rc;
   if ((rc = ensure(P.swy[0], yf.size() * sizeof(float)))) return rc;
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
-  NmxBankArgs A = P.bank;
+  NmxBankArgs A = P.bank.a;
   A.x = (const float*)P.x_in.p; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr;
   A.clean_on_load = 0; A.out = nullptr;
   A.n_sw_filters = NF; A.sw_out = (float*)P.swy[0].p;
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
   }
-  if (P.bank_w64) {
-    NmxBankW64Args AW = P.bankw;
-    AW.b = A;
-    AW.yb_out = nullptr;
-    bank_launch_all(P, AW, C, s);
-  } else {
-    be_launch_bank(A, C, P.nt_bank, (size_t)A.lds_floats * 4, s);
-  }
+  launch_fir_stage(P, P.bank, A, C, s);
   be_d2h_async(yf.data(), P.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];
