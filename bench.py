@@ -10,7 +10,9 @@ One step = one batch of --windows hops over synthetic data that is already resid
 channels shard across GPUs with no collective on the data path (weak scaling: 256 ch / GPU,
 each GPU = one independently referenced electrode array).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line (rank 0) with the
+contract fields.  With --full it also takes the context measurements and checks below, each outside the timed steps:
+  kernel_ms_per_step  per-stage HIP-event times of a few extra steps; `kernels` names what each stage launched
   roofline     dominant kernel (FIR bank; its NAME comes from the plan = the variant that actually ran):
                algorithmic bytes / HIP-event kernel time vs the 8 TB/s HBM roof, the same kernel against the
                157.3 TFLOP/s FP32 vector roof (`roofline.fp32`, SURVEY 8(d): the FIR bank is FP32 / LDS
@@ -20,6 +22,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   cpu_baseline_allcores  the same port with the channels split over worker processes (context row)
   cold_start_ms  the first 1024-hop step of a FRESH plan (the burst history fills during its first 291 hops:
                the fill-regime threshold walk costs more than a whole steady-state step)
+  max_rel_err_vs_cpu  the CPU oracle's hops through a fresh engine, with a gate on its ceilings (exit code 3)
+  nan_outputs  NaN entries of the last stage-timer step
+--config c4 | c5 and --scaling strong: --full adds the stage times, the kernel names, nan_outputs and the exchange step
+timed alone.
 """
 
 from __future__ import annotations
@@ -385,12 +391,13 @@ def run_config(args, torch, dist, world, rank, dev, dev_index) -> None:
     if args.dump_outputs:   # (the stage-timer steps below overwrite `out`)
         dump_outputs(args.dump_outputs, "features" if world == 1 else f"features_rank{rank}", out.cpu().numpy(),
                      DUMP_LIMIT_BYTES // world)
-    kt = {k: 0.0 for k in names_t}   # per-stage HIP-event times from a few more steps outside the timed region
-    n_kt = min(10, args.steps)
-    for _ in range(n_kt):
-        step()
-        for name, idx in (("batch", 0), ("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("bursts", 4), ("sharp", 5)):
-            kt[name] += eng.timing_ms(idx)
+    if args.full:   # per-stage HIP-event times from a few more steps outside the timed region
+        kt = {k: 0.0 for k in names_t}
+        n_kt = min(10, args.steps)
+        for _ in range(n_kt):
+            step()
+            for name, idx in (("batch", 0), ("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("bursts", 4), ("sharp", 5)):
+                kt[name] += eng.timing_ms(idx)
     if world > 1:
         tdt = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tdt, op=dist.ReduceOp.MAX)
@@ -400,21 +407,18 @@ def run_config(args, torch, dist, world, rank, dev, dev_index) -> None:
         rank_ms = [float(t.item()) for t in every]
     else:
         rank_ms = None
-    bad = int(torch.isnan(out).sum().item())
-    exchange_ms = None
-    if car:   # the exchange step alone (outside the timed region): partial sums + all-reduce + hi / lo rows, per step
-        torch.cuda.synchronize(dev)
-        te = time.perf_counter()
-        for _ in range(args.steps):
-            exchange()
-        torch.cuda.synchronize(dev)
-        exchange_ms = (time.perf_counter() - te) / args.steps * 1e3
+    if args.full:
+        bad = int(torch.isnan(out).sum().item())
+        exchange_ms = None
+        if car:   # the exchange step alone (outside the timed region): partial sums + all-reduce + hi / lo rows, per step
+            torch.cuda.synchronize(dev)
+            te = time.perf_counter()
+            for _ in range(args.steps):
+                exchange()
+            torch.cuda.synchronize(dev)
+            exchange_ms = (time.perf_counter() - te) / args.steps * 1e3
     if rank == 0:
         value = args.steps * n_win / dt               # windows of the WHOLE array (all ranks work on the same windows)
-        stage = max(("timeosc", "bank", "sharp", "prep"), key=lambda k: kt[k])
-        idx = {"prep": 1, "timeosc": 2, "bank": 3, "sharp": 5}[stage]
-        ms = kt[stage] / n_kt
-        algo = n_win * C * (4 * W + 4 * F / C)        # window in + features out, this rank's channels
         res = {
             "metric": ("windows/sec (all features), 256 ch @ 1 kHz" if args.config == "headline"
                        else f"windows/sec, BASELINE config {args.config}"), "value": value, "unit": "windows/s",
@@ -426,17 +430,25 @@ def run_config(args, torch, dist, world, rank, dev, dev_index) -> None:
                        "features_per_window_per_gpu": F,
                        "parallelism": f"channel-shard x{world}" + (", group sum all-reduced per step" if car else ", no collective")},
             "features_per_sec": value * F * world,
-            "kernel_ms_per_step": {k: v / n_kt for k, v in kt.items()},
             "ms_per_step_by_rank": rank_ms,   # (N > 1: every rank's own wall time per step; `value` uses the slowest)
-            "exchange_ms_per_step": exchange_ms,   # c4: column sums + all-reduce + hi / lo rows (inside the timed step; timed alone here)
-            "kernels": {name: eng.kernels(i) for name, i in (("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("sharp", 5))},
-            "nan_outputs": bad,
-            "roofline": {"bound": "hbm", "kernel": eng.kernels(idx), "stage": stage,
-                         "achieved": algo / (ms * 1e-3) / 1e9 if ms > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (algo / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if ms > 0 else 0.0, "traffic": None,
-                         "note": "stage with the largest HIP-event time on rank 0; algorithmic bytes = the step's "
-                                 "window-in + features-out bytes of this rank's channels"},
+            "full": args.full,
         }
+        if args.full:
+            stage = max(("timeosc", "bank", "sharp", "prep"), key=lambda k: kt[k])
+            idx = {"prep": 1, "timeosc": 2, "bank": 3, "sharp": 5}[stage]
+            ms = kt[stage] / n_kt
+            algo = n_win * C * (4 * W + 4 * F / C)        # window in + features out, this rank's channels
+            res.update({
+                "kernel_ms_per_step": {k: v / n_kt for k, v in kt.items()},
+                "exchange_ms_per_step": exchange_ms,   # c4: column sums + all-reduce + hi / lo rows (inside the timed step; timed alone here)
+                "kernels": {name: eng.kernels(i) for name, i in (("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("sharp", 5))},
+                "nan_outputs": bad,
+                "roofline": {"bound": "hbm", "kernel": eng.kernels(idx), "stage": stage,
+                             "achieved": algo / (ms * 1e-3) / 1e9 if ms > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": (algo / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if ms > 0 else 0.0, "traffic": None,
+                             "note": "stage with the largest HIP-event time on rank 0; algorithmic bytes = the step's "
+                                     "window-in + features-out bytes of this rank's channels"},
+            })
         print(json.dumps(res))
     dp.engine.close()
 
@@ -451,6 +463,10 @@ def main() -> None:
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="N > 1 on the headline workload: weak = --channels per GPU (no collective), strong = --channels in "
                          "TOTAL split over the ranks, jointly re-referenced (one all-reduce of the column sums per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the context measurements and checks (stage times, kernel names, rooflines, cold start, "
+                         "CPU baselines, max_rel_err_vs_cpu and its gate, nan_outputs, the exchange step alone) outside "
+                         "the timed steps; without it a run prints the headline figure only")
     ap.add_argument("--no-gate", action="store_true", help="report max_rel_err_vs_cpu without failing on its ceilings")
     ap.add_argument("--channels", type=int, default=256, help="channels per GPU")
     ap.add_argument("--windows", type=int, default=1024, help="hops per step (batch)")
@@ -541,7 +557,7 @@ def main() -> None:
             dist.barrier()
 
     cold_ms = None
-    if not args.no_cold_start and rank == 0:   # first step of a fresh plan (outside the timed region)
+    if args.full and not args.no_cold_start and rank == 0:   # first step of a fresh plan (outside the timed region)
         # ... on a process that has launched a kernel before (code object uploaded, device awake).  What stays in the number:
         # the plan's ~3 GB of hand-off buffers allocated for the first time -- 20 ms on a device this process family has used
         # before, up to 260 ms on the first process after other tenants released the memory (driver side, measured both)
@@ -591,18 +607,19 @@ def main() -> None:
     if args.dump_outputs:   # the headline leg's last step (the stage-timer steps below overwrite `out`)
         dump_outputs(args.dump_outputs, "features" if world == 1 else f"features_rank{rank}", out.cpu().numpy(),
                      DUMP_LIMIT_BYTES // world)
-    if with_norm:
-        eng.attach_normalizer(None)
-    # per-stage HIP-event times (recorded on the launch stream inside libnmx): a few more steps OUTSIDE the timed region --
-    # reading an event waits for it, which would serialise the host against every step above.  Normaliser detached: a
-    # step is then ONE launch sequence of 1024 hops and a stage's timer brackets the kernel(s) of the whole step (with it
-    # the plan works in chunks of 384 hops and the timers hold the last chunk's)
-    kt = {k: 0.0 for k in ("prep", "timeosc", "bank", "bank_sw", "bursts", "sharp", "batch")}
-    n_kt = min(10, args.steps)
-    for _ in range(n_kt):
-        step()
-        for name, idx in (("batch", 0), ("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("bursts", 4), ("sharp", 5)):
-            kt[name] += eng.timing_ms(idx)
+    if args.full:
+        if with_norm:
+            eng.attach_normalizer(None)
+        # per-stage HIP-event times (recorded on the launch stream inside libnmx): a few more steps OUTSIDE the timed region --
+        # reading an event waits for it, which would serialise the host against every step above.  Normaliser detached: a
+        # step is then ONE launch sequence of 1024 hops and a stage's timer brackets the kernel(s) of the whole step (with it
+        # the plan works in chunks of 384 hops and the timers hold the last chunk's)
+        kt = {k: 0.0 for k in ("prep", "timeosc", "bank", "bank_sw", "bursts", "sharp", "batch")}
+        n_kt = min(10, args.steps)
+        for _ in range(n_kt):
+            step()
+            for name, idx in (("batch", 0), ("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("bursts", 4), ("sharp", 5)):
+                kt[name] += eng.timing_ms(idx)
     dt_own = dt
     rank_ms = None
     if world > 1:
@@ -614,30 +631,12 @@ def main() -> None:
         every = [torch.zeros(1, dtype=torch.float64, device=cdev) for _ in range(world)]
         dist.all_gather(every, torch.tensor([dt_own / args.steps * 1e3], dtype=torch.float64, device=cdev))
         rank_ms = [float(t.item()) for t in every]
-    bad = int(torch.isnan(out).sum().item())
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = args.steps * n_win * world / dt
         F_c = F / C
         bytes_cw = 4 * W + 4 * F_c                      # fp32 window in + features out
-        bank_ms = kt["bank"] / n_kt
-        # dominant kernel = FIR bank (nmx_kern_bank_w64_*): reads each (channel, window) once, writes
-        # its 4 band-pass features; the filtered-series hand-off to the Hilbert / sharp-wave kernels
-        # is NOT algorithmic traffic (it shows up in `traffic`)
-        n_bp = sum(1 for i in range(int(eng.desc.n_filters)) if eng.desc.filters[i].bp_seglen > 0)
-        bank_bytes = n_win * C * (4 * W + 4 * n_bp)
-        achieved = bank_bytes / (bank_ms * 1e-3) / 1e9 if bank_ms > 0 else 0.0
-        kernel = eng.kernels(3)   # what the plan launched in the FIR-bank stage of the last step
-        traffic, traffic_at = measured_traffic(kernel)
-        nf = int(eng.desc.n_filters)
-        if "w64c" in kernel:   # the M = 1536 channel-pair kernel took the filters with W + (L - 1) / 2 <= 1536
-            sel = [i for i in range(nf) if W + (int(eng.desc.filters[i].n_taps) - 1) // 2 <= 1536]
-            nf = len(sel)
-            flops_item = bank_flops_per_item_pair(1536, nf, [eng.desc.filters[i].bp_seglen for i in sel])
-        else:
-            flops_item = bank_flops_per_item(2048, nf, [eng.desc.filters[i].bp_seglen for i in range(nf)])
-        tflops = n_win * C * flops_item / (bank_ms * 1e-3) / 1e12 if bank_ms > 0 else 0.0
         res = {
             "metric": "windows/sec (all features), 256 ch @ 1 kHz", "value": value, "unit": "windows/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -655,9 +654,30 @@ def main() -> None:
             "ms_per_step_without_normalisation": plain_dt / args.steps * 1e3,
             "normalisation": ("zscore over 30 s of feature rows inside the plan (default_settings.yaml:69-78)"
                               if with_norm else "none (--no-normalisation)"),
-            "kernel_ms_per_step": {k: v / n_kt for k, v in kt.items()},
             "ms_per_step_by_rank": rank_ms,   # (N > 1: every rank's own wall time per step; `value` uses the slowest)
-            "nan_outputs": bad,
+            "full": args.full,
+        }
+    if args.full and rank == 0:
+        bank_ms = kt["bank"] / n_kt
+        # dominant kernel = FIR bank (nmx_kern_bank_w64_*): reads each (channel, window) once, writes
+        # its 4 band-pass features; the filtered-series hand-off to the Hilbert / sharp-wave kernels
+        # is NOT algorithmic traffic (it shows up in `traffic`)
+        n_bp = sum(1 for i in range(int(eng.desc.n_filters)) if eng.desc.filters[i].bp_seglen > 0)
+        bank_bytes = n_win * C * (4 * W + 4 * n_bp)
+        achieved = bank_bytes / (bank_ms * 1e-3) / 1e9 if bank_ms > 0 else 0.0
+        kernel = eng.kernels(3)   # what the plan launched in the FIR-bank stage of the last step
+        traffic, traffic_at = measured_traffic(kernel)
+        nf = int(eng.desc.n_filters)
+        if "w64c" in kernel:   # the M = 1536 channel-pair kernel took the filters with W + (L - 1) / 2 <= 1536
+            sel = [i for i in range(nf) if W + (int(eng.desc.filters[i].n_taps) - 1) // 2 <= 1536]
+            nf = len(sel)
+            flops_item = bank_flops_per_item_pair(1536, nf, [eng.desc.filters[i].bp_seglen for i in sel])
+        else:
+            flops_item = bank_flops_per_item(2048, nf, [eng.desc.filters[i].bp_seglen for i in range(nf)])
+        tflops = n_win * C * flops_item / (bank_ms * 1e-3) / 1e12 if bank_ms > 0 else 0.0
+        res.update({
+            "kernel_ms_per_step": {k: v / n_kt for k, v in kt.items()},
+            "nan_outputs": int(torch.isnan(out).sum().item()),
             "kernels": {name: eng.kernels(idx) for name, idx in
                         (("prep", 1), ("timeosc", 2), ("bank", 3), ("bank_sw", 6), ("bursts", 4), ("sharp", 5))},
             "roofline": {"bound": "hbm", "kernel": kernel, "achieved": achieved,
@@ -673,7 +693,7 @@ def main() -> None:
                                  "kernels.bank_sw / kernel_ms_per_step.bank_sw"},
             "cold_start_ms": cold_ms,
             "regime": "steady state: warm-up steps fill the 30 s burst history; cold_start_ms = first step of a fresh plan on a process that has launched a kernel before",
-        }
+        })
         if world == 1 and not args.no_mode_a:
             try:
                 eng.close()
@@ -705,6 +725,7 @@ def main() -> None:
                                   f"reference applied once by the parent; hops / slowest worker ({slow:.1f} s)"}
                 except Exception as e:   # never let the context row break the bench line
                     res["cpu_baseline_allcores"] = {"error": repr(e)}
+    if rank == 0:
         print(json.dumps(res))
         if not args.no_gate and not res.get("parity_gate", {"ok": True})["ok"]:
             print("bench.py: max_rel_err_vs_cpu above its ceilings: " + json.dumps(res["parity_gate"]["violations"]), file=sys.stderr)

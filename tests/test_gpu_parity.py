@@ -1021,7 +1021,7 @@ def test_bench_two_gloo_ranks_share_one_gpu(scaling):
     env = dict(os.environ, NMX_BENCH_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "128",
-           "--cpu-windows", "0", "--no-cold-start", "--no-mode-a", "--backend", "gloo", "--scaling", scaling]
+           "--full", "--cpu-windows", "0", "--no-cold-start", "--no-mode-a", "--backend", "gloo", "--scaling", scaling]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

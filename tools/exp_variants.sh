@@ -9,13 +9,13 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   echo "== [$i] $cfg"
-  env $cfg timeout 300 python bench.py --steps 6 --warmup 3 --cpu-windows 0 --no-cold-start > $O/v$i.json 2>$O/v$i.err
+  env $cfg timeout 300 python bench.py --full --steps 6 --warmup 3 --cpu-windows 0 --no-cold-start > $O/v$i.json 2>$O/v$i.err
   python - "$O/v$i.json" << 'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: round(v, 3) for k, v in d["kernel_ms_per_step"].items()}, "ms/step", round(d["ms_per_step"], 3), d["kernels"]["bank"], d["kernels"]["prep"])
 PY
-  env $cfg NMX_OVERLAP=0 timeout 300 python bench.py --steps 4 --warmup 2 --cpu-windows 0 --no-cold-start 2>/dev/null | python -c "
+  env $cfg NMX_OVERLAP=0 timeout 300 python bench.py --full --steps 4 --warmup 2 --cpu-windows 0 --no-cold-start 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  solo:', {k: round(v,3) for k,v in d['kernel_ms_per_step'].items()})"
   env $cfg timeout 300 python tools/dump_outputs.py $O/out$i.npy > /dev/null 2>$O/d$i.err

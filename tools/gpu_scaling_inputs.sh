@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out
 for c in 256 128 64 32; do
-  timeout 300 python bench.py --channels $c --steps 100 --warmup 5 --cpu-windows 0 --no-cold-start --no-mode-a > $O/tmp_b.json 2>/dev/null
+  timeout 300 python bench.py --full --channels $c --steps 100 --warmup 5 --cpu-windows 0 --no-cold-start --no-mode-a > $O/tmp_b.json 2>/dev/null
   python - <<PY
 import json
 d=json.load(open("$O/tmp_b.json"))
