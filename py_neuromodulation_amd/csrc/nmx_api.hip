@@ -19,7 +19,9 @@
 #include "nmx_k_resample.h"
 #include "nmx_k_resample64.h"
 #include "nmx_k_sharpwave.h"
+#include "nmx_k_specmm.h"
 #include "nmx_k_timeosc.h"
+#include "nmx_k_timeosc_w510.h"   // (the kernel predicates build_timeosc chooses with)
 
 #include <cstdlib>
 #include <map>
@@ -37,9 +39,6 @@ __global__ void __launch_bounds__(256) nmx_kern_bank(const NmxBankArgs A, int n_
   // one item per workgroup; partitioned mode (NmxBankArgs::ups_*): a workgroup walks items with its scratch slot
   for (int item = blockIdx.x; item < n_items; item += gridDim.x)
     nmx_bank_item(A, item / A.n_channels, item % A.n_channels, nmx_smem, (int)blockIdx.x);
-}
-__global__ void __launch_bounds__(256) nmx_kern_hilbert(const NmxHilbertArgs A) {
-  nmx_hilbert_item(A, (long long)blockIdx.x, nmx_smem);
 }
 template <int CH>
 __global__ void __launch_bounds__(256) nmx_kern_burst_thr(const NmxBurstThrArgs A) {
@@ -179,6 +178,10 @@ static int be_device_count() {
   return n;
 }
 static int be_set_device(int dev) { return be_hip(hipSetDevice(dev), "hipSetDevice"); }
+static int be_cu_count(int dev) {
+  int n = 0;
+  return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+}
 // Device allocations are recycled across plans.  The reference builds a fresh DataProcessor per Stream and per run
 // (stream/stream.py:130, 233-242): a plan's ~50 hipMalloc and its owner's ~35 hipFree (each an unmap and a device
 // synchronisation, ~0.1 ms) were 10 of the 39 ms a fresh Stream on a warm process costs.  A freed block goes to a
@@ -440,7 +443,6 @@ static void be_init_once() {
   if (!nmx_first_on_device(seen)) return;
   be_allow_lds(nmx_kern_timeosc);
   be_allow_lds(nmx_kern_bank);
-  be_allow_lds(nmx_kern_hilbert);
   be_allow_lds(nmx_kern_resample);
   be_allow_lds(nmx_kern_burst_thr<32>);
   be_allow_lds(nmx_kern_burst_thr<64>);
@@ -452,36 +454,28 @@ static void be_init_once() {
 }
 
 extern "C" void nmx_wave_launch_scan(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-extern "C" int nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-extern "C" int nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-extern "C" int nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-extern "C" int nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
+extern "C" void nmx_wave_launch_timeosc_w1000_low(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s);
+extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
+extern "C" void nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
+extern "C" void nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
+extern "C" void nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s);
 extern "C" void nmx_wave_launch_timeosc_w1000_todo(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-// -> 1 when the kernel launched leaves flagged windows to be_launch_timeosc_redo (the matrix-pipe kernel's dirty tiles)
-static int be_launch_timeosc(const NmxTimeOscArgs& A, int n_items, int nt, size_t lds, be_stream_t s) {
+// `kind`: the plan's choice (build_timeosc).  The matrix-pipe kernel leaves flagged windows to be_launch_timeosc_redo.
+static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind kind, int n_items, int nt, size_t lds, int n_cu, be_stream_t s) {
   be_init_once();
-  static int scan_ok = -1;
-  if (scan_ok < 0) { const char* v = getenv("NMX_SCAN_KERNEL"); scan_ok = !(v && v[0] == '0'); }
-  // no oscillatory feature: the register-resident scan (one wave per window, no LDS)
-  if (scan_ok && !A.fft.enabled && !A.welch.enabled && !A.stft.enabled && A.W <= 1024 && A.W >= 3) {
-    nmx_wave_launch_scan(&A, n_items, s);
-    return 0;
+  switch (kind) {
+    case NMX_TO_SCAN: nmx_wave_launch_scan(&A, n_items, s); return;
+    case NMX_TO_SPECMM: nmx_specmm_launch(&A, n_items, n_cu, s); return;
+    case NMX_TO_W1000_LOW: nmx_wave_launch_timeosc_w1000_low(&A, n_items, n_cu, s); return;
+    case NMX_TO_W1000: nmx_wave_launch_timeosc_w1000(&A, n_items, s); return;
+    case NMX_TO_STFT500: nmx_wave_launch_timeosc_stft500(&A, n_items, s); return;
+    case NMX_TO_W510: nmx_wave_launch_timeosc_w510(&A, n_items, s); return;
+    case NMX_TO_FIXED128: nmx_timeosc_fixed_launch128(&A, n_items, lds, s); return;
+    case NMX_TO_GENERIC:
+      hipLaunchKernelGGL(nmx_kern_timeosc, dim3(n_items), dim3(nt), lds, s, A);
+      nmxi_note_kernel("nmx_kern_timeosc");
+      return;
   }
-  // FFT band means of 1000-sample windows whose bins fit 32 rows: the spectrum on the matrix pipe (nmx_k_specmm.h)
-  // (any batch size, one window included: a result must not depend on how the hops were batched)
-  if (A.smm_tab) {
-    const int r = nmx_specmm_launch(&A, n_items, s);
-    if (r) return r == 2;
-  }
-  // default shape (W = 1000, band means): one wave per item, wave-level 500-point transforms
-  if (A.w500_tab && nmx_wave_launch_timeosc_w1000(&A, n_items, s)) return 0;
-  if (A.w500_tab && nmx_wave_launch_timeosc_stft500(&A, n_items, s)) return 0;
-  // 510-sample FFT / STFT segments (17 ms at 30 kHz): one wave per item, in-place prime-factor transforms
-  if (A.w510_tab && nmx_wave_launch_timeosc_w510(&A, n_items, s)) return 0;
-  if (nt == 128) { nmx_timeosc_fixed_launch128(&A, n_items, lds, s); return 0; }
-  hipLaunchKernelGGL(nmx_kern_timeosc, dim3(n_items), dim3(nt), lds, s, A);
-  nmxi_note_kernel("nmx_kern_timeosc");
-  return 0;
 }
 static void be_launch_timeosc_redo(const NmxTimeOscArgs& A, int n_items, be_stream_t s) {
   nmx_wave_launch_timeosc_w1000_todo(&A, n_items, s);
@@ -508,15 +502,7 @@ extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, s
 //   M = 2048, >= 4096 items: persistent 8-wave workgroups, pipelined   nmx_kern_bank_w64pp
 //   notch (odd-reflected window), >= 1024 items: four items / workgroup nmx_kern_notch_w64q
 //   a window or two (nmx_process_window): one wave per workgroup        nmx_kern_bank_w64 / nmx_kern_notch_w64
-static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds, be_stream_t s) {
-  static thread_local int n_cu = -1, n_cu_dev = -1;   // per host thread and device (multi-device streams)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (n_cu < 0 || n_cu_dev != dev) {
-    hipDeviceProp_t prop;
-    n_cu = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 0;
-    n_cu_dev = dev;
-  }
+static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds, int n_cu, be_stream_t s) {
   if (A.tw2) {
     if (!nmx_w64x2_launch_rd64(&A, n_items, n_cu, s)) g_be_rc = nmx_fail(NMX_E_INVALID, "M = 4096 FIR path: LDS budget");
     return;
@@ -530,8 +516,6 @@ static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds,
 }
 extern "C" int nmx_w64_takes_dc_rd64(const NmxBankW64Args*, int);
 static bool be_bank_w64_takes_dc(const NmxBankW64Args& A, int n_items) { return nmx_w64_takes_dc_rd64(&A, n_items) != 0; }
-extern "C" int nmx_wave_timeosc_takes_dc(const NmxTimeOscArgs* A);
-static bool be_timeosc_takes_dc(const NmxTimeOscArgs& A) { return nmx_wave_timeosc_takes_dc(&A) != 0; }
 extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s);
 static void be_launch_sharp_dense(const NmxSharpArgs& A, int n_items, be_stream_t s) {
   be_init_once();
@@ -543,35 +527,31 @@ static void be_launch_sharp_todo(const NmxSharpArgs& A, int n_items, size_t lds,
 }
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
-static void be_launch_hilbert(const NmxHilbertArgs& A, long long n_items, int nt, size_t lds, be_stream_t s) {
+static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind kind, long long n_items, size_t lds, be_stream_t s) {
   be_init_once();
-  static int w500 = -1;
-  if (w500 < 0) { const char* v = getenv("NMX_HILBERT_W500"); w500 = !(v && v[0] == '0'); }
-  if (w500 && A.W == 1000 && !A.hil_full) { nmx_wave_launch_hilbert_w500(&A, n_items, s); return; }
-  if (w500 && A.W == 2000 && A.w1000_tab) { nmx_wave_launch_hilbert_w1000(&A, n_items, s); return; }
-  if (nt == 128) { nmx_hilbert_fixed_launch128(&A, n_items, lds, s); return; }
-  hipLaunchKernelGGL(nmx_kern_hilbert, dim3((unsigned)n_items), dim3(nt), lds, s, A);
-  nmxi_note_kernel("nmx_kern_hilbert");
+  if (kind == NMX_HIL_W500) nmx_wave_launch_hilbert_w500(&A, n_items, s);
+  else if (kind == NMX_HIL_W1000) nmx_wave_launch_hilbert_w1000(&A, n_items, s);
+  else nmx_hilbert_fixed_launch128(&A, n_items, lds, s);
 }
-extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen);
-// windows_seen: hops every sequence has absorbed before this batch (-1: always the workgroup kernel)
-static void be_launch_burst_thr(const NmxBurstThrArgs& A, int n_items, int nt, size_t lds, be_stream_t s,
-                                long long windows_seen = -1) {
+extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen, bool list_lds);
+// windows_seen: hops every sequence has absorbed before this batch (-1: always the workgroup kernel); list_lds: the one-wave
+// walk may keep its top-K list in LDS
+static void be_launch_burst_thr(const NmxBurstThrArgs& A, int n_items, int nt, size_t lds, be_stream_t s, long long windows_seen,
+                                bool list_lds) {
   be_init_once();
   // ring already full at the first hop: the barrier-free one-wave walk over the list in L2
-  if (windows_seen > 0 && nmx_burst_thr_wave_ok(A, windows_seen)) { nmx_wave_launch_burst_thr(&A, n_items, s, windows_seen); return; }
+  if (windows_seen > 0 && nmx_burst_thr_wave_ok(A, windows_seen)) { nmx_wave_launch_burst_thr(&A, n_items, s, windows_seen, list_lds); return; }
   const int chunk = (A.K + nt - 1) / nt;
   if (nt > 256) { hipLaunchKernelGGL(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_wide"); }
   else if (chunk <= 32) { hipLaunchKernelGGL(nmx_kern_burst_thr<32>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<32>"); }
   else if (chunk <= 64) { hipLaunchKernelGGL(nmx_kern_burst_thr<64>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<64>"); }
   else { hipLaunchKernelGGL(nmx_kern_burst_thr<128>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<128>"); }
 }
-static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n_items, unsigned short* slots, float* sorted, be_stream_t s) {
+// split: the sort and the walk as two launches
+static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n_items, unsigned short* slots, float* sorted, bool split, be_stream_t s) {
   be_init_once();
   int n2 = 2048;
   while (n2 < A.W + (A.n_windows - 1) * A.overlap) n2 <<= 1;
-  const char* v_split = getenv("NMX_FILL_SPLIT");   // (read per launch -- once per fresh stream: the tests run both forms in one process)
-  const bool split = !(v_split && v_split[0] == '0');
   const size_t lds_walk = nmx_burst_fill_walk_lds(n2, A.n_windows);
   if (split && lds_walk <= 48 * 1024) {   // (a hop count whose slot pairs do not fit: the one-launch form)
     hipLaunchKernelGGL(nmx_kern_burst_fill_sort, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_sort_lds(n2), s, A, n2, slots, sorted);

@@ -184,6 +184,10 @@ struct NmxTimeOscArgs {
                            // NULL without that kernel
 };
 
+// the time / oscillatory and Hilbert kernels a plan launches, chosen when it is built (build_timeosc, build_hilbert)
+enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC };
+enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128 };
+
 #define NMXD_F_HJORTH (1u << 0)
 #define NMXD_F_RAW (1u << 1)
 #define NMXD_F_BANDPOWER (1u << 2)

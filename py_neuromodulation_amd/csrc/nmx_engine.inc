@@ -33,6 +33,21 @@ static int nmx_fail(int code, const std::string& msg) {
 #define NMX_REQUIRE(cond, msg) \
   do { if (!(cond)) return nmx_fail(NMX_E_INVALID, std::string(msg)); } while (0)
 
+#ifdef NMX_HOST_EMU
+// The logic emulator (tests/emu) runs the item code of every stage, whatever kernel the plan chose: its launch interface
+// carries none of those choices (it runs the matrix-pipe spectrum's arithmetic when run_chunk hands it `todo`).
+static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind, int n, int nt, size_t lds, int, be_stream_t s) { be_launch_timeosc(A, n, nt, lds, s); }
+static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind, long long n, size_t lds, be_stream_t s) { be_launch_hilbert(A, n, 128, lds, s); }
+static void be_launch_bank_w64(const NmxBankW64Args& A, int n, size_t lds, int, be_stream_t s) { be_launch_bank_w64(A, n, lds, s); }
+static void be_launch_burst_thr(const NmxBurstThrArgs& A, int n, int nt, size_t lds, be_stream_t s, long long seen, bool) {
+  be_launch_burst_thr(A, n, nt, lds, s, seen);
+}
+static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n, unsigned short* slots, float* sorted, bool, be_stream_t s) {
+  be_launch_burst_fill(A, n, slots, sorted, s);
+}
+static int be_cu_count(int) { return 256; }
+#endif
+
 namespace {
 
 constexpr double kPi = 3.14159265358979323846;
@@ -65,6 +80,7 @@ struct Plan {
   std::vector<double> notch_taps, ref_matrix;
   std::vector<double> notch_taps_used;     // what the notch kernels convolve with: h, or delta - h (NmxBankArgs::residual)
   int device = 0;
+  int n_cu = 256;                          // compute units of that device (the persistent kernels' grids)
   be_stream_t stream = nullptr;            // the plan's own stream
   be_stream_t last_stream = nullptr;       // stream of the last nmx_process_batch (may be the caller's): state calls wait for it
   be_stream_t stream_b = nullptr;          // side stream: bursts chain overlaps time/osc + sharp waves
@@ -90,6 +106,8 @@ struct Plan {
   // kernel argument templates (per-call fields are patched in process_batch)
   NmxTimeOscArgs to{};
   bool have_to = false;
+  NmxTimeOscKind to_kind = NMX_TO_GENERIC;
+  bool to_takes_dc = true;            // the kernel adds the carried offset on load (else: it reads a copy with it added back)
   FirStage bank;                      // band-pass bank: feeds bursts and sharp waves
   bool have_bank = false;
   FirStage notch;
@@ -97,8 +115,8 @@ struct Plan {
   std::vector<FirStage> pre;          // preprocessing_filter stages (one filter each)
   const float* w64e_tw = nullptr;     // twiddles of the M = 2048 channel-pair kernel (nmx_k_bank_w64e.h): notch and bank
   NmxHilbertArgs hil{};
+  NmxHilbertKind hil_kind = NMX_HIL_FIXED128;
   const float* w500_tab = nullptr;
-  int nt_hilbert = 128;
   NmxBurstThrArgs bthr{};
   NmxBurstStatArgs bstat{};
   bool have_bursts = false;
@@ -115,7 +133,10 @@ struct Plan {
   int chunk_windows = 1024;
   bool sharp_dense_first = false;   // compact-LDS dense launch + generic launch over the flagged items
   bool thr_wave = true;             // one-wave threshold walk once the burst ring is full (nmx_k_bursts.h)
-  bool thr_fill = true;             // fresh stream: sort-once walk of the fill phase (nmx_k_burst_fill.h)
+  bool thr_fill = true;             // fresh stream: sort-once walk of the fill phase (nmx_k_burst_fill.h) ...
+  bool fill_split = true;           // ... as two launches (sort, one-wave walk)
+  bool thr_list_lds = true;         // the one-wave walk may keep its top-K list in LDS while the stream is young
+  bool tiny_inline = true;          // host batches of a few hops on ONE stream (nmx_engine_run.inc)
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
   long long burst_windows_seen = 0; // host mirror of the per-sequence window counter (all sequences advance together)
   // scratch

@@ -75,6 +75,7 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   for (auto& t : P->timers) t = be_timer_t{};
   int rc = be_set_device(P->device);
   if (rc) { delete P; return rc; }
+  P->n_cu = be_cu_count(P->device);
   P->w_in = P->d.raw_window > 0 ? P->d.raw_window : P->d.window;   // samples per incoming window
   P->stream = be_stream_create();
   P->stream_b = be_stream_create_high();
@@ -155,9 +156,11 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   P->nt_timeosc = desc->window <= 1024 ? 128 : 256;
   P->nt_bank = 256;
   P->nt_thr = 256;
-  P->nt_hilbert = 128;
   P->thr_wave = env_int("NMX_THR_WAVE", 1) != 0;
   P->thr_fill = env_int("NMX_THR_FILL", 1) != 0;
+  P->fill_split = env_int("NMX_FILL_SPLIT", 1) != 0;
+  P->thr_list_lds = env_int("NMX_THR_LIST_LDS", 1) != 0;
+  P->tiny_inline = env_int("NMX_TINY_INLINE", 1) != 0;
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
   if ((rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) || (rc = build_notch(*P)) ||

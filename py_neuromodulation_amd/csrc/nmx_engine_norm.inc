@@ -5,6 +5,7 @@ namespace {
 struct NmxNormHandle {
   int device = 0, n_cols = 0, method = 0, cap = 0;
   float clip = 0.f;
+  bool scan_on = true;         // mean / z-score as scans (NMX_NORM_SCAN, read when the normaliser is created)
   long long seq = 0;
   float* d_ring = nullptr;
   float* d_sorted = nullptr;   // median methods: scratch, same shape as the ring
@@ -28,6 +29,7 @@ int nmx_norm_create(int32_t device, int32_t n_cols, int32_t method, float clip, 
   if (rc) return rc;
   NmxNormHandle* H = new NmxNormHandle();
   H->device = device; H->n_cols = n_cols; H->method = method; H->cap = n_hist; H->clip = clip;
+  H->scan_on = env_int("NMX_NORM_SCAN", 1) != 0;
   H->d_ring = (float*)be_alloc((size_t)n_hist * n_cols * sizeof(float));
   if (!H->d_ring) { delete H; return nmx_fail(NMX_E_NOMEM, "device allocation failed"); }
   if (method >= NMX_NORM_MEDIAN && method != NMX_NORM_POWER) {
@@ -82,8 +84,7 @@ int nmx_norm_process(nmx_norm* norm, float* rows, int64_t ld, int64_t n_rows, in
     if (H->method != NMX_NORM_POWER) {
       // mean / z-score: scans + independent cells (nmx_k_norm.h) in pieces of at most cap - 1 hops; the column walk for
       // the one-window call shape (a launch sequence of three is no gain there), short histories and the median family
-      static const bool scan_on = [] { const char* v = getenv("NMX_NORM_SCAN"); return !(v && v[0] == '0'); }();
-      const bool scan = scan_on && (H->method == NMX_NORM_MEAN || H->method == NMX_NORM_ZSCORE) && N.n_rows >= 8 &&
+      const bool scan = H->scan_on && (H->method == NMX_NORM_MEAN || H->method == NMX_NORM_ZSCORE) && N.n_rows >= 8 &&
                         H->cap - 1 >= 64 && H->cap < 65536;   // (a short history would cut a batch into many pieces of five launches each)
       if (!scan) { be_launch_norm(N, s); return 0; }
       const int piece = std::min<int>(N.n_rows, H->cap - 1);

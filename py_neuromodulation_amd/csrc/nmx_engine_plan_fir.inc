@@ -209,7 +209,7 @@ static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, i
         if (timed) { be_timer_stop(P.timers[cur], s); be_timer_start(P.timers[L.stage], s); }
         be_stage(cur = L.stage);
       }
-      be_launch_bank_w64(fir_launch_args(W, L), n_items, (size_t)W.lds_floats * 4, s);
+      be_launch_bank_w64(fir_launch_args(W, L), n_items, (size_t)W.lds_floats * 4, P.n_cu, s);
     }
     if (cur != first) be_stage(first);
   }
@@ -261,6 +261,9 @@ int build_hilbert(Plan& P) {
     if (!H.w1000_tab) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
   }
 #endif
+  // the kernel (be_launch_hilbert): one wave per series at W = 1000 / 2000, else the 128-thread workgroup kernel
+  const bool wave = env_int("NMX_HILBERT_W500", 1) != 0;
+  P.hil_kind = wave && d.window == 1000 ? NMX_HIL_W500 : wave && H.w1000_tab ? NMX_HIL_W1000 : NMX_HIL_FIXED128;
   return 0;
 }
 

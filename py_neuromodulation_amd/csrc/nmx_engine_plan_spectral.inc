@@ -203,6 +203,28 @@ int build_w500_tab(Plan& P) {
   return 0;
 }
 
+// the time / oscillatory kernel (be_launch_timeosc), in this order of precedence.  (The logic emulator runs the matrix-pipe
+// kernel's arithmetic or the generic item.)
+NmxTimeOscKind timeosc_kind(const Plan& P, const NmxTimeOscArgs& A) {
+#ifndef NMX_HOST_EMU
+  // no oscillatory feature: the register-resident scan (one wave per window, no LDS)
+  if (!A.fft.enabled && !A.welch.enabled && !A.stft.enabled && A.W <= 1024 && A.W >= 3 && env_int("NMX_SCAN_KERNEL", 1)) return NMX_TO_SCAN;
+#endif
+  // (any batch size, one window included: a result must not depend on how the hops were batched)
+  if (A.smm_tab && nmx_specmm_ok(A)) return NMX_TO_SPECMM;
+#ifndef NMX_HOST_EMU
+  // default shape (W = 1000, band means): one wave per item, wave-level 500-point transforms; the persistent form for the
+  // bands below bin 100
+  if (A.w500_tab && nmx_timeosc_w1000_ok(A))
+    return nmx_timeosc_w1000_low_ok(A) && env_int("NMX_TOW_PERSISTENT", 1) ? NMX_TO_W1000_LOW : NMX_TO_W1000;
+  if (A.w500_tab && nmx_timeosc_stft500_ok(A)) return NMX_TO_STFT500;
+  // 510-sample FFT / STFT segments (17 ms at 30 kHz): one wave per item, in-place prime-factor transforms
+  if (A.w510_tab && nmx_timeosc_w510_ok(A, A.w510_tab)) return NMX_TO_W510;
+  if (P.nt_timeosc == 128) return NMX_TO_FIXED128;
+#endif
+  return NMX_TO_GENERIC;
+}
+
 int build_timeosc(Plan& P) {
   const nmx_plan_desc& d = P.d;
   const unsigned mask = NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_STFT;
@@ -298,6 +320,8 @@ int build_timeosc(Plan& P) {
     if (!A.w510_tab) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
   }
 #endif
+  P.to_kind = timeosc_kind(P, A);
+  P.to_takes_dc = P.to_kind != NMX_TO_STFT500 && P.to_kind != NMX_TO_W510;
   P.have_to = true;
   return 0;
 }

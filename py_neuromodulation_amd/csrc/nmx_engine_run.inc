@@ -213,7 +213,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     if (P.bank.w64 || P.bank.a.partitioned) {
       NmxHilbertArgs H = P.hil;
       H.y = (const float*)P.yb.p; H.env = (float*)B_env.p;
-      be_launch_hilbert(H, (long long)nw * C * d.n_burst_bands, P.nt_hilbert, (size_t)H.lds_floats * 4, sb);
+      be_launch_hilbert(H, P.hil_kind, (long long)nw * C * d.n_burst_bands, (size_t)H.lds_floats * 4, sb);
     }
     if (P.overlap >= 2) {
       sb = P.stream_b;
@@ -247,7 +247,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
         const size_t n_slot = (size_t)n_seq * NMX_FILL_MAX;
         if ((rc = ensure(P.thr_slots, n_slot * (sizeof(unsigned short) + sizeof(float))))) return rc;
         float* sorted = (float*)P.thr_slots.p;   // (the floats first: 4-byte aligned whatever n_slot)
-        be_launch_burst_fill(hops(0, n), n_seq, (unsigned short*)(sorted + n_slot), sorted, sb);
+        be_launch_burst_fill(hops(0, n), n_seq, (unsigned short*)(sorted + n_slot), sorted, P.fill_split, sb);
         done = n;
       }
     }
@@ -263,10 +263,11 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       }
 #endif
       if (k_fill > 0 && k_fill < rem) {
-        be_launch_burst_thr(hops(done, k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, -1);
-        be_launch_burst_thr(hops(done + k_fill, rem - k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, seen + k_fill);
+        be_launch_burst_thr(hops(done, k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, -1, P.thr_list_lds);
+        be_launch_burst_thr(hops(done + k_fill, rem - k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, seen + k_fill,
+                            P.thr_list_lds);
       } else {
-        be_launch_burst_thr(hops(done, rem), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, P.thr_wave ? seen : -1);
+        be_launch_burst_thr(hops(done, rem), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, P.thr_wave ? seen : -1, P.thr_list_lds);
       }
     }
     P.burst_windows_seen += nw;
@@ -282,20 +283,21 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     A.out = d_out; A.clean_on_load = clean;
     A.starts_mod4 = (!starts || P.starts_mod4) ? 1 : 0;
     A.dcf = dcf;
-    if (dcf && !be_timeosc_takes_dc(A)) {
+    if (dcf && !P.to_takes_dc) {
       if ((rc = with_dc())) return rc;
       A.x = src_dc; A.ch_stride = W; A.win_stride = (long long)C * W; A.starts = nullptr; A.clean_on_load = 0; A.dcf = nullptr;
     }
     A.todo = nullptr;
-    if (A.smm_tab) {   // flags of the matrix-pipe kernel (nmx_k_specmm.h): a 16-bit mask per tile of 16 windows
+    const bool smm = P.to_kind == NMX_TO_SPECMM;
+    if (smm) {   // flags of the matrix-pipe kernel (nmx_k_specmm.h): a 16-bit mask per tile of 16 windows
       if ((rc = ensure(P.to_todo, (size_t)((nw + 15) / 16) * C * sizeof(unsigned short)))) return rc;
       A.todo = (unsigned short*)P.to_todo.p;
     }
     if (tev) be_timer_start(P.timers[2], s);
     be_stage(2);
-    const int redo = be_launch_timeosc(A, nw * C, P.nt_timeosc, (size_t)A.lds_floats * 4, s);
+    be_launch_timeosc(A, P.to_kind, nw * C, P.nt_timeosc, (size_t)A.lds_floats * 4, P.n_cu, s);
     if (tev) be_timer_stop(P.timers[2], s);
-    if (redo) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }   // (windows the kernel flagged: NaN / infinity on load; outside the stage's timer and kernel list)
+    if (smm) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }   // (windows the kernel flagged: NaN / infinity on load; outside the stage's timer and kernel list)
   }
   if (P.have_coh) {   // coherence between channel pairs: stateless, on the main stream behind the time / oscillatory kernel
     NmxCohArgs A = P.coh;
@@ -377,8 +379,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   // normaliser.  Side streams buy such a batch nothing -- its kernels are microseconds -- and every cross-stream hand-off
   // (fork / join of the bursts and sharp-wave chains, finalize stream, copy stream) is an event round trip of 10 - 25 us
   // on a 0.4 ms call.  (NMX_TINY_INLINE=0: the schedule of large batches.)
-  static const bool tiny_on = env_int("NMX_TINY_INLINE", 1) != 0;
-  const bool tiny = tiny_on && host && n_windows < 8 && !P.pipe_in_ready && !P.pipe_out_done;
+  const bool tiny = P.tiny_inline && host && n_windows < 8 && !P.pipe_in_ready && !P.pipe_out_done;
   struct OverlapGuard { Plan& P; int keep; ~OverlapGuard() { P.overlap = keep; } } overlap_guard{P, P.overlap};
   if (tiny) P.overlap = 0;
   be_stream_t sc = tiny ? s : P.stream_c;   // the copy stream of this batch (input)

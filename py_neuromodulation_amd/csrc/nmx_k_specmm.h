@@ -51,7 +51,7 @@ static_assert(NMX_SMM_RING >= 3 && NMX_SMM_RING <= 5, "ring depth");
 
 static inline bool nmx_specmm_ok(const NmxTimeOscArgs& A) {
   if (!A.smm_tab || A.W != 1000 || A.n_bands > 8 || A.n_bands < 1) return false;
-  if (!A.w500_tab || !A.todo) return false;   // (windows with a NaN / an infinity go to the wave-level kernel)
+  if (!A.w500_tab) return false;   // (windows with a NaN / an infinity go to the wave-level kernel: run_chunk gives it `todo`)
   if (A.welch.enabled || A.stft.enabled || !A.fft.enabled) return false;
   const NmxOsc& O = A.fft;
   if (O.complex_full || O.estimators != NMXD_EST_MEAN || O.return_spectrum || O.n != 1000) return false;

@@ -29,7 +29,7 @@
 #define NMX_TOW_LDS_FLOATS (1008 + 1000)
 #define NMX_TOW_LDS_FLOATS_NOSTFT 1008
 
-// can this configuration run on the wave kernel?  (host side, called by the launcher)
+// can this configuration run on the wave kernel?  (host side: build_timeosc)
 static inline bool nmx_timeosc_w1000_ok(const NmxTimeOscArgs& A) {
   if (!A.w500_tab || A.W != 1000 || A.n_bands > 8) return false;
   auto mean_only = [](const NmxOsc& O) {

@@ -3,8 +3,6 @@
 // nothing: the DFT table lives in each lane's registers, the LDS is four rings of step buffers).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "nmx_k_specmm.h"
 
 extern __shared__ __attribute__((aligned(16))) char nmx_smem_smm[];
@@ -57,21 +55,10 @@ __global__ void __launch_bounds__(256, 1) nmx_kern_specmm_w1000(const NmxTimeOsc
   W.flush();
 }
 
-extern "C" void nmx_wave_launch_timeosc_w1000_todo(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
-
-// returns 0 when the configuration needs another kernel, 1 / 2 when launched (2: windows may have been flagged)
-extern "C" int nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
-  static int on = -1;
-  if (on < 0) { const char* v = getenv("NMX_SPECMM"); on = (v && v[0] == '0') ? 0 : 1; }
-  if (!on || !nmx_specmm_ok(*A) || n_items < 1) return 0;
-  static thread_local int n_cu = 0, n_cu_dev = -1;   // per host thread and device (multi-device streams)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (!n_cu || n_cu_dev != dev) {
-    hipDeviceProp_t prop;
-    n_cu = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    n_cu_dev = dev;
-  }
+// the caller launches the pass over the flagged windows (nmx_wave_launch_timeosc_w1000_todo) behind it -- and behind its
+// stage timer, which brackets THIS kernel alone (bench.py: roofline_modeA is this kernel's launch duration).  (A window's
+// power can overflow behind a cleaning stage too: samples on the rail, re-referenced.)
+extern "C" void nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s) {
   const int n_win = n_items / A->n_channels;
   const long long n_tiles = (long long)((n_win + 15) / 16) * A->n_channels;
   long long grid = (n_tiles + NMX_SMM_WAVES - 1) / NMX_SMM_WAVES;
@@ -100,7 +87,4 @@ extern "C" int nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, hipStream
   }
 #endif
 #undef NMX_SMM_LAUNCH
-  // 2: the caller launches the pass over the flagged windows (nmx_wave_launch_timeosc_w1000_todo) -- behind its stage
-  // timer, which brackets THIS kernel alone (bench.py: roofline_modeA is this kernel's launch duration)
-  return 2;   // (a window's power can overflow behind a cleaning stage too: samples on the rail, re-referenced)
 }

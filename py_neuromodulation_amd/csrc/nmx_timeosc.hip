@@ -1,7 +1,7 @@
 // nmx_timeosc.hip -- the time / oscillatory and Hilbert kernels at their default launch width, compiled with
 // -DNMX_BLOCK_FIXED=128: NMX_NT is a constant, so the grid-stride loops of the statically planned
-// transforms and of the fused scans have compile-time trip counts.  nmx_api.hip keeps the
-// run-time-width version for other widths (NMX_NT_TIMEOSC, windows > 1024 samples).
+// transforms and of the fused scans have compile-time trip counts.  nmx_api.hip keeps the time /
+// oscillatory kernel's run-time-width version for windows > 1024 samples (256 threads).
 #ifndef NMX_BLOCK_FIXED
 #error "compile with -DNMX_BLOCK_FIXED=128"
 #endif

@@ -78,9 +78,7 @@ __global__ void __launch_bounds__(64) nmx_kern_burst_thr_wave(const NmxBurstThrA
   nmx_burst_thr_wave_item<NR, LL>(A, item / A.n_bands, item % A.n_bands, nmx_smem_wave);
 }
 
-extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen) {
-  const char* v_ll = getenv("NMX_THR_LIST_LDS");   // (read per launch: the tests run both forms in one process)
-  const bool lds_list = !(v_ll && v_ll[0] == '0');
+extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen, bool lds_list) {
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -212,52 +210,32 @@ nmx_kern_timeosc_w1000_low(const NmxTimeOscArgs A0, int n_items) {
 }
 
 
-// does the kernel be_launch_timeosc (nmx_api.hip) would pick take the carried offset (NmxTimeOscArgs::dcf)?  Every one but
-// the two special-shape kernels below (they read a copy of the windows with the offset added back: nmx_engine_run.inc)
-extern "C" int nmx_wave_timeosc_takes_dc(const NmxTimeOscArgs* A) {
-  if (!A->fft.enabled && !A->welch.enabled && !A->stft.enabled) return 1;
-  if (A->w500_tab && nmx_timeosc_w1000_ok(*A)) return 1;
-  if (A->w500_tab && nmx_timeosc_stft500_ok(*A)) return 0;
-  if (A->w510_tab && nmx_timeosc_w510_ok(*A, A->w510_tab)) return 0;
-  return 1;
+// the persistent form (nmx_timeosc_w1000_low_ok).  Resident waves per CU: 12, 3 per SIMD (168 VGPRs).  The channel of a
+// wave's items stays fixed -- and with it the XCD whose L2 holds the overlapping windows -- when the stride is a multiple
+// of the channel count
+extern "C" void nmx_wave_launch_timeosc_w1000_low(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s) {
+  int grid = n_cu * 12;
+  const int C = A->n_channels;
+  if (grid > C && grid % C) grid -= grid % C;
+  if (grid > n_items) grid = n_items;
+  const size_t lds = (size_t)NMX_TOW_LOW_LDS_FLOATS * 4;
+  const unsigned spec = nmx_tow_spec(*A);
+  if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_C2) {
+    hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_C2>), dim3(grid), dim3(64), lds, s, *A, n_items);
+    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 65809u>");
+  } else if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_DEFAULT) {
+    hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_DEFAULT>), dim3(grid), dim3(64), lds, s, *A, n_items);
+    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 196915u>");
+  } else if (A->n_bands <= 4) {
+    hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
+    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4>");
+  } else {
+    hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
+    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<8>");
+  }
 }
 
-// returns 0 when the configuration needs the generic kernel
-extern "C" int nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
-  if (!nmx_timeosc_w1000_ok(*A)) return 0;
-  static int n_cu = 0, want = 0, low_ok = 1;
-  if (!n_cu) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    want = 12;
-    const char* u = getenv("NMX_TOW_PERSISTENT");
-    low_ok = !(u && u[0] == '0');
-  }
-  if (low_ok && nmx_timeosc_w1000_low_ok(*A)) {
-    // resident waves per CU: 3 per SIMD (168 VGPRs).  The channel of a wave's items stays fixed -- and with it the XCD
-    // whose L2 holds the overlapping windows -- when the stride is a multiple of the channel count
-    int grid = n_cu * want;
-    const int C = A->n_channels;
-    if (grid > C && grid % C) grid -= grid % C;
-    if (grid > n_items) grid = n_items;
-    const size_t lds = (size_t)NMX_TOW_LOW_LDS_FLOATS * 4;
-    const unsigned spec = nmx_tow_spec(*A);
-    if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_C2) {
-      hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_C2>), dim3(grid), dim3(64), lds, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 65809u>");
-    } else if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_DEFAULT) {
-      hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_DEFAULT>), dim3(grid), dim3(64), lds, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 196915u>");
-    } else if (A->n_bands <= 4) {
-      hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4>");
-    } else {
-      hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_timeosc_w1000_low<8>");
-    }
-    return 1;
-  }
+extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   const size_t lds = (size_t)(A->stft.enabled ? NMX_TOW_LDS_FLOATS : NMX_TOW_LDS_FLOATS_NOSTFT) * 4;
   const int k = waves_per_wg(lds);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
@@ -272,7 +250,6 @@ extern "C" int nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_item
     hipLaunchKernelGGL(nmx_kern_timeosc_w1000<8>, grid, block, lds * k, s, *A, n_items, slice);
     nmxi_note_kernel("nmx_kern_timeosc_w1000<8>");
   }
-  return 1;
 }
 
 // The windows the matrix-pipe kernel (nmx_k_specmm.h) flagged -- a NaN or an infinity among the samples: it does not clean
@@ -324,8 +301,7 @@ __global__ void __launch_bounds__(256) nmx_kern_timeosc_stft500(const NmxTimeOsc
   NMX_WAVE_ITEM(item, smem, n_items, NMX_TOS_LDS_FLOATS);
   nmx_timeosc_stft500_item<NB>(A, item / A.n_channels, item % A.n_channels, smem);
 }
-extern "C" int nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
-  if (!nmx_timeosc_stft500_ok(*A)) return 0;
+extern "C" void nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   const int k = waves_per_wg((size_t)NMX_TOS_LDS_FLOATS * 4);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
   if (A->n_bands <= 4) {
@@ -335,7 +311,6 @@ extern "C" int nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_it
     hipLaunchKernelGGL(nmx_kern_timeosc_stft500<8>, grid, block, (size_t)NMX_TOS_LDS_FLOATS * 4 * k, s, *A, n_items);
     nmxi_note_kernel("nmx_kern_timeosc_stft500<8>");
   }
-  return 1;
 }
 
 // 510-sample transforms (17 ms at 30 kHz): prime-factor transform per wave (nmx_k_timeosc_w510.h)
@@ -355,8 +330,7 @@ __global__ void __launch_bounds__(256) NMX_W510_WPE nmx_kern_timeosc_w510(const 
   const NmxTimeOscArgs& A = *(const NmxTimeOscArgs*)(nmx_karg_p)__builtin_amdgcn_kernarg_segment_ptr();
   nmx_timeosc_w510_item<NB>(A, A.w510_tab, item / A.n_channels, item % A.n_channels, smem);
 }
-extern "C" int nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
-  if (!nmx_timeosc_w510_ok(*A, A->w510_tab)) return 0;
+extern "C" void nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   const int slice = NMX_TO510_LDS_FLOATS(A->W);
   const int k = waves_per_wg((size_t)slice * 4);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
@@ -367,7 +341,6 @@ extern "C" int nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_items
     hipLaunchKernelGGL(nmx_kern_timeosc_w510<8>, grid, block, (size_t)slice * 4 * k, s, *A, n_items, slice);
     nmxi_note_kernel("nmx_kern_timeosc_w510<8>");
   }
-  return 1;
 }
 
 // register-resident scan (Hjorth / Raw / LineLength only): four waves per workgroup, no LDS

@@ -75,20 +75,19 @@ static void be_stage_reset() {}
 static std::string be_stage_kernels(int) { return "host emulator (tests only)"; }
 
 // the matrix-pipe spectrum kernel's arithmetic and flag protocol (nmx_k_specmm.h): a 16-bit mask per tile of 16 windows of one
-// channel (tile = group * n_channels + channel), the flagged windows redone by the generic item code with its cleaning
-static int be_launch_timeosc(const NmxTimeOscArgs& A, int n_items, int, size_t lds, be_stream_t) {
-  static const bool smm = [] { const char* v = getenv("NMX_SPECMM"); return !(v && v[0] == '0'); }();
-  if (smm && A.smm_tab && nmx_specmm_ok(A)) {
+// channel (tile = group * n_channels + channel), the flagged windows redone by the generic item code with its cleaning.
+// The plan hands over `todo` when it chose that kernel (build_timeosc); every other choice runs the generic item.
+static void be_launch_timeosc(const NmxTimeOscArgs& A, int n_items, int, size_t lds, be_stream_t) {
+  if (A.todo) {
     const int C = A.n_channels, n_windows = n_items / C;
     for (int t = 0; t < ((n_windows + 15) / 16) * C; ++t) A.todo[t] = 0;
     for (int w = 0; w < n_windows; ++w)
       for (int c = 0; c < C; ++c)
         if (nmx_specmm_item_emu(A, w, c)) A.todo[(w / 16) * C + c] |= (unsigned short)(1u << (w & 15));
-    return 1;
+    return;
   }
   std::vector<float> sm(lds / 4 + 16);
   for (int it = 0; it < n_items; ++it) nmx_time_osc_item(A, it / A.n_channels, it % A.n_channels, sm.data());
-  return 0;
 }
 static void be_launch_timeosc_redo(const NmxTimeOscArgs& A, int n_items, be_stream_t) {
   const int C = A.n_channels, n_windows = n_items / C;
@@ -109,7 +108,6 @@ static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds,
   }
 }
 static bool be_bank_w64_takes_dc(const NmxBankW64Args&, int) { return false; }   // (the one-wave item code reads a copy)
-static bool be_timeosc_takes_dc(const NmxTimeOscArgs&) { return true; }
 static void be_launch_sharp_todo(const NmxSharpArgs&, int, size_t, const unsigned char*, be_stream_t) {}
 static void be_launch_sharp_dense(const NmxSharpArgs&, int, be_stream_t) {}
 static void be_launch_hilbert(const NmxHilbertArgs& A, long long n_items, int, size_t lds, be_stream_t) {

@@ -680,6 +680,61 @@ def test_alternative_code_paths_agree(gpu_lib, monkeypatch):
         check(" ".join(f"{k}={v}" for k, v in knobs.items()), got)
 
 
+def test_kernel_selectors_are_read_per_plan(gpu_lib, monkeypatch):
+    """The time / oscillatory and Hilbert kernels are chosen when a plan is built (build_timeosc, build_hilbert), and so
+    are the knobs that switch them: in ONE process, behind an engine of the default choice, an engine built with the knob
+    at 0 launches the other kernel.  Both agree with the float64 oracle under the standard policy."""
+    from oracle import nm_oracle as orc
+    from py_neuromodulation_amd import NMSettings
+    from py_neuromodulation_amd.engine import HotPathEngine
+
+    sfreq, C, n_hops = 1000.0, 6, 40
+    T = 1000 + (n_hops - 1) * 100
+    rng = np.random.default_rng(31)
+    t = np.arange(T) / sfreq
+    x = (rng.standard_normal((C, T)) * 50 + 10 * np.sin(2 * np.pi * 20 * t) + rng.uniform(-300, 300, (C, 1))).astype(np.float32)
+    ch = [f"ch{i}" for i in range(C)]
+    starts = np.arange(n_hops) * 100
+
+    def shape(*feats, low_bands=False):
+        s = NMSettings.get_default()
+        if low_bands:   # every band below bin 100, no STFT: the persistent wave kernel (Welch: not the matrix-pipe one)
+            s.frequency_ranges_hz = {k: v for k, v in s.frequency_ranges_hz.items() if v[1] < 100}
+        s.features.disable_all()
+        for f in feats:
+            setattr(s.features, f, True)
+        return s.validate()
+
+    cases = (("NMX_SCAN_KERNEL", shape("raw_hjorth", "linelength", "return_raw"), 2, "nmx_kern_scan", "nmx_kern_timeosc_fixed128"),
+             ("NMX_TOW_PERSISTENT", shape("fft", "welch", low_bands=True), 2, "nmx_kern_timeosc_w1000_low", "nmx_kern_timeosc_w1000<"),
+             ("NMX_HILBERT_W500", shape("bursts"), 4, "nmx_kern_hilbert_w500", "nmx_kern_hilbert_fixed128"),
+             ("NMX_SPECMM", shape("fft", "raw_hjorth", "linelength"), 2, "nmx_kern_specmm_w1000", "nmx_kern_timeosc_w1000"))
+    for knob, s, stage, default, other in cases:
+        feats = [orc._FEATURE_CLS[f](s, ch, sfreq) for f in s.features.get_enabled()]
+        want, vers = [], []
+        for a in starts:   # (in hop order: the oracle's Bursts carries its history)
+            w = x[:, a:a + 1000].astype(np.float64)
+            d = {}
+            for f in feats:
+                d.update(f.calc_feature(w))
+            want.append(list(d.values()))
+            ob = next((f for f in feats if isinstance(f, orc.Bursts)), None)
+            vers.append(parity.Verifier(s, ch, sfreq, w, bursts=parity.BurstTrace(ob) if ob else None))
+        for val, name in ((None, default), ("0", other)):
+            if val is not None:
+                monkeypatch.setenv(knob, val)
+            eng = HotPathEngine(s, ch, sfreq, lib=gpu_lib)
+            got = eng.process_batch(x, starts)
+            ran, keys = eng.kernels(stage), list(eng.keys)
+            eng.close()
+            monkeypatch.delenv(knob, raising=False)
+            assert name in ran and (val is None or default not in ran), f"{knob}={val}: {ran}"
+            assert keys == list(d)
+            for i in range(n_hops):
+                b, rep, _ = parity.compare(keys, got[i], want[i], s, sfreq, 400.0, 1000, verifier=vers[i])
+                assert b == 0, f"{knob}={val} hop {i}\n{rep}"
+
+
 def test_channel_pair_bank_odd_count_and_unequal_scales(gpu_lib):
     """The M = 1536 FIR-bank kernel carries two channels in one complex transform (nmx_k_bank_w64c.h).  An ODD
     channel count leaves the last channel alone in its transform; neighbours whose amplitudes differ by 10^4 and
