@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 12
+#define NMX_ABI_VERSION 13
 
 /* error codes */
 #define NMX_OK 0
@@ -220,6 +220,11 @@ typedef struct {
   uint32_t coh_methods;
   double coh_df;
   nmx_cols coh_cols;
+
+  /* Room behind the features: every output row of the plan is n_outputs + n_extra_cols floats (its row stride); the
+   * features fill columns [0, n_outputs), the extra columns are left to an attached grid projection (nmx_proj below)
+   * and hold NaN without one.  0 = today's layout. */
+  int32_t n_extra_cols;
 } nmx_plan_desc;
 
 typedef struct nmx_plan nmx_plan;
@@ -311,11 +316,12 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
 /* Timing of the last nmx_process_batch, measured with HIP events on the launch stream:
  * which = 0 whole batch, 1 pre-processing, 2 time/oscillatory kernel, 3 FIR-bank kernel,
  * 4 bursts kernels, 5 sharp-wave kernel, 6 second FIR-bank launch (the filters whose taps are too long for the
- * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel.  Blocks until the events have completed. */
+ * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel, 8 grid-projection kernel (attached nmx_proj).
+ * Stages 1..8 are those of the first chunk of the batch.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
 /* Names of the kernels the first launch sequence of the last nmx_process_batch ran in stage `which`
- * (1..7 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
+ * (1..8 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
  * (template arguments included).  Which variant runs depends on the shape, the batch size and the tuning
  * knobs, so measurement code names the kernel from here instead of hard-coding it.  NUL-terminated,
  * truncated to n - 1 characters. */
@@ -360,6 +366,48 @@ int nmx_norm_state_import(nmx_norm* norm, const void* src, int64_t n_bytes);
  * nmx_norm_process call.  norm == NULL detaches.  The normaliser must live on the plan's device and have
  * n_cols == the plan's n_outputs; the plan does not own it. */
 int nmx_plan_attach_norm(nmx_plan* plan, nmx_norm* norm);
+
+/* ---- Grid projection (processing/projection.py, stream/data_processor.py:292-294) ----
+ * The reference projects the normalised features of the ECoG / LFP channels onto the active points of a cortical and a
+ * subcortical grid: per hop Y = P @ X, X[channel][feature], P[point][channel] = (1 / d) / sum(1 / d) over the contacts
+ * within max_dist_mm.  The host resolves the key names (which columns of a row are feature f of channel k, where the
+ * grid keys go) and hands over the sparse rows of P:
+ *   n_feat, n_chan  features per projected channel, projected channels (n_chan <= 12288)
+ *   gather          [n_chan][n_feat] row column of feature f of channel k
+ *   n_points        active grid points of both grids; ptr[n_points + 1] / idx[nnz] / w[nnz]: their non-zero weights
+ *                   (CSR over the channels, float64)
+ *   out_col / out_stride  [n_points]: the row column of (point p, feature f) is out_col[p] + f * out_stride[p]
+ *   n_groups        1 .. 4 products (cortex grid / ECoG channels, subcortex grid / LFP channels): group g holds the
+ *                   channels [group_chan[g], group_chan[g + 1]) (group_chan[0] = 0, group_chan[n_groups] = n_chan),
+ *                   point_group[n_points] the group of every point (a point's weights address its group's channels only)
+ * Every output column must lie behind every gathered column.  Arrays are copied at creation.  Stateless.
+ * nmx_proj_process writes the grid columns of rows[n_rows][ld] IN PLACE (ld >= the last column used + 1), each a float64
+ * sum over the point's contacts rounded once to float32; a non-finite input of a channel of its group out of reach makes
+ * the point NaN (the 0 x NaN of the reference's dense product).  memspace / hip_stream as in nmx_process_batch; a host call is
+ * synchronous.  NMX_E_INVALID for a bad description or row layout. */
+typedef struct {
+  int32_t n_feat, n_chan;
+  const int32_t* gather;
+  int32_t n_points;
+  const int32_t* ptr;
+  const int32_t* idx;
+  const double* w;
+  const int32_t* out_col;
+  const int32_t* out_stride;
+  int32_t n_groups;
+  const int32_t* group_chan;
+  const int32_t* point_group;
+} nmx_proj_desc;
+typedef struct nmx_proj nmx_proj;
+int nmx_proj_create(int32_t device, const nmx_proj_desc* desc, nmx_proj** out);
+int nmx_proj_destroy(nmx_proj* proj);
+int nmx_proj_process(nmx_proj* proj, float* rows, int64_t ld, int64_t n_rows, int memspace, void* hip_stream);
+
+/* The projection INSIDE the launch sequence: once attached, every nmx_process_batch / nmx_process_window of `plan` projects
+ * its output rows on the device, after the attached normaliser, on the same stream, before they are copied back.  The plan's
+ * rows are n_outputs + n_extra_cols floats; every column the projection reads or writes must lie inside them.  proj == NULL
+ * detaches.  Same device as the plan; the plan does not own it. */
+int nmx_plan_attach_proj(nmx_plan* plan, nmx_proj* proj);
 
 /* Page-locked host memory for the buffers handed to memspace-0 calls: copies from / to it run at the full
  * PCIe rate and truly asynchronously (pageable memory is staged by the runtime at a fraction of that and

@@ -12,7 +12,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-NMX_ABI_VERSION = 12
+NMX_ABI_VERSION = 13
 NMX_MAX_BANDS = 16
 NMX_MAX_FILTERS = 24
 NMX_MAX_SW_COMBOS = 48
@@ -73,7 +73,15 @@ class PlanDesc(C.Structure):
         ("coh_n_pairs", C.c_int32), ("coh_pairs", C.POINTER(C.c_int32)), ("coh_nperseg", C.c_int32),
         ("coh_n_bands", C.c_int32), ("coh_bin_lo", C.c_int32 * NMX_MAX_BANDS), ("coh_bin_hi", C.c_int32 * NMX_MAX_BANDS),
         ("coh_features", C.c_uint32), ("coh_methods", C.c_uint32), ("coh_df", C.c_double), ("coh_cols", Cols),
+        ("n_extra_cols", C.c_int32),
     ]
+
+
+class ProjDesc(C.Structure):
+    _fields_ = [("n_feat", C.c_int32), ("n_chan", C.c_int32), ("gather", C.POINTER(C.c_int32)), ("n_points", C.c_int32),
+                ("ptr", C.POINTER(C.c_int32)), ("idx", C.POINTER(C.c_int32)), ("w", C.POINTER(C.c_double)),
+                ("out_col", C.POINTER(C.c_int32)), ("out_stride", C.POINTER(C.c_int32)), ("n_groups", C.c_int32),
+                ("group_chan", C.POINTER(C.c_int32)), ("point_group", C.POINTER(C.c_int32))]
 
 
 class NmxError(RuntimeError):
@@ -90,6 +98,7 @@ _EXPORTS = [
     "nmx_plan_attach_norm", "nmx_host_alloc", "nmx_host_free", "nmx_device_pool_trim", "nmx_reref_f64", "nmx_resample_f64",
     "nmx_plan_carries_offsets", "nmx_plan_set_offsets", "nmx_plan_get_offsets", "nmx_plan_set_pipeline",
     "nmx_host_stage_rows", "nmx_host_group_sums", "nmx_host_stage_parts", "nmx_host_widen_rows",
+    "nmx_proj_create", "nmx_proj_destroy", "nmx_proj_process", "nmx_plan_attach_proj",
 ]
 
 
@@ -156,6 +165,10 @@ class NmxLibrary:
         L.nmx_norm_state_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.nmx_norm_state_import.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.nmx_plan_attach_norm.argtypes = [C.c_void_p, C.c_void_p]
+        L.nmx_proj_create.argtypes = [C.c_int32, C.POINTER(ProjDesc), C.POINTER(C.c_void_p)]
+        L.nmx_proj_destroy.argtypes = [C.c_void_p]
+        L.nmx_proj_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+        L.nmx_plan_attach_proj.argtypes = [C.c_void_p, C.c_void_p]
         L.nmx_host_alloc.argtypes = [C.c_int64, C.POINTER(C.c_void_p)]
         L.nmx_host_free.argtypes = [C.c_void_p]
         L.nmx_device_pool_trim.argtypes = [C.c_int64, C.POINTER(C.c_int64)]

@@ -145,16 +145,16 @@ __global__ void __launch_bounds__(256) nmx_kern_tap(const NmxTapArgs A) {
 
 // ---- which kernels ran (per stage of the launch sequence; stage indices = nmx_last_timing_ms) ----
 static thread_local int g_stage = 0;
-static thread_local std::string g_stage_kernels[8];
+static thread_local std::string g_stage_kernels[16];
 extern "C" void nmxi_note_kernel(const char* name) {
-  std::string& s = g_stage_kernels[g_stage & 7];
+  std::string& s = g_stage_kernels[g_stage & 15];
   if (s.find(name) != std::string::npos) return;
   if (!s.empty()) s += " + ";
   s += name;
 }
 static void be_stage(int st) { g_stage = st; }
 static void be_stage_reset() { for (auto& s : g_stage_kernels) s.clear(); }
-static std::string be_stage_kernels(int st) { return g_stage_kernels[st & 7]; }
+static std::string be_stage_kernels(int st) { return g_stage_kernels[st & 15]; }
 
 // ---- backend ------------------------------------------------------------------------------
 typedef hipStream_t be_stream_t;

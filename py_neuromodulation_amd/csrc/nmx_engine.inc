@@ -24,6 +24,7 @@
 
 #include "../../include/nmx.h"
 #include "nmx_k_coh.h"   // coherence kernel + its be_launch_coh (HIP launcher, or the emulator's loop)
+#include "nmx_k_proj.h"  // grid-projection kernel + its be_launch_proj (likewise)
 
 static thread_local std::string g_nmx_err;
 static int nmx_fail(int code, const std::string& msg) {
@@ -165,9 +166,11 @@ struct Plan {
   int nt_resample = 256;
   double* d_kf = nullptr;
   size_t kf_bytes = 0;
-  be_timer_t timers[8];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence
-  std::string kernels[8];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
+  be_timer_t timers[9];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence,
+                          // 8 grid projection
+  std::string kernels[9];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
   nmx_norm* norm = nullptr; // attached feature normaliser (not owned): applied to every chunk's rows on the device
+  nmx_proj* proj = nullptr; // attached grid projection (not owned): behind the normaliser, on the same stream
   // offset split (nmx_engine_dc.inc): x = u + d per input row, the constants carried in float64 on the host
   bool dc_ok = false;            // every pre-processing stage of this plan is affine in the window
   bool dc_auto = true;           // learn the rows' constants in front of a re-reference kernel (fp32 input, no host offsets)
@@ -231,4 +234,5 @@ int env_int(const char* name, int dflt) {
 #include "nmx_engine_abi.inc"
 #include "nmx_engine_run.inc"
 #include "nmx_engine_norm.inc"
+#include "nmx_engine_proj.inc"
 #include "nmx_engine_host.inc"

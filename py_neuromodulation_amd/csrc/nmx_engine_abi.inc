@@ -63,6 +63,8 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   NMX_REQUIRE(desc->window >= 4 && desc->window <= 16384, "window must be in [4, 16384] samples");
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");
+  NMX_REQUIRE(desc->n_extra_cols >= 0 && (long long)desc->n_outputs + desc->n_extra_cols < (1ll << 30),
+              "n_extra_cols must be >= 0 and the row shorter than 2^30 floats");
   NMX_REQUIRE(desc->n_bands >= 0 && desc->n_bands <= NMX_MAX_BANDS, "n_bands out of range");
   NMX_REQUIRE(desc->n_filters >= 0 && desc->n_filters <= NMX_MAX_FILTERS, "n_filters out of range");
   const int ndev = be_device_count();

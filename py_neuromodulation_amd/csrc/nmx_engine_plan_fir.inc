@@ -404,7 +404,7 @@ int build_bank(Plan& P) {
   NMX_REQUIRE(d.n_filters <= NMX_MAX_FILTERS_DEV, "too many filters");
   FirStage& S = P.bank;
   NmxBankArgs& A = S.a;
-  A.n_outputs = d.n_outputs;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.W = d.window;
   A.pad_mode = 0;
@@ -491,7 +491,7 @@ int build_notch(Plan& P) {
   if (!d.notch_taps) return 0;
   FirStage& S = P.notch;
   NmxBankArgs& A = S.a;
-  A.n_outputs = d.n_outputs;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.W = P.w_in;
   const int L = d.n_notch_taps;

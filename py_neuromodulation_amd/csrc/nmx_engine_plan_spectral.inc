@@ -230,7 +230,7 @@ int build_timeosc(Plan& P) {
   const unsigned mask = NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_STFT;
   if (!(d.features & mask)) return 0;
   NmxTimeOscArgs& A = P.to;
-  A.n_outputs = d.n_outputs;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.W = d.window;
   A.n_bands = d.n_bands;
@@ -344,7 +344,7 @@ int build_coh(Plan& P) {
   A.nseg = (W - n) / A.step + 1;
   A.nfreq = n / 2 + 1;
   A.W = W;
-  A.n_outputs = d.n_outputs;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_pairs = d.coh_n_pairs;
   A.n_bands = d.coh_n_bands;
   for (int b = 0; b < d.coh_n_bands; ++b) {

@@ -92,7 +92,7 @@ int build_prefilters(Plan& P) {
   P.pre.assign(d.n_pre_filters, FirStage{});
   for (int i = 0; i < d.n_pre_filters; ++i) {
     NmxBankArgs& A = P.pre[i].a;
-    A.n_outputs = d.n_outputs;
+    A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
     A.n_channels = d.n_channels;
     A.W = P.w_in;
     A.pad_mode = 0;
@@ -159,7 +159,7 @@ int build_bursts(Plan& P) {
   NMX_REQUIRE(T.lds_floats * 4 <= 160 * 1024,
               "burst threshold state does not fit in 160 KiB LDS (ring x (1 - q) too large)");
   NmxBurstStatArgs& S = P.bstat;
-  S.n_outputs = d.n_outputs;
+  S.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   S.n_channels = d.n_channels;
   S.n_bands = d.n_burst_bands;
   S.W = d.window;
@@ -260,7 +260,7 @@ int build_kalman(Plan& P) {
   NMX_REQUIRE(d.kalman_Tp > 0 && d.kalman_sigma_v > 0, "Kalman Tp and sigma_v must be positive");
   NMX_REQUIRE((d.bp_kalman_mask >> d.n_bands) == 0u, "Kalman band outside frequency_ranges_hz");
   NmxKalmanArgs& K = P.kal;
-  K.n_outputs = d.n_outputs; K.n_channels = d.n_channels; K.n_bands = d.n_bands;
+  K.n_outputs = d.n_outputs + d.n_extra_cols; K.n_channels = d.n_channels; K.n_bands = d.n_bands;
   K.mask = d.bp_kalman_mask; K.cols = cv(d.bp_cols);
   const double T = d.kalman_Tp, sw2 = d.kalman_sigma_w * d.kalman_sigma_w;
   K.Tp = T; K.R = d.kalman_sigma_v;
@@ -283,7 +283,7 @@ int build_sharp(Plan& P) {
   NMX_REQUIRE(!(d.sw_between && !(d.sw_estimate_peaks && d.sw_estimate_troughs)),
               "apply_estimator_between_peaks_and_troughs needs both polarities estimated");
   NmxSharpArgs& A = P.sharp;
-  A.n_outputs = d.n_outputs;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.n_filters = d.n_sw_filters;
   A.W = d.window;

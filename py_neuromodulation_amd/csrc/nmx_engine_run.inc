@@ -322,17 +322,29 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
 // third stream costs two cross-stream hand-offs per call, as much as the whole batch of a light plan (BASELINE
 // config[1]: 0.27 ms of kernel, 0.70 ms per call with the detour, 0.30 without).
 // (`inline_on`: a batch of a few hops on ONE stream -- process_batch_impl -- normalises there too)
-static int chunk_finalize(Plan& P, float* d_outk, int F, int nw, be_stream_t inline_on = nullptr) {
+// An attached grid projection (nmx_engine_proj.inc) follows the normaliser on the same stream: it reads normalised rows.
+// `ld`: the row stride (features + the plan's extra columns); `timed`: the batch's first chunk (stage 8 timer / kernel name).
+static int proj_launch(nmx_proj* proj, float* rows, long long ld, int n_rows, be_stream_t s);
+static int chunk_finalize(Plan& P, float* d_outk, int ld, int nw, be_stream_t inline_on = nullptr, bool timed = false) {
   const int par = (int)(P.chunk_seq & 1);
   int rc = 0;
-  if (P.norm) {
+  if (timed) P.kernels[8].clear();
+  if (P.norm || P.proj) {
     be_stream_t sf = inline_on ? inline_on : P.stream_f;
     if (!inline_on) {
       be_stream_wait(sf, P.ev_main[par]);
       if (P.have_bursts && P.overlap) be_stream_wait(sf, P.ev_join[par]);
       if (P.overlap == 4 && P.have_sharp) be_stream_wait(sf, P.ev_join_d[par]);
     }
-    rc = nmx_norm_process(P.norm, d_outk, F, nw, 1, (void*)sf);
+    if (P.norm) rc = nmx_norm_process(P.norm, d_outk, ld, nw, 1, (void*)sf);
+    if (P.proj && !rc) {
+      const bool tev = timed && nw >= 8;
+      if (tev) be_timer_start(P.timers[8], sf);
+      if (timed) { be_stage_reset(); be_stage(8); }
+      rc = proj_launch(P.proj, d_outk, ld, nw, sf);
+      if (tev) be_timer_stop(P.timers[8], sf);
+      if (timed) { P.kernels[8] = be_stage_kernels(8); be_stage(0); }
+    }
     be_event_record(P.ev_done[par], sf);
   }
   ++P.chunk_seq;
@@ -340,7 +352,7 @@ static int chunk_finalize(Plan& P, float* d_outk, int F, int nw, be_stream_t inl
 }
 // stream `st` waits until the chunk of parity `par` is complete (its rows final); `own_main`: st IS the chunk's main stream
 static void chunk_wait_done(Plan& P, be_stream_t st, int par, bool own_main) {
-  if (P.norm) { be_stream_wait(st, P.ev_done[par]); return; }
+  if (P.norm || P.proj) { be_stream_wait(st, P.ev_done[par]); return; }
   if (!own_main) be_stream_wait(st, P.ev_main[par]);
   if (P.have_bursts && P.overlap) be_stream_wait(st, P.ev_join[par]);
   if (P.overlap == 4 && P.have_sharp) be_stream_wait(st, P.ev_join_d[par]);
@@ -366,7 +378,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   if (rc) return rc;
   be_stream_t s = hip_stream ? (be_stream_t)hip_stream : P.stream;
   P.last_stream = s;
-  const int Cin = d.n_channels_in, F = d.n_outputs;
+  const int Cin = d.n_channels_in, F = d.n_outputs + d.n_extra_cols;   // (F: the row stride)
   const float* d_x = x;
   long long d_ldx = ldx;
   float* d_out = out;
@@ -515,7 +527,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
     if (pre && host)   // same stream as the kernels: the next chunk's gather waits for this copy
       be_d2h_async(pre + (size_t)w0 * d.n_channels * d.window, d_prek, pre_n * sizeof(float), s);
     const int par_k = (int)(P.chunk_seq & 1);
-    if ((rc = chunk_finalize(P, d_outk, F, nw, tiny ? s : nullptr))) return bail(rc);   // (normaliser: hop order = chunk order)
+    if ((rc = chunk_finalize(P, d_outk, F, nw, tiny ? s : nullptr, w0 == 0))) return bail(rc);   // (normaliser: hop order = chunk order)
     last_par = par_k;
     if (host) {
       if (prev_w0 >= 0) fetch_back(prev_w0, prev_nw, par_k ^ 1);
@@ -529,9 +541,9 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   be_timer_stop(P.timers[0], s);
   if (host) {
     fetch_back(prev_w0, prev_nw, last_par);
-    if ((rc = be_sync_watch(so, P.kernels, 8))) return rc;   // (a watchdog verdict: nothing more is waited for)
-    if ((rc = be_sync_watch(sc, P.kernels, 8))) return rc;
-    if ((rc = be_sync_watch(s, P.kernels, 8))) return rc;
+    if ((rc = be_sync_watch(so, P.kernels, 9))) return rc;   // (a watchdog verdict: nothing more is waited for)
+    if ((rc = be_sync_watch(sc, P.kernels, 9))) return rc;
+    if ((rc = be_sync_watch(s, P.kernels, 9))) return rc;
     if (P.pipe_out_done) __atomic_store_n(P.pipe_out_done, (int64_t)n_windows, __ATOMIC_RELEASE);
   }
   return be_check_launch();
@@ -553,7 +565,7 @@ int nmx_process_batch_tap(nmx_plan* plan, const float* x, int64_t ldx, int64_t n
 int nmx_process_window(nmx_plan* plan, const double* x, int64_t ldx, float* out, uint8_t* nan_mask) {
   Plan* P = (Plan*)plan;
   if (!P || !x || !out) return nmx_fail(NMX_E_INVALID, "null argument");
-  const int Cin = P->d.n_channels_in, W = P->w_in, F = P->d.n_outputs;
+  const int Cin = P->d.n_channels_in, W = P->w_in, F = P->d.n_outputs + P->d.n_extra_cols;
   // The reference's real-time loop makes this call once per hop (stream/stream.py:280-296): everything that crosses the
   // bus lives in ONE page-locked staging block of the plan -- the window cast to float32, the feature row, the mask -- so
   // both copies are plain DMA transfers (a pageable source is staged by the runtime, synchronously: ~0.1 ms per MB).
@@ -669,7 +681,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
 
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms) {
   Plan* P = (Plan*)plan;
-  if (!P || !ms || which < 0 || which > 7) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !ms || which < 0 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
   be_set_device(P->device);
   *ms = be_timer_elapsed(P->timers[which]);
   return 0;
@@ -795,7 +807,7 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
-  if (!P || !buf || n < 1 || which < 1 || which > 7) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !buf || n < 1 || which < 1 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
   const std::string& k = P->kernels[which];
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
   memcpy(buf, k.data(), m);

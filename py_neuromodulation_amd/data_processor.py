@@ -29,6 +29,7 @@ from . import channels as chmod
 from . import fir_design
 from .engine import HotPathEngine, parallel_cast, table_empty
 from .processing import DeviceFeatureNormalizer, FeatureNormalizer
+from .projection import DeviceProjection, GridProjection
 from .settings import NMSettings
 
 PREPROCESSOR_ORDER = ["preprocessing_filter", "notch_filter", "raw_resampling", "re_referencing",
@@ -141,7 +142,11 @@ class DataProcessor:
                  resample_features_at_new_rate: bool = False, local_inputs: bool = False,
                  staging_slot: int = 0, _share: "DataProcessor | None" = None) -> None:
         """``_share``: the processor this one is the twin of for another window length (`_for_length`): the twin takes
-        its feature normaliser, user features and table of twins instead of building its own."""
+        its feature normaliser, user features, grid projection and table of twins instead of building its own.
+
+        ``coord_names`` / ``coord_list`` / ``path_grids``: the contacts' coordinates and the directory of grid_cortex.tsv /
+        grid_subcortex.tsv for the grid projection (postprocessing.project_cortex / project_subcortex,
+        processing/projection.py); ``path_grids=None`` takes the grids of an installed reference package."""
         self.settings = NMSettings.load(settings)
         self.channels = chmod.load_channels(channels)
         # (what a twin for another window length is built from: `process` under the reference's own loop, below)
@@ -155,8 +160,15 @@ class DataProcessor:
         self.line_noise = line_noise
         self.verbose = verbose
         st = self.settings
+        self._proj = None            # grid projection: the host plan (projection.GridProjection) ...
+        self._proj_dev = None        # ... and its device object for the rows of the engine
+        self._proj_in_engine = False
         if st.postprocessing.project_cortex or st.postprocessing.project_subcortex:
-            raise NotImplementedError("grid projection is outside the accelerated hot path")
+            if channel_subset is not None:   # a grid point mixes channels of every shard
+                raise NotImplementedError("grid projection (project_cortex / project_subcortex) needs every channel in one "
+                                          "plan: it is not supported with channels sharded over several devices (use one device)")
+            self._proj = _share._proj if _share is not None else GridProjection(st, self.channels, coord_names, coord_list,
+                                                                               path_grids)
         self.ch_names_used, self.feature_idx, self.target_idx = chmod.channel_info(self.channels)
         n_all = len(self.channels)
 
@@ -256,29 +268,42 @@ class DataProcessor:
                 full = loc if not (loc.shape[0] == loc.shape[1] and np.array_equal(loc, np.eye(len(loc)))) else None
                 self.local_rows = rows
                 self.local_groups = [groups[k] for k in used_groups]
+        from . import user_features as _registered
+
+        has_user = (_share._user is not None) if _share is not None else bool(_registered and not dry_run
+                                                                             and channel_subset is None)
+        # the grid columns follow the built-in ones in the engine's rows (the key list is known when the plan is built);
+        # with user features their keys come first, and the projection runs on the merged table (_project_user)
+        grid = self._proj is not None and not has_user
+        extra = (lambda keys: self._proj.layout(keys).n_grid) if grid else 0
         if resample_to is None:
             self.engine = HotPathEngine(st, names, self.sfreq_raw, ref_matrix=full, notch_taps=notch_taps,
                                         device=device, window=window, lib=lib, dry_run=dry_run,
-                                        pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot)
+                                        pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot, extra_cols=extra)
         elif resample_features_at_new_rate:   # `window` counts RAW samples (the generator cuts raw data)
             self.engine = HotPathEngine(st, names, resample_to, ref_matrix=full, notch_taps=notch_taps,
                                         device=device, lib=lib, dry_run=dry_run,
                                         resample_from=self.sfreq_raw, raw_window=window, pre_taps=pre_taps,
-                                        raw_norm=raw_norm, staging_slot=staging_slot)
+                                        raw_norm=raw_norm, staging_slot=staging_slot, extra_cols=extra)
             self.sfreq_raw = resample_to
         else:   # the reference: windows resampled, everything designed with the raw rate
             self.engine = HotPathEngine(st, names, self.sfreq_raw, ref_matrix=full, notch_taps=notch_taps,
                                         device=device, lib=lib, dry_run=dry_run,
                                         resample_from=self.sfreq_raw, resample_to=resample_to,
-                                        raw_window=window, pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot)
+                                        raw_window=window, pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot,
+                                        extra_cols=extra)
         self.keys = list(self.engine.keys)
+        layout = None
+        if grid:
+            layout = self._proj.layout(self.engine.keys)
+            self.keys += layout.grid_keys
         # user features: instantiated after the built-ins with the same arguments (feature_processor.py:45-53); a
         # channel shard leaves them to its coordinator (they see ALL channels: sharding.MultiDeviceProcessor)
-        from . import user_features as _registered
-
         self._user = None
         if _share is not None:
             self._user = _share._user
+            if self._user is not None:   # (one key list: the plugin and grid keys are appended to it at the first hop)
+                self.keys = _share.keys
         elif _registered and not dry_run and channel_subset is None:
             self._user = UserColumns(st, names, self.sfreq_raw, self.keys, device=device, lib=lib)
         self._user_chunk = 64                          # hops per tapped batch (bounds the [n, C, W] hand-back)
@@ -292,14 +317,22 @@ class DataProcessor:
                 # every method of normalization.py:57-70: one HIP scan per batch of hops; the column mask carries the
                 # "psd" exclusion (stream/data_processor.py:263-290)
                 mask = None
+                feat = self.engine.keys   # (the feature columns: not the grid columns behind them)
                 if not st.feature_normalization_settings.normalize_psd:
-                    mask = np.array(["psd" not in k for k in self.keys], dtype=np.uint8)
-                self.device_normalizer = DeviceFeatureNormalizer(st, len(self.keys), colmask=mask,
+                    mask = np.array(["psd" not in k for k in feat], dtype=np.uint8)
+                self.device_normalizer = DeviceFeatureNormalizer(st, len(feat), colmask=mask,
                                                                  device=device, lib=lib)
             if _share is None or _share._norm_in_engine:
                 # inside the engine's launch sequence: rows come back normalised (no second round trip)
                 self.engine.attach_normalizer(self.device_normalizer)
                 self._norm_in_engine = True
+        if layout is not None and layout.n_grid and not dry_run:
+            # stateless: the twins of other window lengths with the same key list share the device object
+            share = _share._proj_dev if _share is not None else None
+            self._proj_dev = share if share is not None and share.layout is layout else DeviceProjection(layout, device, lib)
+            if self.device_normalizer is None or self._norm_in_engine:   # (it reads normalised rows)
+                self.engine.attach_projection(self._proj_dev)
+                self._proj_in_engine = True
         self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
         self.cnt_samples = 0
         self.settings_token = None
@@ -309,9 +342,20 @@ class DataProcessor:
         from . import file_writer as fw
 
         sidecar = {"original_fs": self._sfreq_raw_orig, "final_fs": self.sfreq_raw, "sfreq": self.sfreq_features}
+        sidecar.update(self.projection_sidecar())
         if additional_args is not None:
             sidecar = sidecar | additional_args
         fw.save_sidecar(sidecar, out_dir, prefix)
+
+    def projection_sidecar(self) -> dict:
+        """What the grid projection adds to the sidecar (stream/data_processor.py:326-333): coords, grid_cortex,
+        proj_matrix_cortex, grid_subcortex, proj_matrix_subcortex; {} without a projection."""
+        return self._proj.sidecar() if self._proj is not None else {}
+
+    @property
+    def projection(self):
+        """The grid projection's host plan (projection.GridProjection: matrices, active points, channels) or None."""
+        return self._proj
 
     def save_settings(self, out_dir, prefix: str = "") -> None:
         self.settings.save(out_dir, prefix)
@@ -343,10 +387,19 @@ class DataProcessor:
 
     # ------------------------------------------------------------------------------------
     def _finish(self, out: np.ndarray, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
-        """Engine rows ``float32[n, F]`` in hop order -> the float64 table: the normaliser (unless it ran inside the
-        engine), the cast, the user columns, the NaN policy (last: the plugin keys follow it too)."""
+        """Engine rows ``float32[n, row_width]`` in hop order -> the float64 table: the normaliser (unless it ran inside the
+        engine), the grid projection (likewise), the cast, the user columns and their projection, the NaN policy (last:
+        the plugin and grid keys follow it too)."""
+        F = self.engine.n_outputs
         if self.device_normalizer is not None and not self._norm_in_engine:
-            out = self.device_normalizer.process_batch(out)
+            if out.shape[1] == F:
+                out = self.device_normalizer.process_batch(out)
+            else:   # (the grid columns behind the features)
+                out = np.array(out, dtype=np.float32, order="C")
+                out[:, :F] = self.device_normalizer.process_batch(out[:, :F])
+        if self._proj_dev is not None and not self._proj_in_engine and out.shape[1] > F:
+            out = np.require(out, np.float32, "C")
+            self._proj_dev.process(out)
         if len(out) == 1:   # (one hop, `process`: the pooled table and the threaded cast cost more than they save)
             table = out.astype(np.float64)
         else:
@@ -354,7 +407,22 @@ class DataProcessor:
             parallel_cast(table, out, None, self.engine.lib)
         if user is not None:
             table = self._user.merge(table, user)
+            if self._proj is not None:
+                table = self._project_user(table)
         return self._nan_cols.apply(table, mask)
+
+    def _project_user(self, table: np.ndarray) -> np.ndarray:
+        """The grid projection behind the user columns (dict.update after the plugin keys): laid out at the first hop, when
+        the plugin keys are known (Projection.init_projection_run); the grid keys are appended to the key list the plugins
+        extended -- the one the NaN policy scans."""
+        u = self._user
+        g = getattr(u, "grid", None)
+        if g is None:
+            lay = self._proj.layout(u.keys)
+            dev = DeviceProjection(lay, self._ctor["device"], self.engine.lib) if lay.n_grid else None
+            u.keys.extend(lay.grid_keys)
+            g = u.grid = (lay, dev)
+        return g[1].process_table(table) if g[1] is not None else table
 
     # -- user-registered features (features/feature_processor.py:52-53,80-82) ----------------------
     @property
@@ -466,10 +534,14 @@ class DataProcessor:
     # -- ragged window lengths (a non-integer number of samples per segment): `Stream.run` cuts the hops into
     # consecutive runs of one length, one processor per length; what carries over from hop to hop travels between them
     def ragged_prepare(self) -> None:
-        """The feature normaliser is sequential over ALL hops: it runs on the merged table (`ragged_finish`)."""
+        """The feature normaliser is sequential over ALL hops: it runs on the merged table (`ragged_finish`), and the grid
+        projection, which reads normalised rows, behind it."""
         if self._norm_in_engine:
             self.engine.attach_normalizer(None)
             self._norm_in_engine = False
+        if self._proj_in_engine:
+            self.engine.attach_projection(None)
+            self._proj_in_engine = False
 
     def ragged_state(self):
         """Burst history, Kalman filters ... of the engine (its layout depends on sfreq and the settings, not on the

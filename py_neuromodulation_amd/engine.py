@@ -332,7 +332,8 @@ class HotPathEngine:
                  window: int | None = None, dry_run: bool = False,
                  resample_from: float | None = None, raw_window: int | None = None,
                  pre_taps: Sequence[np.ndarray] | None = None,
-                 raw_norm: tuple | None = None, resample_to: float | None = None, staging_slot: int = 0) -> None:
+                 raw_norm: tuple | None = None, resample_to: float | None = None, staging_slot: int = 0,
+                 extra_cols=0) -> None:
         """``sfreq`` is the rate every feature and filter is DESIGNED with (what the reference passes to the
         feature constructors).  ``resample_from`` = sampling rate of the incoming windows when they are
         resampled (raw_resampling, processing/resample.py:19-60): incoming windows then hold ``raw_window``
@@ -346,7 +347,11 @@ class HotPathEngine:
         seg_s = segment_length_features_ms / 1000).
 
         ``dry_run=True`` only derives the plan description and the key list (no library, no
-        GPU) -- used to lay out the global column order when channels are sharded over GPUs."""
+        GPU) -- used to lay out the global column order when channels are sharded over GPUs.
+
+        ``extra_cols``: columns behind the features in every output row (an int, or a function of the key list that
+        returns one): room for the grid projection (``attach_projection``).  The rows are then ``row_width`` =
+        n_outputs + n_extra floats; 0 keeps the plain layout."""
         self.lib = None if dry_run else (lib if lib is not None else _lib.get_library())
         self.settings = settings
         self.ch_names = list(ch_names)
@@ -377,6 +382,9 @@ class HotPathEngine:
         self.coh_pairs: list[tuple[int, int]] = []   # coherence: (seed, target) channel indices of the emitted pairs
         self.desc = self._build(ref_matrix, notch_taps, device, bank_taps, sharpwave_taps)
         self.n_outputs = len(self.keys)
+        self.n_extra = int(extra_cols(self.keys) if callable(extra_cols) else extra_cols)
+        self.desc.n_extra_cols = self.n_extra
+        self.row_width = self.n_outputs + self.n_extra   # floats per output row (features, then the extra columns)
         self.C_in = int(self.desc.n_channels_in)
         self._plan = C.c_void_p()
         self._dc = None        # host offsets in force (None: not decided yet -- `_host_offsets`)
@@ -858,14 +866,14 @@ class HotPathEngine:
             self._dc, self._dc_any = np.zeros(self.C_in), False
 
     def process_window(self, data: np.ndarray, want_nan_mask: bool = False):
-        """data[C_in, W] (float64, may be a non-contiguous view) -> float32[n_outputs]."""
+        """data[C_in, W] (float64, may be a non-contiguous view) -> float32[row_width]."""
         data = np.asarray(data, dtype=np.float64)
         if data.ndim != 2 or data.shape[0] != self.C_in or data.shape[1] != self.W_in:
             raise ValueError(f"expected data of shape ({self.C_in}, {self.W_in}), got {data.shape}")
         if data.strides[1] != 8:
             data = np.ascontiguousarray(data)
         self._host_offsets(data)   # (the library subtracts them from the float64 window itself)
-        out = np.empty(self.n_outputs, np.float32)
+        out = np.empty(self.row_width, np.float32)
         mask = np.zeros(self.C_in, np.uint8) if want_nan_mask else None
         self.lib.check(self.lib.lib.nmx_process_window(
             self._plan, data.ctypes.data, _ld(data), out.ctypes.data,
@@ -877,6 +885,12 @@ class HotPathEngine:
         window comes back already normalised, without a second host round trip (nmx_plan_attach_norm)."""
         self.lib.check(self.lib.lib.nmx_plan_attach_norm(self._plan, norm._h if norm is not None else None))
         self._norm = norm   # keep it alive
+
+    def attach_projection(self, proj) -> None:
+        """Run ``proj`` (a projection.DeviceProjection or None) inside this plan's launch sequence, behind the attached
+        normaliser: the grid columns of every row come back filled (nmx_plan_attach_proj; they need ``extra_cols``)."""
+        self.lib.check(self.lib.lib.nmx_plan_attach_proj(self._plan, proj._h if proj is not None else None))
+        self._proj = proj   # keep it alive
 
     def pinned_empty(self, shape, dtype=np.float32) -> np.ndarray:
         """A page-locked array of the caller's own: inputs / ``out=`` buffers allocated here move at the full PCIe
@@ -904,7 +918,7 @@ class HotPathEngine:
 
     def process_batch(self, data: np.ndarray, starts: np.ndarray, want_nan_mask: bool = False,
                       staged_output: bool = False, out: np.ndarray | None = None, tap: bool = False):
-        """data[C_in, T] host array, starts[n] window start samples -> float32[n, n_outputs].
+        """data[C_in, T] host array, starts[n] window start samples -> float32[n, row_width].
 
         ``tap=True`` appends float32[n, C, W] to the result: the pre-processed windows the features were computed
         from (nmx_process_batch_tap) -- the ``data`` argument of ``NMFeature.calc_feature`` for user-registered
@@ -913,7 +927,7 @@ class HotPathEngine:
         A recording that is not contiguous float32 is cast into a page-locked staging array (first axis
         split over a few threads): the host -> device copies then run at the PCIe rate next to the kernels;
         contiguous float32 input is handed over as it is (allocate it with ``pinned_empty`` for the same
-        effect).  ``out``: caller's float32[n, n_outputs] buffer.  ``staged_output=True`` returns a VIEW of
+        effect).  ``out``: caller's float32[n, row_width] buffer.  ``staged_output=True`` returns a VIEW of
         the library's page-locked output staging array (valid until the next call) instead of a fresh
         array -- for callers that convert / consume the rows right away."""
         data = np.asarray(data)
@@ -933,13 +947,14 @@ class HotPathEngine:
             x = np.ascontiguousarray(np.asarray(data, dtype=np.float64) - dc[:, None], dtype=np.float32)
         else:
             x = np.ascontiguousarray(data, dtype=np.float32)
+        F = self.row_width
         if out is not None:
-            if out.dtype != np.float32 or out.shape != (n, self.n_outputs) or not out.flags.c_contiguous:
-                raise ValueError(f"out must be a C-contiguous float32 array of shape ({n}, {self.n_outputs})")
-        elif staged_output and n * self.n_outputs >= (1 << 18):
-            out = self._pinned.array("out", (n, self.n_outputs), np.float32)
+            if out.dtype != np.float32 or out.shape != (n, F) or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous float32 array of shape ({n}, {F})")
+        elif staged_output and n * F >= (1 << 18):
+            out = self._pinned.array("out", (n, F), np.float32)
         else:
-            out = np.empty((n, self.n_outputs), np.float32)
+            out = np.empty((n, F), np.float32)
         if want_nan_mask and data.size >= (1 << 18):   # (page-locked next to page-locked samples / rows: see run_pipelined)
             mask = self._pinned.array("mask", (n, self.C_in), np.uint8)
             mask[:] = 0
@@ -971,7 +986,7 @@ class HotPathEngine:
         table they need no column insert)."""
         data = np.asarray(data)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
-        n, F = len(starts), self.n_outputs
+        n, F = len(starts), self.row_width
         if data.ndim != 2 or data.shape[0] != self.C_in:
             raise ValueError(f"expected data with {self.C_in} rows, got {data.shape}")
         small = data.size < (1 << 20) or n < 64 or os.environ.get("NMX_PIPELINE", "1") == "0"
@@ -1019,9 +1034,9 @@ class HotPathEngine:
         if not (_rows_ok(x, np.float32) and x.shape[0] == self.C_in and _rows_ok(table, np.float64) and table.shape[0] == n):
             raise ValueError("run_pipelined: float32 staging rows and a float64 table with one row per window")
         if runs is None:
-            runs = np.array([[0, 0, self.n_outputs]], dtype=np.int64)
+            runs = np.array([[0, 0, self.row_width]], dtype=np.int64)
         runs = np.ascontiguousarray(runs, dtype=np.int64).reshape(-1, 3)
-        out = self._pinned.array("out", (n, self.n_outputs), np.float32)
+        out = self._pinned.array("out", (n, self.row_width), np.float32)
         # (page-locked like `out`: a copy into PAGEABLE memory is synchronous for the calling thread -- the library's host
         # loop stood at the mask of chunk k - 1 until that chunk was complete, and the samples of chunk k + 1 waited with it)
         mask = self._pinned.array("mask", (n, self.C_in), np.uint8) if want_nan_mask else None
@@ -1050,7 +1065,7 @@ class HotPathEngine:
                     d = int(ctr[8])
                     if d > done:
                         lib.check(lib.lib.nmx_host_widen_rows(table.ctypes.data, table.strides[0] // 8, out.ctypes.data,
-                                                              self.n_outputs, done, d, runs.ctypes.data, len(runs), 0))
+                                                              self.row_width, done, d, runs.ctypes.data, len(runs), 0))
                         done = d
                     else:
                         time.sleep(0.0001)
@@ -1117,7 +1132,7 @@ class HotPathEngine:
     def kernels(self, which: int) -> str:
         """Kernels the last batch launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
         5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
-        7 coherence), named as rocprofv3 prints them."""
+        7 coherence, 8 grid projection), named as rocprofv3 prints them."""
         buf = C.create_string_buffer(512)
         self.lib.check(self.lib.lib.nmx_last_kernels(self._plan, which, buf, 512))
         return buf.value.decode()

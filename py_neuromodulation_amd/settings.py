@@ -211,6 +211,9 @@ def _default_dict() -> dict:
         "feature_normalization_settings": {"normalization_time_s": 30,
                                            "normalization_method": "zscore",
                                            "normalize_psd": False, "clip": 3},
+        # processing/projection.py:11-12 (ProjectionSettings), default_settings.yaml:80-84
+        "project_cortex_settings": {"max_dist_mm": 20},
+        "project_subcortex_settings": {"max_dist_mm": 5},
         "fft_settings": _osc(1000),
         "welch_settings": _osc(1000),
         "stft_settings": _osc(500),
@@ -409,6 +412,10 @@ class NMSettings(_Node):
         if self.bursts_settings.threshold < 0 or self.bursts_settings.time_duration_s < 0:
             errors.append("bursts_settings threshold / time_duration_s must be >= 0")
         errors += self.coherence_settings.errors()
+        for name in ("project_cortex_settings", "project_subcortex_settings"):   # NMField(gt=0.0)
+            v = self[name].max_dist_mm
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not v > 0:
+                errors.append(f"{name}.max_dist_mm must be a number > 0, got {v!r}")
         if errors:
             raise SettingsError("; ".join(errors))
 

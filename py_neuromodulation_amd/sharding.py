@@ -45,6 +45,14 @@ def channel_shard(n_channels: int, world_size: int, rank: int) -> range:
     return range(lo, lo + base + (1 if rank < rem else 0))
 
 
+def _no_projection(settings) -> None:
+    """A grid point mixes the features of channels of every shard: the projection needs them all in one plan."""
+    pp = settings.postprocessing
+    if pp.project_cortex or pp.project_subcortex:
+        raise NotImplementedError("grid projection (project_cortex / project_subcortex) needs every channel in one plan: "
+                                  "it is not supported with channels sharded over several devices (use one device)")
+
+
 def global_keys(sfreq, settings, channels) -> list[str]:
     """Reference column order for ALL channels (no GPU needed)."""
     dp = DataProcessor(sfreq, settings, channels, line_noise=50, verbose=False, dry_run=True)
@@ -58,6 +66,7 @@ class ShardedStream:
                  world_size: int = 1, device: int | None = None, lib=None, local_input: bool = False) -> None:
         self.sfreq = sfreq
         self.settings = NMSettings.load(settings)
+        _no_projection(self.settings)
         self.channels = chmod.load_channels(channels)
         self.line_noise = line_noise
         self.rank, self.world_size = rank, world_size
@@ -213,6 +222,7 @@ class MultiDeviceProcessor:
         from concurrent.futures import ThreadPoolExecutor
 
         self.settings = NMSettings.load(settings)
+        _no_projection(self.settings)
         self.channels = chmod.load_channels(channels)
         devices = [int(d) for d in devices]
         if not devices:
@@ -295,6 +305,10 @@ class MultiDeviceProcessor:
     @property
     def user_keys(self):
         return self._user.user_keys if self._user is not None else None
+
+    def projection_sidecar(self) -> dict:
+        """No grid projection across devices (``_no_projection``): nothing to add to the sidecar."""
+        return {}
 
     def reset(self) -> None:
         for p in self.parts:

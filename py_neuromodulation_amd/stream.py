@@ -53,6 +53,7 @@ class Stream:
         self._resample_new_rate = resample_features_at_new_rate
         self._lib = lib  # None = the product library (libnmx.so); tests may inject a binding
         self.data = data
+        self.path_grids, self.coord_names, self.coord_list = path_grids, coord_names, coord_list
         self.sess_right = None
         self.is_running = False
         # fail early like the reference (it builds a DataProcessor in __init__, :130)
@@ -69,10 +70,13 @@ class Stream:
         reference reads afresh on every run (stream/stream.py:233-242 builds a new DataProcessor per run)."""
         from . import user_features
 
+        coords = None if self.coord_list is None else np.asarray(self.coord_list, dtype=np.float64).tobytes()
         return (settings_token if settings_token is not None else self._settings_token(), repr(self.line_noise),
                 repr(self.sfreq), bool(self._resample_new_rate),
                 int(self.device), tuple(self.devices or ()), id(self._lib),
-                tuple((k, id(v)) for k, v in user_features.items()))
+                tuple((k, id(v)) for k, v in user_features.items()),
+                None if self.coord_names is None else tuple(self.coord_names), coords,
+                None if self.path_grids is None else str(self.path_grids))
 
     def _make_processor(self, window):
         if self.devices is not None and len(self.devices) > 1:
@@ -84,6 +88,7 @@ class Stream:
             dp.settings_token = self._processor_token()
             return dp
         dp = DataProcessor(sfreq=self.sfreq, settings=self.settings, channels=self.channels,
+                           coord_names=self.coord_names, coord_list=self.coord_list, path_grids=self.path_grids,
                            line_noise=self.line_noise, verbose=self.verbose,
                            device=self.devices[0] if self.devices else self.device,
                            window=window, lib=self._lib,
@@ -264,7 +269,9 @@ class Stream:
 
         # stream/data_processor.py:313-337: original_fs = the rate passed in, final_fs = sfreq // 1
         sidecar = {"original_fs": self.sfreq, "final_fs": self.data_processor.sfreq_raw,
-                   "sfreq": float(self.settings.sampling_rate_features_hz), "sess_right": self.sess_right}
+                   "sfreq": float(self.settings.sampling_rate_features_hz)}
+        sidecar.update(self.data_processor.projection_sidecar())   # (coords, grids, matrices of a grid projection)
+        sidecar["sess_right"] = self.sess_right
         fw.save_sidecar(sidecar, out_dir, experiment_name)
         # the serialised settings / channel table of the previous run are re-used while both are unchanged
         # (process-wide: a fresh Stream with the settings of the one before -- the reference builds one per run -- does not
