@@ -499,6 +499,7 @@ extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, s
 //   M = 4096 (windows + filter half-length in (2048, 4096])            nmx_kern_bank_w64x2
 //   channel pairs, M = 1536 / 1024 (every filter that fits)            nmx_kern_bank_w64c / w64d
 //   channel pairs, M = 2048 (longer filters; the notch)                nmx_kern_bank_w64e<0 / 1>
+//   ... the notch with those filters behind it in one item             nmx_kern_notch_bank_w64e (be_launch_notch_bank_fused)
 //   M = 2048, >= 4096 items: persistent 8-wave workgroups, pipelined   nmx_kern_bank_w64pp
 //   notch (odd-reflected window), >= 1024 items: four items / workgroup nmx_kern_notch_w64q
 //   a window or two (nmx_process_window): one wave per workgroup        nmx_kern_bank_w64 / nmx_kern_notch_w64
@@ -516,6 +517,17 @@ static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds,
 }
 extern "C" int nmx_w64_takes_dc_rd64(const NmxBankW64Args*, int);
 static bool be_bank_w64_takes_dc(const NmxBankW64Args& A, int n_items) { return nmx_w64_takes_dc_rd64(&A, n_items) != 0; }
+// the notch N with the PAD = 0 filters F behind it in one kernel (nmx_kern_notch_bank_w64e): waves per workgroup, 0 = no
+extern "C" int nmx_w64e_fused_waves_rd64(const NmxBankW64Args*, const NmxBankW64Args*, int);
+extern "C" int nmx_w64e_launch_fused_rd64(const NmxBankW64Args*, const NmxBankW64Args*, int, int, int, hipStream_t);
+static int be_notch_bank_fused_waves(const NmxBankW64Args& F, const NmxBankW64Args& N, bool g_lds) {
+  return nmx_w64e_fused_waves_rd64(&F, &N, g_lds ? 1 : 0);
+}
+static void be_launch_notch_bank_fused(const NmxBankW64Args& F, const NmxBankW64Args& N, bool g_lds, int n_items, int n_cu,
+                                       be_stream_t s) {
+  if (!nmx_w64e_launch_fused_rd64(&F, &N, g_lds ? 1 : 0, n_items, n_cu, s))
+    g_be_rc = nmx_fail(NMX_E_INVALID, "fused notch + filter launch: the plan chose it for a shape it does not take");
+}
 extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s);
 static void be_launch_sharp_dense(const NmxSharpArgs& A, int n_items, be_stream_t s) {
   be_init_once();

@@ -67,6 +67,7 @@ struct FirLaunch {
   const float* twc = nullptr;
   int pair_m = 0;
   int stage = 3;       // timer / kernel-name stage it reports under (6: the bank's second launch)
+  bool fused = false;  // runs inside the notch's kernel (choose_notch_bank_fuse): the stage's own launches skip it
 };
 struct FirStage {
   NmxBankArgs a{};     // argument template (per-call fields are patched in by the caller)
@@ -113,6 +114,8 @@ struct Plan {
   bool have_bank = false;
   FirStage notch;
   bool have_notch = false;
+  int notch_bank_fuse = 0;            // the bank's second launch runs inside the notch kernel (NMX_NOTCH_SW_FUSE; 2: the notch's
+                                      // spectrum in LDS as well, one exchange tile fewer -- kept for measurement)
   std::vector<FirStage> pre;          // preprocessing_filter stages (one filter each)
   const float* w64e_tw = nullptr;     // twiddles of the M = 2048 channel-pair kernel (nmx_k_bank_w64e.h): notch and bank
   NmxHilbertArgs hil{};

@@ -173,6 +173,9 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
     g_nmx_err = keep;
     return rc;
   }
+#ifndef NMX_HOST_EMU
+  choose_notch_bank_fuse(*P);   // (behind every stage's own choice: it reads the notch's, the bank's and what sits between them)
+#endif
   if ((P->d.features & NMX_F_BANDPOWER) && !P->have_bank) {
     nmx_plan_destroy((nmx_plan*)P);
     return nmx_fail(NMX_E_INVALID, "bandpass_filter enabled without filters");

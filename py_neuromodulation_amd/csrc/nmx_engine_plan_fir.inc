@@ -185,15 +185,17 @@ static bool fir_stage_takes_dc(const FirStage& S, int n_items) {
   NmxBankW64Args W = S.w;
   W.b = S.a;
   for (const FirLaunch& L : S.launches)
-    if (!be_bank_w64_takes_dc(fir_launch_args(W, L), n_items)) return false;
+    if (!L.fused && !be_bank_w64_takes_dc(fir_launch_args(W, L), n_items)) return false;   // (a fused launch takes it: its condition)
   return true;
 }
 
 // Launches FIR stage S over n_items (window, channel) items; A = S.a with the per-call fields patched in (A.yb_out: the
 // band series for the stand-alone Hilbert kernel).  The bank's filters may take two launches: the channel-pair kernel over
 // those it can take, the M = 2048 kernel over the others (stage 6: with the default settings the two 1651-tap sharp-wave
-// filters, whose "same" convolution needs M >= 1825).  `timed`: each launch's stage timer runs around it.
-static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, int n_items, be_stream_t s, bool timed = false) {
+// filters, whose "same" convolution needs M >= 1825).  `timed`: each launch's stage timer runs around it.  A launch that
+// the plan moved into the notch kernel (FirLaunch::fused) is skipped unless `with_fused` (nmx_filter_window: no notch).
+static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, int n_items, be_stream_t s, bool timed = false,
+                             bool with_fused = false) {
   const int first = S.launches[0].stage;
   int cur = first;
   if (timed) be_timer_start(P.timers[cur], s);
@@ -205,6 +207,7 @@ static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, i
     W.yb_out = A.yb_out;   // (the one-wave kernels take the band series through their own field)
     W.b.yb_out = nullptr;
     for (const FirLaunch& L : S.launches) {
+      if (L.fused && !with_fused) continue;
       if (L.stage != cur) {
         if (timed) { be_timer_stop(P.timers[cur], s); be_timer_start(P.timers[L.stage], s); }
         be_stage(cur = L.stage);
@@ -215,6 +218,45 @@ static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, i
   }
   if (timed) be_timer_stop(P.timers[cur], s);
 }
+
+#ifndef NMX_HOST_EMU
+// The notch hand-off that is a register move (nmx_k_bank_w64e.h, FUSE).  The default notch and the bank's second launch
+// (stage 6: the 1651-tap sharp-wave pre-filters at the default settings) are two instantiations of one item -- same M,
+// tile, twiddles, workgroup shape, one wave per (window, channel pair) -- and the window the notch stores sits in the
+// registers the filters load it into.  The plan moves that launch into the notch kernel when
+//   * the notch is the pair kernel of the compile-time shape and the launch is the M = 2048 PAD = 0 pair kernel taking the
+//     carried offset on load (be_notch_bank_fused_waves), none of its filters a burst band (their series tensor and the
+//     Hilbert kernel belong to the bank stage);
+//   * nothing sits between notch and bank (no resampler, no raw normaliser).
+// y_notch is still written: the M = 1536 launch, the time / oscillatory kernel, coherence and the tap read it.
+// NMX_NOTCH_SW_FUSE: 1 (default) the notch's spectrum from global memory -- the tiles of the two launches, seven waves per
+// workgroup with two filters; 2 its spectrum in LDS, one tile fewer (for measurement); 0 two launches.
+void choose_notch_bank_fuse(Plan& P) {
+  const int want = env_int("NMX_NOTCH_SW_FUSE", 1);
+  if (!want || !P.have_notch || !P.have_bank || P.have_resample || P.have_rawnorm) return;
+  if (!P.notch.w64 || !P.bank.w64 || P.notch.launches.size() != 1 || P.bank.launches.size() != 2) return;
+  FirLaunch& L = P.bank.launches[1];
+  if (L.stage != 6 || L.pair_m != 2048 || !L.hc) return;
+  for (int i = 0; i < P.bank.a.n_filters; ++i)
+    if (((L.mask >> i) & 1u) && P.bank.a.f[i].burst_index >= 0) return;
+  NmxBankW64Args N = P.notch.w, F = P.bank.w;
+  N.b = P.notch.a;
+  F.b = P.bank.a;
+  if (!be_notch_bank_fused_waves(fir_launch_args(F, L), fir_launch_args(N, P.notch.launches[0]), want == 2)) return;
+  L.fused = true;
+  P.notch_bank_fuse = want == 2 ? 2 : 1;
+}
+// the fused launch: An / Ab = the notch's and the bank's arguments with the per-call fields patched in
+static void launch_notch_bank_fused(Plan& P, const NmxBankArgs& An, const NmxBankArgs& Ab, int n_items, be_stream_t s) {
+  NmxBankW64Args N = P.notch.w, F = P.bank.w;
+  N.b = An;
+  F.b = Ab;
+  F.yb_out = nullptr;
+  F.b.yb_out = nullptr;
+  be_launch_notch_bank_fused(fir_launch_args(F, P.bank.launches[1]), fir_launch_args(N, P.notch.launches[0]),
+                             P.notch_bank_fuse == 2, n_items, P.n_cu, s);
+}
+#endif
 
 int build_hilbert(Plan& P) {
   const nmx_plan_desc& d = P.d;

@@ -4,9 +4,10 @@
 // The pre-processing behind a re-reference / offset shift, of a chunk (nw hops) or of one window (nw = 1, win_stride = 0):
 // preprocessing_filter stages -> notch -> resampler (after the notch like the reference, data_preprocessor.py:9-15,68-71)
 // -> raw normaliser (the last pre-processor; its input already nan_to_num'ed).  src / strides / starts / clean follow the
-// output of each stage that runs.
+// output of each stage that runs.  `fuse_bank` (run_chunk, a plan with notch_bank_fuse): the bank's arguments of this chunk --
+// its second launch runs inside the notch kernel (choose_notch_bank_fuse).
 static int run_prep_stages(Plan& P, const float*& src, long long& ch_stride, long long& win_stride,
-                           const long long*& starts, int nw, int& clean, be_stream_t s) {
+                           const long long*& starts, int nw, int& clean, be_stream_t s, const NmxBankArgs* fuse_bank = nullptr) {
   const int C = P.d.n_channels, W = P.d.window, Wi = P.w_in;
   int rc;
   auto take = [&](const void* y, int w) {   // the next stage reads y, [nw][C][w]
@@ -27,6 +28,10 @@ static int run_prep_stages(Plan& P, const float*& src, long long& ch_stride, lon
     NmxBankArgs A = P.notch.a;
     A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
     A.out = nullptr; A.y_out = (float*)P.y_notch.p;
+#ifndef NMX_HOST_EMU
+    if (fuse_bank) launch_notch_bank_fused(P, A, *fuse_bank, nw * C, s);
+    else
+#endif
     launch_fir_stage(P, P.notch, A, nw * C, s);
     take(P.y_notch.p, Wi);
   }
@@ -114,7 +119,21 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       if ((long long)(h_starts[i] - h_starts[i - 1]) != hop) hop = -1;
     if (hop >= 0) { src += h_starts[0]; win_stride = hop; starts = nullptr; }
   }
-  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, nw, clean, s))) return rc;
+  // ---- the carried offset (nmx_engine_dc.inc): consumers take it on load; one that cannot reads a copy with it added back
+  const float* dcf = P.dc_active ? P.d_dc_pref : nullptr;
+  // the bank's second launch inside the notch kernel (choose_notch_bank_fuse): its outputs exist before the notch runs
+  // (the wait on ev_join_d[par] above has freed this parity's sharp-wave series)
+  NmxBankArgs fuse_a{};
+  if (P.notch_bank_fuse) {
+    fuse_a = P.bank.a;
+    fuse_a.out = d_out;
+    fuse_a.dcf = dcf;
+    if (P.have_sharp) {
+      if ((rc = ensure(B_swy, (size_t)nw * C * d.n_sw_filters * W * sizeof(float)))) return rc;
+      fuse_a.sw_out = (float*)B_swy.p;
+    }
+  }
+  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, nw, clean, s, P.notch_bank_fuse ? &fuse_a : nullptr))) return rc;
   if (!P.pre.empty() || P.have_notch || P.have_resample || P.have_rawnorm) raw_live = false;
   if (d_pre) {   // user-registered host features read what the device features read
     NmxTapArgs T{};
@@ -127,8 +146,6 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   // for the chunk's threshold walk and normaliser -- process_batch_impl)
   P.raw_consumed = !raw_live;
   if (P.raw_consumed && P.in_free_slot >= 0) be_event_record(P.ev_in_free[P.in_free_slot], s);
-  // ---- the carried offset (nmx_engine_dc.inc): consumers take it on load; one that cannot reads a copy with it added back
-  const float* dcf = P.dc_active ? P.d_dc_pref : nullptr;
   const float* src_dc = nullptr;
   auto with_dc = [&]() -> int {   // [nw][C][W], the true windows
     if (src_dc) return 0;
@@ -672,7 +689,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
   }
-  launch_fir_stage(P, P.bank, A, C, s);
+  launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
   be_d2h_async(yf.data(), P.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];

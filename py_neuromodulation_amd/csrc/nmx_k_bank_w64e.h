@@ -6,6 +6,13 @@
 //            (features/sharpwaves.py:127-154,242-251).
 //   PAD = 1  the notch: MNE's _overlap_add_filter(phase="zero", pad="reflect_limited") (filter/notch_filter.py:78-93):
 //            odd reflection by (L - 1) / 2 samples (at most min(L, W) - 1 of them), linear FIR, crop to the window.
+//   FUSE     (PAD = 1 of the compile-time shape, nmx_kern_notch_bank_w64e) the notch, and then the PAD = 0 filters on the
+//            window it has just stored: register j of lane l holds sample l + 64 j on the way out of the notch and on the
+//            way into the filters, so the hand-off is a register move -- the window still goes to HBM for its other
+//            readers, but the filters' launch, its 4 W bytes per channel of compulsory read and its per-item set-up are
+//            gone.  What is handed over is the fp32 value that was stored (samples beyond W and a missing partner zeroed,
+//            as the buffer range checks do; then the carried offset; then the pair rescale, recomputed): the filters'
+//            results are those of the two launches bit for bit.  Both notch forms hand over (NmxBankArgs::residual 1 / 0).
 //
 // Why a pair kernel.  Both used to run one channel per wave on the half-length real-FFT trick (1024-point complex
 // transform, conjugate partner from the mirrored lane, two tables, split / unsplit algebra: nmx_k_bank_w64.h).  Taps are
@@ -235,11 +242,47 @@ NMX_DEV void nmx_w64e_reflect_fixed(nmx_c2* v, const nmx_rsrc r1, const nmx_rsrc
   ((v[J] = nmx_w64e_reflect_reg<J, WC, HC, CLEAN>(r1, r2, l, x0_2, xl_2)), ...);
 }
 
+// The second channel of a pair at the first one's scale: an exact power of two (nmx_k_bank_w64c.h).  Returns what takes the
+// results back (a channel that is identically zero comes out EXACTLY zero, as it does alone).
+template <int NJ>
+NMX_DEV nmx_c2 nmx_w64e_pair_scale(nmx_c2* v) {
+  float m1 = 0.f, m2 = 0.f;
+  NMX_UNROLL
+  for (int j = 0; j < NJ; ++j) { m1 = fmaxf(m1, fabsf(v[j].x)); m2 = fmaxf(m2, fabsf(v[j].y)); }
+  m1 = nmx_wave_reduce(m1, 0.f, [](float a_, float b_) { return fmaxf(a_, b_); });
+  m2 = nmx_wave_reduce(m2, 0.f, [](float a_, float b_) { return fmaxf(a_, b_); });
+  int e = 0;
+  if (m1 > 0.f && m2 > 0.f) {
+    e = __builtin_amdgcn_frexp_expf(m1) - __builtin_amdgcn_frexp_expf(m2);
+    e = e < -60 ? -60 : (e > 60 ? 60 : e);
+  }
+  NMX_UNROLL
+  for (int j = 0; j < NJ; ++j) v[j].y = __builtin_amdgcn_ldexpf(v[j].y, e);
+  return nmx_mk2(m1 > 0.f ? 1.f : 0.f, m2 > 0.f ? __builtin_amdgcn_ldexpf(1.f, -e) : 0.f);
+}
+
+// The notch half of a fused item (FUSE below): what the notch launch carries per call, next to the bank's arguments
+struct NmxW64eNotchHalf {
+  const float* x;
+  long long ch_stride, win_stride;
+  const long long* starts;
+  float* y_out;        // [n_windows][C][W]
+  const float* hg;     // the notch's spectrum in register order, [16][64] pairs (the `hc` of its own launch)
+  int clean_on_load, residual;
+};
+struct NmxW64eFusedArgs {   // (ONE kernel argument: the item loop re-reads both halves through the same laundered pointer)
+  NmxBankW64Args f;    // the PAD = 0 filters
+  NmxW64eNotchHalf n;
+};
+
 // one item: window w, channels c and c + 1 (c even; c + 1 == n_channels: the second half is zeros)
 // WC, HC != 0: the notch of that shape (nmx_w64e_reflect_fixed); 0: the lane's table `rt`
-template <int PAD, int WC = 0, int HC = 0>
+// FUSE != 0 (PAD = 1 with a compile-time shape): AA describes the PAD = 0 FILTERS that follow the notch (htab: their
+// tables), N the notch; 1: the notch's spectrum comes from global memory (N->hg), 2: from LDS behind the filters' tables
+template <int PAD, int WC = 0, int HC = 0, int FUSE = 0>
 NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const NmxW64cLane& Ln, const float* htab,
-                                const unsigned* rt) {
+                                const unsigned* rt, const NmxW64eNotchHalf* N = nullptr) {
+  static_assert(!FUSE || (PAD && WC), "the fused item is the notch of a compile-time shape");
   w = nmx_uniform_i(w);
   c = nmx_uniform_i(c);
   const NmxBankArgs& A = AA.b;
@@ -247,11 +290,19 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
   const int l = (int)(threadIdx.x & 63);
   const bool two = c + 1 < A.n_channels;
   float* out_row = A.out ? A.out + (long long)w * A.n_outputs : nullptr;
-  const float* src = A.x + (long long)c * A.ch_stride + (long long)w * A.win_stride +
-                     (A.starts ? nmx_uniform_ll(A.starts[w]) : 0ll);
+  const float* x = A.x;
+  long long ch_stride = A.ch_stride, win_stride = A.win_stride;
+  const long long* starts = A.starts;
+  int clean_on_load = A.clean_on_load, residual = A.residual;
+  float* y_out = A.y_out;
+  if constexpr (FUSE != 0) {
+    x = N->x; ch_stride = N->ch_stride; win_stride = N->win_stride; starts = N->starts;
+    clean_on_load = N->clean_on_load; residual = N->residual; y_out = N->y_out;
+  }
+  const float* src = x + (long long)c * ch_stride + (long long)w * win_stride + (starts ? nmx_uniform_ll(starts[w]) : 0ll);
   nmx_c2 v[32];
   const nmx_rsrc r1 = nmx_make_rsrc(src, 4 * W);
-  const nmx_rsrc r2 = nmx_make_rsrc(src + A.ch_stride, two ? 4 * W : 0);
+  const nmx_rsrc r2 = nmx_make_rsrc(src + ch_stride, two ? 4 * W : 0);
   constexpr int NJ = PAD ? 32 : 16;
 
   if (PAD && WC) {
@@ -259,7 +310,7 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
                         __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r2, 0, 0, 0)));
     nmx_c2 xl = nmx_mk2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r1, 4 * (WC - 1), 0, 0)),
                         __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r2, 4 * (WC - 1), 0, 0)));
-    if (A.clean_on_load) {
+    if (clean_on_load) {
       x0 = nmx_mk2(nmx_clean_bl(x0.x), nmx_clean_bl(x0.y));
       xl = nmx_mk2(nmx_clean_bl(xl.x), nmx_clean_bl(xl.y));
       nmx_w64e_reflect_fixed<WC, HC, true>(v, r1, r2, l, x0 + x0, xl + xl, NMX_W64E_SEQ32);
@@ -324,21 +375,15 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
     for (int j = 0; j < 16; ++j) keep[j] = v[j];
   }
   // ---- the second channel at the first one's scale: an exact power of two (nmx_k_bank_w64c.h) ------------------------
-  float m1 = 0.f, m2 = 0.f;
-  NMX_UNROLL
-  for (int j = 0; j < NJ; ++j) { m1 = fmaxf(m1, fabsf(v[j].x)); m2 = fmaxf(m2, fabsf(v[j].y)); }
-  m1 = nmx_wave_reduce(m1, 0.f, [](float a_, float b_) { return fmaxf(a_, b_); });
-  m2 = nmx_wave_reduce(m2, 0.f, [](float a_, float b_) { return fmaxf(a_, b_); });
-  int e = 0;
-  if (m1 > 0.f && m2 > 0.f) {
-    e = __builtin_amdgcn_frexp_expf(m1) - __builtin_amdgcn_frexp_expf(m2);
-    e = e < -60 ? -60 : (e > 60 ? 60 : e);
-  }
-  NMX_UNROLL
-  for (int j = 0; j < NJ; ++j) v[j].y = __builtin_amdgcn_ldexpf(v[j].y, e);
-  // (a channel that is identically zero comes out EXACTLY zero, as it does alone)
-  const nmx_c2 unscale = nmx_mk2(m1 > 0.f ? 1.f : 0.f, m2 > 0.f ? __builtin_amdgcn_ldexpf(1.f, -e) : 0.f);
+  nmx_c2 unscale = nmx_w64e_pair_scale<NJ>(v);
 
+  // (FUSE = 1: the notch's spectrum, 8 KiB that every item reads -- L1 / L2 resident -- is in flight during the transform)
+  nmx_c2 hg[FUSE == 1 ? 16 : 1];
+  if constexpr (FUSE == 1) {
+    const nmx_rsrc rg = nmx_make_rsrc(N->hg, 4 * NMX_W64E_H_FLOATS);
+    NMX_UNROLL
+    for (int i = 0; i < 16; ++i) hg[i] = __builtin_bit_cast(nmx_c2, __builtin_amdgcn_raw_buffer_load_b64(rg, 8 * l + 512 * i, 0, 0));
+  }
   nmx_w64e_forward<PAD>(v, Ln);
   const unsigned h_addr = nmx_lds_addr(htab) + 8u * (unsigned)l;
 
@@ -346,8 +391,13 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
     // ---- ONE filter: scale the spectrum in place, transform back, store the window ------------------------------------
     {
       nmx_c2 h[16];
-      nmx_w64e_rdt16<0>(h, h_addr, NMX_W64E_SEQ16);
-      NMX_SCHED_FENCE();
+      if constexpr (FUSE == 1) {
+        NMX_UNROLL
+        for (int i = 0; i < 16; ++i) h[i] = hg[i];
+      } else {
+        nmx_w64e_rdt16<0>(h, h_addr + (FUSE ? (unsigned)A.n_filters * (NMX_W64E_H_FLOATS * 4u) : 0u), NMX_W64E_SEQ16);
+        NMX_SCHED_FENCE();
+      }
       NMX_UNROLL
       for (int i = 0; i < 16; ++i) {
         v[2 * i] = nmx_pk_mul_lo(v[2 * i], h[i]);
@@ -355,13 +405,13 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
       }
     }
     nmx_w64e_inverse(v, Ln);
-    float* d = A.y_out + ((long long)w * A.n_channels + c) * W;
+    float* d = y_out + ((long long)w * A.n_channels + c) * W;
     const nmx_rsrc s1 = nmx_make_rsrc(d, 4 * W);
     const nmx_rsrc s2 = nmx_make_rsrc(d + W, two ? 4 * W : 0);
     NMX_UNROLL
     for (int j = 0; j < 16; ++j) {
       nmx_c2 y = v[j] * unscale;
-      if (A.residual) {
+      if (residual) {
         if constexpr (KEEP) {
           y = keep[j] - y;   // (lanes beyond the window's end hold flank samples: their stores are out of range)
         } else {
@@ -373,8 +423,30 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
       }
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y.x), s1, 4 * l + 256 * j, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y.y), s2, 4 * l + 256 * j, 0, 0);
+      if constexpr (FUSE != 0) v[j] = y;
     }
-    return;
+    if constexpr (FUSE == 0) {
+      return;
+    } else {
+      // ---- the window just stored IS the loaded window of the PAD = 0 path below (the fp32 values the second launch
+      // would read back): zero beyond its end and for a missing partner (there: the buffer range checks), then the
+      // carried offset on the samples that exist -- the filters' half only, y_notch stays in the split domain
+      NMX_UNROLL
+      for (int j = 0; j < 16; ++j) {
+        if (!two) v[j].y = 0.f;
+        if (64 * j + 63 >= WC && l + 64 * j >= WC) v[j] = nmx_mk2(0.f, 0.f);
+      }
+      if (A.dcf) {
+        const nmx_c2 dd = nmx_mk2(A.dcf[c], two ? A.dcf[c + 1] : 0.f);
+        NMX_UNROLL
+        for (int j = 0; j < 16; ++j) {
+          if (64 * j + 63 < WC) v[j] += dd;
+          else if (l + 64 * j < WC) v[j] += dd;
+        }
+      }
+      unscale = nmx_w64e_pair_scale<16>(v);
+      nmx_w64e_forward<0>(v, Ln);
+    }
   }
 
   nmx_c2 z[32];

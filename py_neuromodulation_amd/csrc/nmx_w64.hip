@@ -294,6 +294,87 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_N
   }
 }
 
+// The notch with the PAD = 0 filters behind it in ONE item (nmx_k_bank_w64e.h, FUSE): the window the notch stores is the
+// window those filters load, in the same registers.  LDS = the filters' spectra, (FUSE = 2: the notch's,) the pass-A
+// twiddles, one exchange tile per wave; FUSE = 1 reads the notch's spectrum from global memory, which leaves the seven
+// tiles of the two launches it replaces.
+template <int WC, int HC, int FUSE>
+__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)(const NmxW64eFusedArgs A0, int n_windows,
+                                                                                         int n_pairs, int chunk) {
+  typedef const NmxW64eFusedArgs __attribute__((address_space(4)))* nmx_karg_p;
+  nmx_karg_p Ap = (nmx_karg_p)__builtin_amdgcn_kernarg_segment_ptr();
+  float* tab = nmx_smem_w64;
+  const int hff = ((const NmxW64eFusedArgs*)Ap)->f.b.n_filters * NMX_W64E_H_FLOATS;
+  const int hf = hff + (FUSE == 2 ? NMX_W64E_H_FLOATS : 0);
+  NmxW64cLane Ln;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = blockDim.x >> 6;
+  {
+    const NmxW64eFusedArgs& A = *(const NmxW64eFusedArgs*)Ap;
+    for (int i = threadIdx.x; i < hff; i += blockDim.x) tab[i] = A.f.hc[i];
+    if (FUSE == 2)
+      for (int i = threadIdx.x; i < NMX_W64E_H_FLOATS; i += blockDim.x) tab[hff + i] = A.n.hg[i];
+    for (int i = threadIdx.x; i < NMX_W64E_TWA_FLOATS; i += blockDim.x) tab[hf + i] = A.f.twc[i];
+    nmx_w64c_lane_setup(Ln, tab + hf + NMX_W64E_TWA_FLOATS + wave * NMX_W64E_TILE_FLOATS, tab + hf,
+                        A.f.twc + NMX_W64E_TWA_FLOATS, (int)(threadIdx.x & 63));
+  }
+  __syncthreads();
+  const int q0 = (blockIdx.x * nw + wave) * chunk;
+  const int q1 = q0 + chunk < n_pairs ? q0 + chunk : n_pairs;
+#pragma nounroll
+  for (int q = q0; q < q1; ++q) {
+    asm volatile("" : "+s"(Ap));
+    const NmxW64eFusedArgs& A = *(const NmxW64eFusedArgs*)Ap;
+    const int cp = q / n_windows;
+    nmx_bank_w64e_item<1, WC, HC, FUSE>(A.f, q - cp * n_windows, 2 * cp, Ln, tab, nullptr, &A.n);
+  }
+}
+
+// Waves per workgroup of the fused launch of notch Nn and PAD = 0 filters F (g_lds: the notch's spectrum in LDS too), or 0
+// when they do not fuse: only the compile-time notch shape, both on the M = 2048 pair kernels over the same windows, the
+// filters taking the carried offset on load.  Decided when the plan is built (nmx_engine_plan_fir.inc).
+extern "C" int NMX_CAT(nmx_w64_takes_dc_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items);
+extern "C" int NMX_CAT(nmx_w64e_fused_waves_, NMX_W64_NAME)(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds) {
+  if (!Nn->b.pad_mode || Nn->b.n_filters != 1 || Nn->b.W != 1000 || Nn->b.pad_half != 499 || Nn->b.n_edge < 499) return 0;
+  if (!Nn->hc || !Nn->twc || Nn->pair_m != 2048 || Nn->tw2) return 0;
+  if (F->b.W != Nn->b.W || F->b.n_channels != Nn->b.n_channels || F->twc != Nn->twc) return 0;
+  if (!NMX_CAT(nmx_w64_takes_dc_, NMX_W64_NAME)(F, 0) || F->pair_m != 2048) return 0;
+  const int fixed = (F->b.n_filters + (g_lds ? 1 : 0)) * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS;
+  int nw = (160 * 1024 / 4 - fixed) / NMX_W64E_TILE_FLOATS;
+  if (nw > 8) nw = 8;
+  return nw >= 4 ? nw : 0;
+}
+
+// the fused launch: F and Nn as their own launches would get them (per-call fields patched in)
+extern "C" int NMX_CAT(nmx_w64e_launch_fused_, NMX_W64_NAME)(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds,
+                                                           int n_items, int n_cu, hipStream_t s) {
+  int nw = NMX_CAT(nmx_w64e_fused_waves_, NMX_W64_NAME)(F, Nn, g_lds);
+  if (!nw) return 0;
+  static unsigned long long seen = 0;
+  if (nmx_first_on_device(seen)) {
+    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  NmxW64eFusedArgs A;
+  A.f = *F;
+  A.n.x = Nn->b.x; A.n.ch_stride = Nn->b.ch_stride; A.n.win_stride = Nn->b.win_stride; A.n.starts = Nn->b.starts;
+  A.n.y_out = Nn->b.y_out; A.n.hg = Nn->hc; A.n.clean_on_load = Nn->b.clean_on_load; A.n.residual = Nn->b.residual;
+  const int C = F->b.n_channels, n_windows = n_items / C, n_pairs = n_windows * ((C + 1) / 2);
+  const int fixed = (F->b.n_filters + (g_lds ? 1 : 0)) * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS;
+  if (n_pairs < 2048) nw = 2;   // a hop or two: spread the few items over many CUs
+  const size_t lds = (size_t)(fixed + nw * NMX_W64E_TILE_FLOATS) * 4;
+  int grid = n_cu > 0 ? n_cu : 256;
+  if (grid * nw > n_pairs) grid = (n_pairs + nw - 1) / nw;
+  const int chunk = (n_pairs + grid * nw - 1) / (grid * nw);
+  if (g_lds) {
+    hipLaunchKernelGGL((NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 2>), dim3(grid), dim3(64 * nw), lds, s, A, n_windows, n_pairs, chunk);
+    NMX_KNAME("nmx_kern_notch_bank_w64e_", "<1000, 499, 2>");
+  } else {
+    hipLaunchKernelGGL((NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 1>), dim3(grid), dim3(64 * nw), lds, s, A, n_windows, n_pairs, chunk);
+    NMX_KNAME("nmx_kern_notch_bank_w64e_", "<1000, 499, 1>");
+  }
+  return 1;
+}
+
 // Would the dispatcher of nmx_api.hip (be_launch_bank_w64) end up in a kernel that adds the carried offset on load
 // (NmxBankArgs::dcf: the channel-pair kernels of nmx_k_bank_w64c.h / nmx_k_bank_w64e.h)?  The same conditions as the
 // launchers below; anything else reads a copy of the windows with the offset added back (nmx_engine_run.inc).
