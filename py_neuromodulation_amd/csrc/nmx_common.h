@@ -48,7 +48,15 @@ static inline float2 make_float2(float x, float y) { return float2{x, y}; }
 // not drain vmcnt, i.e. it does not stall on outstanding global loads/stores (table prefetches,
 // result stores) at every phase boundary.
 #define NMX_WAVE_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#ifdef NMX_NT_FIXED
+#if defined(NMX_NT_FIXED) && defined(NMX_SYNC_GLOBAL)
+// nmx_wave_slab.hip: the wave's working lists live in device memory -- its own global stores must have landed (and be
+// visible to its other lanes) before the next phase reads them
+#define NMX_SYNC()                                                       \
+  do {                                                                   \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");               \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          \
+  } while (0)
+#elif defined(NMX_NT_FIXED)
 #define NMX_SYNC() NMX_WAVE_FENCE()
 #elif defined(NMX_BLOCK_FIXED)
 #define NMX_SYNC()                                        \

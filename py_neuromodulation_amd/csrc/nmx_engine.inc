@@ -151,6 +151,7 @@ struct Plan {
   Buf x_in, x_in2[2], x_ref, x_rs, x_rn, rn_mean, rn_scale, x_pf[2], y_notch, yb, out, starts, mask;
   Buf win_pin;        // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
   Buf env[2], swy[2], thr[2], sw_todo[2];   // read on the side streams: one set per chunk parity
+  Buf sw_slab;        // list slabs of the long-window sharp-wave kernel (one stream runs every sharp-wave launch of a plan)
   // state
   float* d_top = nullptr;
   long long* d_counts = nullptr;

@@ -16,7 +16,7 @@ int nmx_plan_destroy(nmx_plan* plan) {
   be_sync(P->stream_d);
   be_sync(P->stream_f);
   for (void* t : P->tables) be_free(t);
-  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->thr_slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sw_todo[0], &P->sw_todo[1], &P->y_notch, &P->env[0], &P->env[1], &P->swy[0], &P->swy[1], &P->yb, &P->thr[0], &P->thr[1], &P->out, &P->starts, &P->mask})
+  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->thr_slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sw_todo[0], &P->sw_todo[1], &P->sw_slab, &P->y_notch, &P->env[0], &P->env[1], &P->swy[0], &P->swy[1], &P->yb, &P->thr[0], &P->thr[1], &P->out, &P->starts, &P->mask})
     if (b->p) be_free(b->p);
   if (P->d_top) be_free(P->d_top);
   if (P->d_counts) be_free(P->d_counts);
@@ -60,7 +60,14 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   *out = nullptr;
   NMX_REQUIRE(desc->abi_version == NMX_ABI_VERSION, "nmx_plan_desc.abi_version mismatch");
   NMX_REQUIRE(desc->n_channels >= 1, "n_channels must be >= 1");
-  NMX_REQUIRE(desc->window >= 4 && desc->window <= 16384, "window must be in [4, 16384] samples");
+  // 16 384 samples for a plan in general; up to 40 000 (the partitioned FIR stage's bound) for a plan whose window-sized
+  // stages are all sized for it: the FIR stages (notch, preprocessing_filter, the sharp-wave pre-filters), re-referencing
+  // and the sharp-wave analysis (long-window mode of build_sharp)
+  NMX_REQUIRE(desc->window >= 4 && desc->window <= 40000, "window must be in [4, 40 000 samples]");
+  NMX_REQUIRE(desc->window <= 16384 ||
+                  (!(desc->features & ~(uint32_t)NMX_F_SHARPWAVE) && desc->raw_norm_method <= 0 && desc->raw_window <= 0),
+              "window must be in [4, 16384] samples (up to 40 000 samples for sharpwave_analysis alone, behind re-referencing and FIR "
+              "pre-processing)");
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");
   NMX_REQUIRE(desc->n_extra_cols >= 0 && (long long)desc->n_outputs + desc->n_extra_cols < (1ll << 30),

@@ -326,8 +326,9 @@ int build_sharp(Plan& P) {
   A.cols = cv(d.sw_cols);
   A.np_cols = cv(d.sw_numpeaks_cols);
   const int pm = d.window / 2 + 2;      // an extremum needs a lower neighbour on both sides
-  // 16-bit positions and two 15-bit counters per packed prefix sum; the LDS check below is the binding one (the
-  // series + six position lists + the value list of one item: 11 bytes per sample, ~14 500 samples in 160 KiB).
+  // 16-bit positions and two 15-bit counters per packed prefix sum.  The series + six position lists + the value list
+  // of one item are 11 bytes per sample: ~14 500 samples fit 160 KiB of LDS; longer windows take the long-window mode
+  // below, whose bound is the series alone (the partitioned FIR stage's: about 40 000 samples).
   // Windows beyond 4098 samples take the two-pass extrema walk of nmx_extrema (per-lane chunks > 64 samples).
   NMX_REQUIRE(pm <= 32767, "window too long for the sharp-wave kernel (16-bit positions)");
   A.pm = pm;
@@ -345,11 +346,6 @@ int build_sharp(Plan& P) {
   A.off_res = A.off_selp + tail;
   A.off_red = A.off_res + al4(2 * d.sw_n_combos + 2);
   A.lds_floats = A.off_red + 64;
-  NMX_REQUIRE(A.lds_floats * 4 <= 160 * 1024, "window too long for the sharp-wave kernel: one series and its extrema lists need more than 160 KiB of LDS (about 14 500 samples)");
-  int ns = 0;
-  for (int i = 0; i < d.n_filters; ++i) ns += d.filters[i].sw_index >= 0;
-  NMX_REQUIRE(ns == d.n_sw_filters, "every sharp-wave filter needs exactly one FIR");
-  P.have_sharp = true;
   // dense-first launch layout: series + two raw lists (128 entries suffice, longer ones are only
   // counted) + four 128-entry lists
   A.dz_emax = al4(d.window);
@@ -360,6 +356,34 @@ int build_sharp(Plan& P) {
   A.dz_selp = A.dz_rt + 64;
   A.dz_res = A.dz_selp + 64;
   A.dz_lds_floats = A.dz_res + al4(2 * d.sw_n_combos + 2);
+  // Long-window mode: the carve above does not fit 160 KiB.  The series (with res / red behind it) stays in LDS, the
+  // lists [off_emax, off_res) move to one slab of device memory per resident workgroup of the persistent list kernel
+  // (nmx_wave_slab.hip) -- about 7 bytes per sample and workgroup, whatever the number of hops in a chunk.  The
+  // dense-first launch keeps its compact LDS layout: the number of extrema follows the pre-filter's pass band and the
+  // window's duration, not the sampling rate, so most long windows end there.  (The emulator's be_launch_sharp gives
+  // nmx_sharp_item the whole carve in host memory.)
+  A.slab_mode = 0; A.slab_floats = 0; A.slab_blocks = 0; A.slab = nullptr;
+  A.lz_res = al4(d.window);
+  A.lz_red = A.lz_res + al4(2 * d.sw_n_combos + 2);
+  A.lz_lds_floats = A.lz_red + 64;
+  if ((size_t)A.lds_floats * 4 > 160 * 1024) {
+    // (a guard: nmx_plan_create's 40 000-sample cap and the pre-filter's partitioned FIR stage, 39 872 samples, refuse first)
+    NMX_REQUIRE((size_t)std::max(A.lz_lds_floats, A.dz_lds_floats) * 4 <= 160 * 1024,
+                "window too long for the sharp-wave kernel: the series itself must fit 160 KiB of LDS (about 40 000 samples, "
+                "the bound of the partitioned FIR stage)");
+    A.slab_mode = 1;
+    A.slab_floats = A.off_res - A.off_emax;
+#ifndef NMX_HOST_EMU
+    // one slab per resident workgroup: as many as the LDS copies of the series allow per CU, within 64 MiB of scratch
+    const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)A.lz_lds_floats * 4))));
+    const size_t cap = ((size_t)64 << 20) / ((size_t)A.slab_floats * 4);
+    A.slab_blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)P.n_cu * per_cu, cap));
+#endif
+  }
+  int ns = 0;
+  for (int i = 0; i < d.n_filters; ++i) ns += d.filters[i].sw_index >= 0;
+  NMX_REQUIRE(ns == d.n_sw_filters, "every sharp-wave filter needs exactly one FIR");
+  P.have_sharp = true;
 #ifndef NMX_HOST_EMU   // (the register-resident path exists on the device only)
   P.sharp_dense_first = A.dense_ok != 0;
 #endif

@@ -197,6 +197,14 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     if (!P.have_sharp) return 0;
     NmxSharpArgs A = P.sharp;
     A.y = (const float*)B_swy.p; A.out = d_out; A.n_windows = nw;
+    if (A.slab_blocks > 0) {   // long-window mode: the list kernel's slabs, sized by its grid (nmx_wave_slab.hip)
+      const double scale = g_ensure_scale;   // (a fixed size: not one to grow with the chunks that follow)
+      g_ensure_scale = 1.0;
+      const int rc3 = ensure(P.sw_slab, (size_t)A.slab_blocks * A.slab_floats * sizeof(float));
+      g_ensure_scale = scale;
+      if (rc3) return rc3;
+      A.slab = (float*)P.sw_slab.p;
+    }
     be_stage(5);
     if (tev) be_timer_start(P.timers[5], ss);
     if (P.sharp_dense_first) {

@@ -55,6 +55,14 @@ struct NmxSharpArgs {
   // are flagged in `todo` and redone by the generic kernel with the full layout above
   int dz_emax, dz_emin, dz_selt, dz_lf, dz_rt, dz_selp, dz_res, dz_lds_floats;
   unsigned char* todo;
+  // long-window mode (the carve above exceeds 160 KiB of LDS): the series and res / red stay in LDS (lz_*), the index,
+  // state and value lists keep their offsets relative to off_emax inside one slab of device memory per resident
+  // workgroup of the persistent list kernel -- slab + blockIdx.x * slab_floats.  (Reading the series in place from `y`
+  // instead of staging it was measured 1.3 - 3 times slower: profiles/sharpwave_long.md.)
+  int slab_mode;
+  int lz_res, lz_red, lz_lds_floats;
+  int slab_floats, slab_blocks;
+  float* slab;
 };
 
 #ifdef NMX_HOST_EMU
@@ -1060,6 +1068,28 @@ NMX_DEV void nmx_sharp_item(const NmxSharpArgs& A, int w, int c, int fi, float* 
 }
 
 #ifndef NMX_HOST_EMU
+// long-window mode: the lists of the generic code in this workgroup's slab of device memory (same relative carve as
+// nmx_sharp_layout), the series in LDS
+NMX_DEV void nmx_sharp_item_slab(const NmxSharpArgs& A, int w, int c, int fi, float* smem, float* slab) {
+  NmxSharpLds L;
+  const int o = A.off_emax;
+  L.emax = (nmx_u16*)slab;
+  L.emin = (nmx_u16*)(slab + (A.off_emin - o));
+  L.selP = (nmx_u16*)(slab + (A.off_selp - o));
+  L.selT = (nmx_u16*)(slab + (A.off_selt - o));
+  L.lf = (nmx_u16*)(slab + (A.off_lf - o));
+  L.rt = (nmx_u16*)(slab + (A.off_rt - o));
+  L.st = (unsigned char*)(slab + (A.off_st - o));
+  L.vals = slab + (A.off_vals - o);
+  L.z = smem; L.res = smem + A.lz_res; L.red = smem + A.lz_red;
+  const int W = A.W;
+  const float* src = A.y + (((long long)w * A.n_channels + c) * A.n_filters + fi) * W;
+  float* z = L.z;
+  nmx_stage_row(src, W, [=](int i, float v) { z[i] = v; });
+  NMX_SYNC();
+  nmx_sharp_body(A, L, w, c, fi, false);
+}
+
 // dense-first variant: compact LDS layout, no list fallback in this launch
 NMX_DEV void nmx_sharp_item_dense(const NmxSharpArgs& A, int w, int c, int fi, long long item, float* smem) {
   NmxSharpLds L;

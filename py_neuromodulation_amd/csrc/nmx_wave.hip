@@ -365,7 +365,16 @@ __global__ void __launch_bounds__(256) nmx_kern_sharp_dense(const NmxSharpArgs A
   nmx_sharp_item_dense(A, r / A.n_channels, r % A.n_channels, fi, (long long)item, smem);
 }
 
+// nmx_wave_slab.hip: the list kernel of the long-window mode (todo = nullptr: every item)
+extern "C" void nmx_wave_launch_sharp_slab(const NmxSharpArgs* A, int n_items, const unsigned char* todo, hipStream_t s);
+
 extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s) {
+  if (A->slab_mode) {
+    static unsigned long long seen = 0;   // (the series alone is beyond the 64 KiB a kernel gets without asking)
+    if (nmx_first_on_device(seen)) {
+      (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_dense, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    }
+  }
   const int slice = (A->dz_lds_floats + 3) & ~3;
   const int k = waves_per_wg((size_t)slice * 4, 2);
   hipLaunchKernelGGL(nmx_kern_sharp_dense, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k), (size_t)slice * 4 * k, s, *A,
@@ -394,6 +403,7 @@ __global__ void __launch_bounds__(64) nmx_kern_sharp_todo(const NmxSharpArgs A, 
 
 extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, size_t lds, const unsigned char* todo,
                                            hipStream_t s) {
+  if (A->slab_mode) { nmx_wave_launch_sharp_slab(A, n_items, todo, s); return; }
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_todo, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -427,6 +437,7 @@ extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, int n_item
 }
 
 extern "C" void nmx_wave_launch_sharp(const NmxSharpArgs* A, int n_items, size_t lds, hipStream_t s) {
+  if (A->slab_mode) { nmx_wave_launch_sharp_slab(A, n_items, nullptr, s); return; }
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_sharp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

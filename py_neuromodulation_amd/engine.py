@@ -300,7 +300,8 @@ class _Pinned:
         self._bufs = {}
 
 
-MAX_PLAN_WINDOW = 16384   # nmx_plan_create: window in [4, 16384] samples
+MAX_PLAN_WINDOW = 16384   # nmx_plan_create: window in [4, 16384] samples for a plan in general; the stand-alone filter objects cut longer
+                          # recordings into segments of this length (a sharp-wave-only plan may be built up to 40 000 samples)
 
 
 def long_segments(n_samples: int, halo: int, window: int = MAX_PLAN_WINDOW):
