@@ -140,6 +140,9 @@ struct Plan {
   bool thr_fill = true;             // fresh stream: sort-once walk of the fill phase (nmx_k_burst_fill.h) ...
   bool fill_split = true;           // ... as two launches (sort, one-wave walk)
   bool thr_list_lds = true;         // the one-wave walk may keep its top-K list in LDS while the stream is young
+  bool env_sparse = true;           // the one-wave Hilbert kernels store a row below the threshold floor as its tail only (NMX_BURST_ENV_SPARSE)
+  bool env_sparse_count = false;    // ... = 2: and every chunk's flags are read back and counted (nmx_last_kernels(4) reports them)
+  long long env_tail_rows = 0, env_rows = 0;
   bool tiny_inline = true;          // host batches of a few hops on ONE stream (nmx_engine_run.inc)
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
   long long burst_windows_seen = 0; // host mirror of the per-sequence window counter (all sequences advance together)
@@ -151,11 +154,14 @@ struct Plan {
   Buf x_in, x_in2[2], x_ref, x_rs, x_rn, rn_mean, rn_scale, x_pf[2], y_notch, yb, out, starts, mask;
   Buf win_pin;        // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
   Buf env[2], swy[2], thr[2], sw_todo[2];   // read on the side streams: one set per chunk parity
+  Buf env_full[2];    // ... and which rows of env[] are whole (NmxHilbertArgs::full), with it
   Buf sw_slab;        // list slabs of the long-window sharp-wave kernel (one stream runs every sharp-wave launch of a plan)
   // state
   float* d_top = nullptr;
   long long* d_counts = nullptr;
   size_t top_bytes = 0, counts_bytes = 0;
+  float* d_floor = nullptr;   // [C][Bb] lower bound of each sequence's future thresholds (NmxBurstThrArgs::floor): derived from the
+                              // state, never exported; -INFINITY whenever the state is new to this plan
   NmxKalmanArgs kal{};
   bool have_kalman = false;
   NmxResampleArgs rs{};

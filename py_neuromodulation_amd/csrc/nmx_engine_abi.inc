@@ -16,10 +16,11 @@ int nmx_plan_destroy(nmx_plan* plan) {
   be_sync(P->stream_d);
   be_sync(P->stream_f);
   for (void* t : P->tables) be_free(t);
-  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->thr_slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sw_todo[0], &P->sw_todo[1], &P->sw_slab, &P->y_notch, &P->env[0], &P->env[1], &P->swy[0], &P->swy[1], &P->yb, &P->thr[0], &P->thr[1], &P->out, &P->starts, &P->mask})
+  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->thr_slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sw_todo[0], &P->sw_todo[1], &P->sw_slab, &P->y_notch, &P->env[0], &P->env[1], &P->env_full[0], &P->env_full[1], &P->swy[0], &P->swy[1], &P->yb, &P->thr[0], &P->thr[1], &P->out, &P->starts, &P->mask})
     if (b->p) be_free(b->p);
   if (P->d_top) be_free(P->d_top);
   if (P->d_counts) be_free(P->d_counts);
+  if (P->d_floor) be_free(P->d_floor);
   if (P->d_R) be_free(P->d_R);
   if (P->d_dc_sub) be_free(P->d_dc_sub);
   if (P->d_dc_pref) be_free(P->d_dc_pref);
@@ -268,6 +269,7 @@ int nmx_state_reset(nmx_plan* plan) {
   if (P->have_bursts) {
     be_memset_sync(P->d_top, 0, P->top_bytes);
     be_memset_sync(P->d_counts, 0, P->counts_bytes);
+    burst_floor_reset(*P);
     P->burst_windows_seen = 0;
   }
   if (P->have_kalman) kalman_reset(*P);
@@ -329,6 +331,7 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes) {
     be_h2d_sync(P->d_top, src, P->top_bytes);
     be_h2d_sync(P->d_counts, (const char*)src + P->top_bytes, P->counts_bytes);
     memcpy(&P->burst_windows_seen, (const char*)src + P->top_bytes + sizeof(long long), sizeof(long long));   // counts[0][1]
+    burst_floor_reset(*P);   // (a bound of the history this plan had, not of the imported one: the next steady walk writes it anew)
   }
   if (P->have_kalman) be_h2d_sync(P->d_kf, (const char*)src + P->top_bytes + P->counts_bytes, P->kf_bytes);
   if (P->have_rawnorm) {

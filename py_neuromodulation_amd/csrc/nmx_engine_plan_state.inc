@@ -112,6 +112,12 @@ int build_prefilters(Plan& P) {
   return 0;
 }
 
+// no bound for any sequence: plan creation, state reset, state import (the caller has drained the plan's streams)
+void burst_floor_reset(Plan& P) {
+  const std::vector<float> f((size_t)P.d.n_channels * P.d.n_burst_bands, -INFINITY);
+  be_h2d_sync(P.d_floor, f.data(), f.size() * sizeof(float));
+}
+
 int build_bursts(Plan& P) {
   const nmx_plan_desc& d = P.d;
   if (!(d.features & NMX_F_BURSTS)) return 0;
@@ -175,9 +181,17 @@ int build_bursts(Plan& P) {
   P.counts_bytes = n_state * 2 * sizeof(long long);
   P.d_top = (float*)be_alloc(P.top_bytes);
   P.d_counts = (long long*)be_alloc(P.counts_bytes);
-  if (!P.d_top || !P.d_counts) return nmx_fail(NMX_E_NOMEM, "burst state allocation failed");
+  P.d_floor = (float*)be_alloc(n_state * sizeof(float));
+  if (!P.d_top || !P.d_counts || !P.d_floor) return nmx_fail(NMX_E_NOMEM, "burst state allocation failed");
   be_memset_sync(P.d_top, 0, P.top_bytes);
   be_memset_sync(P.d_counts, 0, P.counts_bytes);
+  burst_floor_reset(P);
+#ifdef NMX_HOST_EMU
+  P.env_sparse = false;   // (the emulator runs the generic Hilbert item, which stores every row)
+#else
+  P.env_sparse = env_int("NMX_BURST_ENV_SPARSE", 1) != 0;
+  P.env_sparse_count = env_int("NMX_BURST_ENV_SPARSE", 1) == 2;
+#endif
   P.have_bursts = true;
   return 0;
 }

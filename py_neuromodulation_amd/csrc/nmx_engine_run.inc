@@ -72,6 +72,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   if (P.overlap == 1 && P.chunk_seq >= 1)   // (this schedule runs the Hilbert kernel on the side stream too: it reads the
     be_stream_wait(s, P.ev_join[par ^ 1]);  // band series `yb`, which exists once)
   Buf& B_env = P.env[par];
+  Buf& B_full = P.env_full[par];
   Buf& B_swy = P.swy[par];
   Buf& B_thr = P.thr[par];
   Buf& B_todo = P.sw_todo[par];
@@ -235,10 +236,30 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       be_stream_wait(sb, P.ev_fork);
     }
     if (tev) be_timer_start(P.timers[4], sb);
+    const unsigned char* env_full = nullptr;
     if (P.bank.w64 || P.bank.a.partitioned) {
       NmxHilbertArgs H = P.hil;
       H.y = (const float*)P.yb.p; H.env = (float*)B_env.p;
+      // Rows that cannot reach their threshold leave only the tail the walk reads (one-wave kernels; NMX_BURST_ENV_SPARSE).
+      // No event orders this launch behind the previous chunk's walk, which may still run on the side stream: the kernel
+      // reads whatever floor is there.  That is safe because EVERY value ever stored there -- -INFINITY, or the s[lo] some
+      // finished walk of this state left -- is a lower bound of all thresholds of the hops behind that walk, this chunk's
+      // included (NmxBurstThrArgs::floor); a 4-byte store is seen whole or not at all.  State reset / import drain the
+      // streams before they put -INFINITY back.
+      if (P.env_sparse && (P.hil_kind == NMX_HIL_W500 || P.hil_kind == NMX_HIL_W1000)) {
+        if ((rc = ensure(B_full, (size_t)nw * C * d.n_burst_bands))) return rc;
+        H.floor = P.d_floor; H.full = (unsigned char*)B_full.p;
+        H.n_seq = C * d.n_burst_bands; H.overlap = P.bthr.overlap;
+        env_full = H.full;
+      }
       be_launch_hilbert(H, P.hil_kind, (long long)nw * C * d.n_burst_bands, (size_t)H.lds_floats * 4, sb);
+      if (env_full && P.env_sparse_count) {   // NMX_BURST_ENV_SPARSE=2 (tests, measurements): read the flags back, at the price of a sync
+        std::vector<unsigned char> f((size_t)nw * C * d.n_burst_bands);
+        if ((rc = be_sync(sb))) return rc;
+        be_d2h_sync(f.data(), env_full, f.size());
+        for (unsigned char v : f) P.env_tail_rows += v == 0;
+        P.env_rows += (long long)f.size();
+      }
     }
     if (P.overlap >= 2) {
       sb = P.stream_b;
@@ -247,6 +268,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     }
     NmxBurstThrArgs T = P.bthr;
     T.env = (const float*)B_env.p; T.thr = (float*)B_thr.p; T.top = P.d_top; T.counts = P.d_counts;
+    T.floor = P.d_floor;
     T.n_windows = nw;
     // The workgroup kernel handles the hops that still FILL the history (the first 291 of a stream at the default
     // settings); from the hop at which the ring is full the one-wave walk takes over -- also in the middle of a chunk
@@ -298,6 +320,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     P.burst_windows_seen += nw;
     NmxBurstStatArgs S = P.bstat;
     S.env = (const float*)B_env.p; S.thr = (const float*)B_thr.p; S.out = d_out; S.n_windows = nw;
+    S.full = env_full;
     be_launch_burst_stat(S, nw * C * d.n_burst_bands, (size_t)S.lds_floats * 4, sb);
     if (tev) be_timer_stop(P.timers[4], sb);
     if (P.overlap) be_event_record(P.ev_join[par], sb);
@@ -833,7 +856,9 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
   if (!P || !buf || n < 1 || which < 1 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
-  const std::string& k = P->kernels[which];
+  std::string k = P->kernels[which];
+  if (which == 4 && P->env_sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
+    k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->env_tail_rows) + "/" + std::to_string(P->env_rows);
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
   memcpy(buf, k.data(), m);
   buf[m] = 0;

@@ -797,6 +797,13 @@ struct NmxHilbertArgs {
   int off_a, off_b, off_y, lds_floats;
   const float* w500_tab;   // W = 1000: tables of the wave-level kernel (nmx_k_fft500.h)
   const float* w1000_tab;  // W = 2000: tables of the 1000-point wave-level transform (nmx_k_fft500.h)
+  // Sparse rows (the one-wave kernels only; full = nullptr: every row is stored whole).  floor[seq] is a lower bound of
+  // every threshold the bursts chain will compare this row with (nmx_k_bursts.h: NmxBurstThrArgs::floor), seq = item %
+  // n_seq.  A row with no sample at or above it yields six +0.f whatever its samples are, and the threshold walk reads
+  // only its last `overlap` samples: only those are stored, and full[item] = 0 tells the statistics kernel to skip it.
+  const float* floor;      // [n_seq]
+  unsigned char* full;     // [n_items]
+  int n_seq, overlap;
 };
 
 NMX_DEV void nmx_hilbert_item(const NmxHilbertArgs& A, long long item, float* smem) {
@@ -857,6 +864,7 @@ NMX_DEV void nmx_hilbert_item(const NmxHilbertArgs& A, long long item, float* sm
 // persistent bank kernel: both call nmx_w500_hilbert with the same tables).
 // LDS per wave: a[500] + b[501] complex.
 #define NMX_W500_LDS_FLOATS (1008 + 1000)
+template <bool SPARSE>
 NMX_DEV void nmx_hilbert_w500_item(const NmxHilbertArgs& A, long long item, float* smem) {
   const int l = NMX_TID;
   nmx_c2* hb = (nmx_c2*)smem;
@@ -867,6 +875,8 @@ NMX_DEV void nmx_hilbert_w500_item(const NmxHilbertArgs& A, long long item, floa
   const nmx_rsrc rin = nmx_make_rsrc(A.y + item * 1000, 4000);
 #endif
   const nmx_rsrc rout = nmx_make_rsrc(A.env + item * 1000, 4000);
+  // (wave-uniform, issued with the row's loads: its latency is gone long before the compare at the item's tail)
+  const float fl = SPARSE ? A.floor[(int)item % A.n_seq] : 0.f;
   NmxW500TwReg T;
   T.load(A.w500_tab, l);
   nmx_c2 y[8];
@@ -877,6 +887,22 @@ NMX_DEV void nmx_hilbert_w500_item(const NmxHilbertArgs& A, long long item, floa
     if (q < 7 || l < 52) hb[l + 64 * q] = y[q];
   NMX_WAVE_FENCE();
   const nmx_c2* ht = nmx_w500_hilbert(ha, hb, T, (const nmx_c2*)A.w500_tab + NMX_W500_TW_N, l);
+  if (SPARSE) {
+    bool hit = !(fl > -INFINITY);   // no bound yet (or not a number): the whole row
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const nmx_c2 h = ht[l + 64 * q];
+      y[q] = nmx_mk2(nmx_sqrt_fast(y[q].x * y[q].x + h.x * h.x), nmx_sqrt_fast(y[q].y * y[q].y + h.y * h.y));
+      hit = hit || ((q < 7 || l < 52) && (y[q].x >= fl || y[q].y >= fl));
+    }
+    const bool row = __ballot(hit) != 0ull;
+    const int keep = 1000 - A.overlap;   // register q of lane l holds samples 2 (l + 64 q) and the next one
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (row || 2 * (l + 64 * q) + 2 > keep) __builtin_amdgcn_raw_buffer_store_b64(y[q], rout, 8 * l + 512 * q, 0, 0);
+    if (l == 0) A.full[item] = row ? 1 : 0;
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const nmx_c2 h = ht[l + 64 * q];
@@ -887,12 +913,14 @@ NMX_DEV void nmx_hilbert_w500_item(const NmxHilbertArgs& A, long long item, floa
 // The same for length-2000 series (BASELINE config 3): 1000 packed points, 1000-point wave-level transforms.
 // LDS per wave: ONE buffer of 1000 complex points (the transforms run in place) = 8 KB.
 #define NMX_W1000_LDS_FLOATS 2000
+template <bool SPARSE>
 NMX_DEV void nmx_hilbert_w1000_item(const NmxHilbertArgs& A, long long item, float* smem) {
   const int l = NMX_TID;
   nmx_c2* hb = (nmx_c2*)smem;
   nmx_c2* ha = hb;
   const nmx_rsrc rin = nmx_make_rsrc(A.y + item * 2000, 8000);
   const nmx_rsrc rout = nmx_make_rsrc(A.env + item * 2000, 8000);
+  const float fl = SPARSE ? A.floor[(int)(item % (long long)A.n_seq)] : 0.f;   // (see nmx_hilbert_w500_item)
   NmxW1000TwReg T;
   T.load(A.w1000_tab, l);
   nmx_c2 y[16];
@@ -903,6 +931,24 @@ NMX_DEV void nmx_hilbert_w1000_item(const NmxHilbertArgs& A, long long item, flo
     if (q < 15 || l < 40) hb[l + 64 * q] = y[q];
   NMX_WAVE_FENCE();
   const nmx_c2* ht = nmx_w1000_hilbert(ha, hb, T, (const nmx_c2*)A.w1000_tab + NMX_W1000_TW_N, l);
+  if (SPARSE) {   // (see nmx_hilbert_w500_item)
+    bool hit = !(fl > -INFINITY);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      if (!(q < 15 || l < 40)) continue;
+      const nmx_c2 h = ht[l + 64 * q];
+      y[q] = nmx_mk2(nmx_sqrt_fast(y[q].x * y[q].x + h.x * h.x), nmx_sqrt_fast(y[q].y * y[q].y + h.y * h.y));
+      hit = hit || y[q].x >= fl || y[q].y >= fl;
+    }
+    const bool row = __ballot(hit) != 0ull;
+    const int keep = 2000 - A.overlap;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if ((q < 15 || l < 40) && (row || 2 * (l + 64 * q) + 2 > keep))
+        __builtin_amdgcn_raw_buffer_store_b64(y[q], rout, 8 * l + 512 * q, 0, 0);
+    if (l == 0) A.full[item] = row ? 1 : 0;
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     if (!(q < 15 || l < 40)) continue;

@@ -12,10 +12,14 @@
 #include "nmx_k_bursts.h"
 
 #ifndef NMX_HOST_EMU
-template <int CH>
+template <int CH, bool SPARSE = false>
 NMX_DEV void nmx_burst_stat_item_reg(const NmxBurstStatArgs& A, int w, int c, int bi) {
   const int l = NMX_TID, W = A.W;
   const long long item = ((long long)w * A.n_channels + c) * A.n_bands + bi;
+  if (SPARSE && !__builtin_amdgcn_readfirstlane((int)A.full[item])) {   // before any load of the row: see nmx_burst_stat_zero
+    if (l == 0) nmx_burst_stat_zero(A, w, c, bi);
+    return;
+  }
   const nmx_rsrc rs = nmx_make_rsrc(A.env + item * W, 4 * W);   // reads past the window return 0
   float v[CH];
 #pragma unroll

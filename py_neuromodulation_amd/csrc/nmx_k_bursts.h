@@ -39,7 +39,21 @@ struct NmxBurstThrArgs {
   int P2;               // power of two >= max(W, overlap): bitonic sort size of the new piece
   int off_l0, off_l1, off_p, off_red, lds_floats;
   int list_in_global;   // the top-K list stays in its global (L2-resident) state array, LDS holds only the working sets
+  // [C][Bb] or nullptr.  A walk that ends with the ring full leaves here the lower of the two order statistics its threshold
+  // interpolates between, a = desc[ia] = s[lo] (b = desc[ia - 1] = s[lo + 1] >= a).  It bounds every LATER threshold of the
+  // sequence from below:
+  //   * with the ring full the rank ia is fixed and desc[] is the top of the whole history: a sample that enters can only
+  //     push the entry at a fixed rank up, so desc[ia] never decreases (until the state is reset or replaced);
+  //   * nmx_lerp_thr(a, b, frac, .) >= (float)a for b >= a and 0 <= frac < 1.  With d = fl(b - a) >= 0 in double:
+  //     frac < 0.5 returns fl(a + fl(d frac)), a sum of a and something >= 0; frac >= 0.5 returns fl(b - fl(d (1 - frac))) with
+  //     fl(d (1 - frac)) <= d / 2 <= (b - a)(1 + 2^-53) / 2, i.e. a value >= (a + b) / 2 - (b - a) 2^-54 >= a.  Rounding is
+  //     monotone and a is a float, so neither the double result nor its conversion to float falls below a.
+  // So a row of the envelope with no sample >= floor has no sample >= its threshold either (a NaN threshold compares false
+  // with every sample as well).  -INFINITY = "no bound": while the ring fills, and when the entry is not finite.
+  float* floor;
 };
+
+NMX_DEV float nmx_burst_floor_of(float v) { return (v - v == 0.f) ? v : -INFINITY; }   // finite, or no bound
 
 // bitonic sort (descending) of p[0..n2), n2 a power of two, in LDS
 NMX_DEV void nmx_bitonic_desc(float* p, int n2) {
@@ -341,6 +355,9 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
   if (NMX_TID == 0) {
     A.counts[2 * sidx] = total;
     A.counts[2 * sidx + 1] = nwin;
+    // ring full at the last hop (either regime; a steady walk ends in a flush: L is whole): its s[lo] is the floor
+    if (A.floor && A.n_windows > 0)
+      A.floor[sidx] = (total >= m_ring && ia_ring >= 0 && ia_ring < len) ? nmx_burst_floor_of(L[ia_ring]) : -INFINITY;
   }
 }
 
@@ -798,6 +815,8 @@ NMX_DEV void nmx_burst_thr_wave_item(const NmxBurstThrArgs& A, int c, int bi, fl
   if (lane == 0) {
     A.counts[2 * sidx] = total;
     A.counts[2 * sidx + 1] = nwin;
+    // (the launch ended in a flush and a re-cut: fh = 0, F[ja] = L[K - 1 - ja] = s[lo] of the last hop)
+    if (A.floor && A.n_windows > 0) A.floor[sidx] = nmx_burst_floor_of(F[fh + ja]);
   }
 }
 #endif
@@ -813,7 +832,21 @@ struct NmxBurstStatArgs {
                       //                   amplitude_max, burst_rate_per_s, in_burst}
   NmxCols cols;       // a = band, b = slot among the enabled ones
   int off_e, off_red, lds_floats;
+  const unsigned char* full;   // [n_windows][C][Bb] or nullptr (every row is whole): 0 = the Hilbert kernel found no sample of the
+                               // row at or above a lower bound of its threshold and stored only the row's tail
 };
+
+// A row without a sample >= thr: no run, no transition, nothing above -- the six statistics below are +0.f each (dmean =
+// 0.f, 0 / sfreq, 0.f, amax = 0.f, 0.f / seg_s, in_burst = 0.f), whatever the samples are (one thread)
+NMX_DEV void nmx_burst_stat_zero(const NmxBurstStatArgs& A, int w, int c, int bi) {
+  float* row = A.out + (long long)w * A.n_outputs;
+  int col = A.cols.base + c * A.cols.ch_stride + bi * A.cols.a_stride;
+  for (int s = 0; s < 6; ++s)
+    if (A.out_mask & (1u << s)) {
+      row[col] = 0.f;
+      col += A.cols.b_stride;
+    }
+}
 
 #ifdef NMX_HOST_EMU
 NMX_DEV double nmx_wave_excl_sum_d(double v, double* total) { *total = v; return 0.0; }
@@ -880,6 +913,10 @@ NMX_DEV void nmx_burst_stat_item(const NmxBurstStatArgs& A, int w, int c, int bi
   float* red = smem + A.off_red;
   const int W = A.W;
   const long long item = ((long long)w * A.n_channels + c) * A.n_bands + bi;
+  if (A.full && !A.full[item]) {   // (uniform over the item's threads; before any load of the row)
+    if (NMX_TID == 0) nmx_burst_stat_zero(A, w, c, bi);
+    return;
+  }
   const float* src = A.env + item * W;
   // padded layout (one pad dword per 16 samples): per-lane contiguous chunks would otherwise hit
   // two LDS banks per half-wave (71 % of this kernel's LDS cycles were bank conflicts)

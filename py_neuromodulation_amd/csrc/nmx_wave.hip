@@ -52,13 +52,14 @@ __global__ void __launch_bounds__(256) nmx_kern_burst_stat(const NmxBurstStatArg
 }
 
 // the envelope of one item in the registers of its wave (nmx_k_burst_stat_reg.h): W % 4 == 0, W <= 64 CH; no LDS
-template <int CH>
+// SPARSE: A.full tells which rows the Hilbert kernel stored whole; the others are six zeros without a load of the row
+template <int CH, bool SPARSE = false>
 __global__ void __launch_bounds__(256) nmx_kern_burst_stat_reg(const NmxBurstStatArgs A, int n_items) {
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int item = blockIdx.x * 4 + wave;
   if (item >= n_items) return;
   const int bi = item % A.n_bands, r = item / A.n_bands;
-  nmx_burst_stat_item_reg<CH>(A, r / A.n_channels, r % A.n_channels, bi);
+  nmx_burst_stat_item_reg<CH, SPARSE>(A, r / A.n_channels, r % A.n_channels, bi);
 }
 
 __global__ void __launch_bounds__(256) nmx_kern_sharp(const NmxSharpArgs A, int n_items, int slice) {
@@ -111,11 +112,22 @@ extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items,
 // Hilbert envelope of length-1000 series, one wave per series (wave-level 500-point transforms)
 __global__ void __launch_bounds__(256) nmx_kern_hilbert_w500(const NmxHilbertArgs A, int n_items) {
   NMX_WAVE_ITEM(item, smem, n_items, NMX_W500_LDS_FLOATS);
-  nmx_hilbert_w500_item(A, (long long)item, smem);
+  nmx_hilbert_w500_item<false>(A, (long long)item, smem);
+}
+// ... rows below the bursts chain's threshold floor leave only their tail (NmxHilbertArgs::full)
+__global__ void __launch_bounds__(256) nmx_kern_hilbert_w500_sparse(const NmxHilbertArgs A, int n_items) {
+  NMX_WAVE_ITEM(item, smem, n_items, NMX_W500_LDS_FLOATS);
+  nmx_hilbert_w500_item<true>(A, (long long)item, smem);
 }
 
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s) {
   const int k = waves_per_wg((size_t)NMX_W500_LDS_FLOATS * 4);
+  if (A->full) {
+    hipLaunchKernelGGL(nmx_kern_hilbert_w500_sparse, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k),
+                       (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
+    nmxi_note_kernel("nmx_kern_hilbert_w500_sparse");
+    return;
+  }
   hipLaunchKernelGGL(nmx_kern_hilbert_w500, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k),
                      (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
   nmxi_note_kernel("nmx_kern_hilbert_w500");
@@ -126,13 +138,26 @@ __global__ void __launch_bounds__(256) nmx_kern_hilbert_w1000(const NmxHilbertAr
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const long long item = (long long)blockIdx.x * 4 + wave;
   if (item >= n_items) return;
-  nmx_hilbert_w1000_item(A, item, nmx_smem_wave + wave * NMX_W1000_LDS_FLOATS);
+  nmx_hilbert_w1000_item<false>(A, item, nmx_smem_wave + wave * NMX_W1000_LDS_FLOATS);
+}
+__global__ void __launch_bounds__(256) nmx_kern_hilbert_w1000_sparse(const NmxHilbertArgs A, long long n_items) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long item = (long long)blockIdx.x * 4 + wave;
+  if (item >= n_items) return;
+  nmx_hilbert_w1000_item<true>(A, item, nmx_smem_wave + wave * NMX_W1000_LDS_FLOATS);
 }
 
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s) {
   static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen))
+  if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_hilbert_w1000, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)nmx_kern_hilbert_w1000_sparse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  if (A->full) {
+    hipLaunchKernelGGL(nmx_kern_hilbert_w1000_sparse, dim3((unsigned)((n_items + 3) / 4)), dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
+    nmxi_note_kernel("nmx_kern_hilbert_w1000_sparse");
+    return;
+  }
   hipLaunchKernelGGL(nmx_kern_hilbert_w1000, dim3((unsigned)((n_items + 3) / 4)), dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
   nmxi_note_kernel("nmx_kern_hilbert_w1000");
 }
@@ -421,11 +446,13 @@ extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, int n_item
   }
   if ((A->W & 3) == 0 && A->W <= 2048) {
     if (A->W <= 1024) {
-      hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_burst_stat_reg<16>");
+      if (A->full) hipLaunchKernelGGL((nmx_kern_burst_stat_reg<16, true>), dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
+      else hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
+      nmxi_note_kernel(A->full ? "nmx_kern_burst_stat_reg_sparse<16>" : "nmx_kern_burst_stat_reg<16>");
     } else {
-      hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      nmxi_note_kernel("nmx_kern_burst_stat_reg<32>");
+      if (A->full) hipLaunchKernelGGL((nmx_kern_burst_stat_reg<32, true>), dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
+      else hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
+      nmxi_note_kernel(A->full ? "nmx_kern_burst_stat_reg_sparse<32>" : "nmx_kern_burst_stat_reg<32>");
     }
     return;
   }
