@@ -42,6 +42,7 @@ extern "C" {
 #define NMX_E_NODEVICE (-2)  /* no HIP device (the engine has no CPU path) */
 #define NMX_E_HIP (-3)       /* a HIP runtime call failed */
 #define NMX_E_NOMEM (-4)
+#define NMX_E_UNSUPPORTED (-5)  /* a valid configuration this build has no kernel for (Python: NotImplementedError) */
 
 /* feature bits of nmx_plan_desc.features; order = FeatureSelector field order
  * (stream/settings.py:41-55), which is the reference's execution and column order */

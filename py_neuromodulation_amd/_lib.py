@@ -197,6 +197,8 @@ class NmxLibrary:
             text = msg.decode() if msg else ""
             if rc == -1:
                 raise ValueError(f"nmx: {text}")
+            if rc == -5:
+                raise NotImplementedError(f"nmx: {text}")
             raise NmxError(f"nmx error {rc}: {text}")
 
     def device_count(self) -> int:

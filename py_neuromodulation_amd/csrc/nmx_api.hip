@@ -460,6 +460,7 @@ extern "C" void nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_item
 extern "C" void nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
 extern "C" void nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s);
 extern "C" void nmx_wave_launch_timeosc_w1000_todo(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
+extern "C" void nmx_timeosc_long_launch(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
 // `kind`: the plan's choice (build_timeosc).  The matrix-pipe kernel leaves flagged windows to be_launch_timeosc_redo.
 static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind kind, int n_items, int nt, size_t lds, int n_cu, be_stream_t s) {
   be_init_once();
@@ -471,6 +472,7 @@ static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind kind, int 
     case NMX_TO_STFT500: nmx_wave_launch_timeosc_stft500(&A, n_items, s); return;
     case NMX_TO_W510: nmx_wave_launch_timeosc_w510(&A, n_items, s); return;
     case NMX_TO_FIXED128: nmx_timeosc_fixed_launch128(&A, n_items, lds, s); return;
+    case NMX_TO_LONG: nmx_timeosc_long_launch(&A, n_items, s); return;
     case NMX_TO_GENERIC:
       hipLaunchKernelGGL(nmx_kern_timeosc, dim3(n_items), dim3(nt), lds, s, A);
       nmxi_note_kernel("nmx_kern_timeosc");

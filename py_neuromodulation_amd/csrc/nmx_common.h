@@ -160,6 +160,12 @@ struct NmxOsc {
   // zero-padded last segment of scipy's padded=True); float64 on the host, [2][nfreq] complex
   const float2* wdc;
   int nadd;          // STFT: zeros appended to the extended signal (the tail of the last segment)
+  // long-window kernel (nmx_k_timeosc_long.h; 0 / NULL elsewhere): the segment is split into split_d interleaved
+  // subsequences x_r[m] = x[m split_d + r] of sub_m = n / split_d samples each; `fft` and `complex_full` then describe the
+  // transform of ONE subsequence (sub_m / 2 complex points, or sub_m when sub_m is odd), and
+  // X[k] = sum_r tw_n[(r k) mod n] X_r[k mod sub_m]
+  int split_d, sub_m;
+  const float2* tw_n;   // [n] exp(-2 pi i j / n), float64 on the host
 };
 
 struct NmxTimeOscArgs {
@@ -190,10 +196,18 @@ struct NmxTimeOscArgs {
   unsigned short* todo;    // matrix-pipe kernel: [ceil(n_windows / 16)][n_channels] masks, bit j = window 16 g + j of the channel holds
                            // a NaN / an infinity (the kernel does not clean on load) and is left to nmx_kern_timeosc_w1000_todo;
                            // NULL without that kernel
+  // long-window kernel (NMX_TO_LONG, nmx_k_timeosc_long.h): the window is staged in LDS for the time-domain features only,
+  // [off_a, off_spec) then holds the transform buffers of one subsequence (NmxOsc::split_d) over it
+  int long_mode;
+  int long_nb;             // floats per spectrum: max over FFT / Welch of k_hi - k_lo, rounded up to 4
+  int long_spec_slab;      // the accumulators + spectrum (3 long_nb floats) live in the workgroup's slab, not at off_spec
+  int slab_floats;         // floats per slab (0: none needed)
+  int slab_blocks;         // slabs allocated = resident workgroups of the persistent kernel
+  float* slab;             // [slab_blocks][slab_floats] device memory owned by the plan (the emulator runs on slab 0)
 };
 
 // the time / oscillatory and Hilbert kernels a plan launches, chosen when it is built (build_timeosc, build_hilbert)
-enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC };
+enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC, NMX_TO_LONG };
 enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128 };
 
 #define NMXD_F_HJORTH (1u << 0)

@@ -105,6 +105,7 @@ struct Plan {
   int overlap = 1;
   std::vector<void*> tables;               // device allocations owned by the plan
   std::map<int, NmxFft> fft_cache;
+  std::map<int, const float2*> twn_cache;   // exp(-2 pi i k / n), k < n, of the long-window kernel's combination step (NmxOsc::tw_n)
   // kernel argument templates (per-call fields are patched in process_batch)
   NmxTimeOscArgs to{};
   bool have_to = false;

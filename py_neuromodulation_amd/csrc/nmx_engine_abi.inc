@@ -62,13 +62,15 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   NMX_REQUIRE(desc->abi_version == NMX_ABI_VERSION, "nmx_plan_desc.abi_version mismatch");
   NMX_REQUIRE(desc->n_channels >= 1, "n_channels must be >= 1");
   // 16 384 samples for a plan in general; up to 40 000 (the partitioned FIR stage's bound) for a plan whose window-sized
-  // stages are all sized for it: the FIR stages (notch, preprocessing_filter, the sharp-wave pre-filters), re-referencing
-  // and the sharp-wave analysis (long-window mode of build_sharp)
+  // stages are all sized for it: the FIR stages (notch, preprocessing_filter, the sharp-wave pre-filters), re-referencing,
+  // the sharp-wave analysis (long-window mode of build_sharp) and the long-window time / oscillatory kernel (build_timeosc:
+  // Hjorth, raw, line length, FFT, Welch)
   NMX_REQUIRE(desc->window >= 4 && desc->window <= 40000, "window must be in [4, 40 000 samples]");
-  NMX_REQUIRE(desc->window <= 16384 ||
-                  (!(desc->features & ~(uint32_t)NMX_F_SHARPWAVE) && desc->raw_norm_method <= 0 && desc->raw_window <= 0),
-              "window must be in [4, 16384] samples (up to 40 000 samples for sharpwave_analysis alone, behind re-referencing and FIR "
-              "pre-processing)");
+  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH;
+  NMX_REQUIRE(desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0),
+              "window must be in [4, 16 384] samples for a plan with stft, bandpass_filter, bursts, coherence, raw_normalization or "
+              "raw_resampling; only raw_hjorth, return_raw, linelength, fft, welch and sharpwave_analysis run up to 40 000 samples, behind "
+              "re-referencing and FIR pre-processing");
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");
   NMX_REQUIRE(desc->n_extra_cols >= 0 && (long long)desc->n_outputs + desc->n_extra_cols < (1ll << 30),

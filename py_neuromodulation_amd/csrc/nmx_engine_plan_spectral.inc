@@ -75,8 +75,48 @@ NmxCols cv(const nmx_cols& c) { return NmxCols{c.base, c.ch_stride, c.a_stride, 
 int popcount4(unsigned e) { return (int)((e & 1) + ((e >> 1) & 1) + ((e >> 2) & 1) + ((e >> 3) & 1)); }
 
 // ---- oscillatory family ---------------------------------------------------------------
-// kind: 0 FFT, 1 Welch, 2 STFT
-int build_osc(Plan& P, const nmx_osc_desc& s, int kind, NmxOsc* o, int* cplx_len, int* spec_len) {
+// the bins [lo, hi) a family evaluates: the union of its bands (all bins with return_spectrum)
+void osc_bin_range(const nmx_plan_desc& d, const nmx_osc_desc& s, int* k_lo, int* k_hi) {
+  const int nfreq = s.n / 2 + 1;
+  *k_lo = 0;
+  *k_hi = nfreq;
+  if (s.return_spectrum) return;
+  int lo = nfreq, hi = 0;
+  for (int b = 0; b < d.n_bands && b < NMX_MAX_BANDS_DEV; ++b)
+    if (s.bin_hi[b] > s.bin_lo[b]) { lo = std::min(lo, s.bin_lo[b]); hi = std::max(hi, s.bin_hi[b]); }
+  if (hi > lo) { *k_lo = lo; *k_hi = hi; } else { *k_lo = 0; *k_hi = 1; }
+}
+
+std::string spaced(int n) {   // 39989 -> "39 989"
+  std::string t = std::to_string(n);
+  for (int i = (int)t.size() - 3; i > 0; i -= 3) t.insert((size_t)i, " ");
+  return t;
+}
+
+// Long-window kernel (nmx_k_timeosc_long.h): the smallest D that divides n and leaves a subsequence of M = n / D samples
+// whose transform -- M / 2 complex points, M when M is odd -- has at most 8192 points (two LDS buffers of 64 KiB, 31 KiB
+// left for the accumulators and the spectrum of a few thousand bins) and factors the FFT engine supports.  0: none.
+int long_split(int n) {
+  for (int D = 1; D <= 64; ++D) {
+    if (n % D) continue;
+    const int M = n / D;
+    if (M < 2) break;
+    int nc = (M & 1) ? M : M / 2, twos = 0, stages = 0;
+    if (nc > 8192) continue;
+    while (nc % 2 == 0) { nc /= 2; ++twos; }
+    bool ok = true;
+    for (int p = 3; nc > 1 && ok; ) {   // (build_fft: one stage per odd prime factor, radix 4 for pairs of twos)
+      if (nc % p == 0) { nc /= p; ++stages; if (p > 4096) ok = false; }
+      else if ((long long)p * p > nc) p = nc;
+      else p += 2;
+    }
+    if (ok && stages + (twos + 1) / 2 <= NMX_MAX_STAGES) return D;
+  }
+  return 0;
+}
+
+// kind: 0 FFT, 1 Welch, 2 STFT.  lng: for the long-window kernel -- `fft` / `complex_full` describe one subsequence
+int build_osc(Plan& P, const nmx_osc_desc& s, int kind, NmxOsc* o, int* cplx_len, int* spec_len, bool lng = false) {
   const nmx_plan_desc& d = P.d;
   const int W = d.window;
   std::memset(o, 0, sizeof(*o));
@@ -102,15 +142,34 @@ int build_osc(Plan& P, const nmx_osc_desc& s, int kind, NmxOsc* o, int* cplx_len
   o->cols = cv(s.cols);
   o->psd_cols = cv(s.psd_cols);
   // only the bins some band reads are evaluated (|X|, log10) and kept in LDS
-  o->k_lo = 0;
-  o->k_hi = o->nfreq;
-  if (!s.return_spectrum) {
-    int lo = o->nfreq, hi = 0;
-    for (int b = 0; b < d.n_bands; ++b)
-      if (s.bin_hi[b] > s.bin_lo[b]) { lo = std::min(lo, s.bin_lo[b]); hi = std::max(hi, s.bin_hi[b]); }
-    if (hi > lo) { o->k_lo = lo; o->k_hi = hi; } else { o->k_lo = 0; o->k_hi = 1; }
+  osc_bin_range(d, s, &o->k_lo, &o->k_hi);
+  int nc = o->complex_full ? s.n : s.n / 2;
+  if (lng) {
+    const char* fam = kind == 0 ? "fft" : "welch";
+    if (s.return_spectrum)
+      return nmx_fail(NMX_E_UNSUPPORTED, std::string(fam) + ": return_spectrum is not implemented in the long-window time/oscillatory "
+                      "kernel (windows above 16 384 samples, or segments whose transform buffers do not fit LDS next to the window)");
+    const int D = long_split(s.n);
+    NMX_REQUIRE(D > 0, std::string(fam) + ": no supported split of a " + spaced(s.n) + "-point transform (the long-window kernel "
+                "needs a divisor D <= 64 with n / D <= 16 384, or <= 8192 when odd, and prime factors <= 4096)");
+    o->split_d = D;
+    o->sub_m = s.n / D;
+    o->complex_full = o->sub_m & 1;
+    nc = o->complex_full ? o->sub_m : o->sub_m / 2;
+    auto it = P.twn_cache.find(s.n);
+    if (it == P.twn_cache.end()) {
+      std::vector<float> t(2 * (size_t)s.n);
+      for (int k = 0; k < s.n; ++k) {
+        const double a = -2.0 * kPi * (double)k / (double)s.n;
+        t[2 * k] = (float)std::cos(a);
+        t[2 * k + 1] = (float)std::sin(a);
+      }
+      const float2* p = (const float2*)upload(P, t.data(), t.size() * sizeof(float));
+      if (!p) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+      it = P.twn_cache.emplace(s.n, p).first;
+    }
+    o->tw_n = it->second;
   }
-  const int nc = o->complex_full ? s.n : s.n / 2;
   int rc = build_fft(P, nc, &o->fft);
   if (rc) return rc;
   *cplx_len = nc;
@@ -206,6 +265,7 @@ int build_w500_tab(Plan& P) {
 // the time / oscillatory kernel (be_launch_timeosc), in this order of precedence.  (The logic emulator runs the matrix-pipe
 // kernel's arithmetic or the generic item.)
 NmxTimeOscKind timeosc_kind(const Plan& P, const NmxTimeOscArgs& A) {
+  if (A.long_mode) return NMX_TO_LONG;   // windows / segments beyond the generic LDS layout (build_timeosc)
 #ifndef NMX_HOST_EMU
   // no oscillatory feature: the register-resident scan (one wave per window, no LDS)
   if (!A.fft.enabled && !A.welch.enabled && !A.stft.enabled && A.W <= 1024 && A.W >= 3 && env_int("NMX_SCAN_KERNEL", 1)) return NMX_TO_SCAN;
@@ -239,9 +299,26 @@ int build_timeosc(Plan& P) {
   A.raw_cols = cv(d.raw_cols);
   A.ll_cols = cv(d.linelength_cols);
   int maxc = 1, maxspec = 1, rc;
+  // The long-window kernel (NMX_TO_LONG) takes every plan above 16 384 samples, and below that every plan without STFT whose
+  // generic layout -- window + two transform buffers + spectrum -- does not fit LDS (FFT / Welch segments above ~13 650
+  // samples).  A plan whose generic layout fits keeps it.
+  bool lng = d.window > 16384;
+  if (!lng && !(d.features & NMX_F_STFT)) {
+    int gc = 1, gs = 1;
+    for (int kind = 0; kind < 2; ++kind) {
+      const nmx_osc_desc& s = kind ? d.welch : d.fft;
+      if (!(d.features & (kind ? NMX_F_WELCH : NMX_F_FFT)) || s.n < 2 || s.n > d.window) continue;
+      int lo, hi;
+      osc_bin_range(d, s, &lo, &hi);
+      const int step = s.n - s.n / 2;
+      gc = std::max(gc, (s.n & 1) ? s.n : s.n / 2);
+      gs = std::max(gs, (hi - lo) * (kind ? (d.window - s.n) / step + 1 : 1));
+    }
+    lng = ((long long)al4(d.window) + 2ll * al4(2 * gc) + al4(gs) + 64) * 4 > 160 * 1024;
+  }
   auto add = [&](const nmx_osc_desc& s, int kind, NmxOsc* o) -> int {
     int c = 0, sp = 0;
-    int r = build_osc(P, s, kind, o, &c, &sp);
+    int r = build_osc(P, s, kind, o, &c, &sp, lng);
     if (r) return r;
     maxc = std::max(maxc, c);
     maxspec = std::max(maxspec, sp);
@@ -252,13 +329,54 @@ int build_timeosc(Plan& P) {
   if (d.features & NMX_F_STFT) if ((rc = add(d.stft, 2, &A.stft))) return rc;
   // per-wave STFT needs room for (threads / 64) transforms of 250 points in each buffer
   A.stft_per_wave = (d.features & NMX_F_STFT) && maxc >= 250 * (P.nt_timeosc / 64);
-  A.off_x = 0;
-  A.off_a = al4(A.W);
-  A.off_b = A.off_a + al4(2 * maxc);
-  A.off_spec = A.off_b + al4(2 * maxc);
-  A.off_red = A.off_spec + al4(maxspec);
-  A.lds_floats = A.off_red + 64;
-  NMX_REQUIRE(A.lds_floats * 4 <= 160 * 1024, "time/oscillatory kernel needs more than 160 KiB LDS");
+  A.long_mode = 0; A.long_nb = 0; A.long_spec_slab = 0; A.slab_floats = 0; A.slab_blocks = 0; A.slab = nullptr;
+  if (lng) {
+    NMX_REQUIRE(!(d.features & NMX_F_STFT), "internal: STFT in a long-window plan");
+    // the window at [0, W) for the time-domain phase; then two transform buffers of one subsequence over it, the
+    // accumulators (long_nb complex) and the spectrum (long_nb floats) behind them -- or in the workgroup's slab
+    A.long_mode = 1;
+    A.long_nb = 0;
+    if (d.features & NMX_F_FFT) A.long_nb = std::max(A.long_nb, al4(A.fft.k_hi - A.fft.k_lo));
+    if (d.features & NMX_F_WELCH) A.long_nb = std::max(A.long_nb, al4(A.welch.k_hi - A.welch.k_lo));
+    const bool osc = (d.features & (NMX_F_FFT | NMX_F_WELCH)) != 0;
+    A.off_x = 0;
+    A.off_a = 0;
+    A.off_b = osc ? al4(2 * maxc) : 0;
+    A.off_spec = osc ? A.off_b + al4(2 * maxc) : 0;
+    int end = A.off_spec + 3 * A.long_nb;
+    if ((size_t)(std::max(end, al4(A.W)) + 64) * 4 > 160 * 1024) {
+      A.long_spec_slab = 1;
+      A.slab_floats = 3 * A.long_nb;
+      end = A.off_spec;
+    }
+    A.off_red = std::max(end, al4(A.W));
+    A.lds_floats = A.off_red + 64;
+    NMX_REQUIRE((size_t)A.lds_floats * 4 <= 160 * 1024, "time/oscillatory kernel needs more than 160 KiB LDS");
+    // one workgroup per CU (the layout is at least half of its LDS), NMX_TIMEOSC_LONG_BLOCKS caps the grid; the slabs --
+    // where a plan needs them: at most 3 x 20 001 floats each -- within 64 MiB of device memory
+    A.slab_blocks = 1;
+#ifndef NMX_HOST_EMU
+    const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)A.lds_floats * 4))));
+    size_t blocks = (size_t)P.n_cu * per_cu;
+    if (A.slab_floats > 0) blocks = std::min(blocks, ((size_t)64 << 20) / ((size_t)A.slab_floats * 4));
+    const int cap = env_int("NMX_TIMEOSC_LONG_BLOCKS", 0);
+    if (cap > 0) blocks = std::min(blocks, (size_t)cap);
+    A.slab_blocks = (int)std::max<size_t>(1, blocks);
+#endif
+    if (A.slab_floats > 0) {
+      A.slab = (float*)be_alloc((size_t)A.slab_blocks * A.slab_floats * sizeof(float));
+      if (!A.slab) return nmx_fail(NMX_E_NOMEM, "time/oscillatory slab allocation failed");
+      P.tables.push_back(A.slab);   // (freed with the plan's tables: nmx_plan_destroy)
+    }
+  } else {
+    A.off_x = 0;
+    A.off_a = al4(A.W);
+    A.off_b = A.off_a + al4(2 * maxc);
+    A.off_spec = A.off_b + al4(2 * maxc);
+    A.off_red = A.off_spec + al4(maxspec);
+    A.lds_floats = A.off_red + 64;
+    NMX_REQUIRE(A.lds_floats * 4 <= 160 * 1024, "time/oscillatory kernel needs more than 160 KiB LDS");
+  }
   A.w500_tab = nullptr;
   const bool stft500 = (d.features & NMX_F_STFT) && !(d.features & (NMX_F_FFT | NMX_F_WELCH)) && A.stft.n == 500 && d.window <= 2048;
   if ((d.window == 1000 || stft500) && env_int("NMX_TIMEOSC_W1000", 1)) {

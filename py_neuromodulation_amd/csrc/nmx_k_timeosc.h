@@ -136,7 +136,15 @@ NMX_DEV float2 nmx_osc_bin(const NmxOsc& O, const float2* Z, int k) {
   return nmx_rfft_bin(Z, O.fft.twr, O.fft.n, k);
 }
 
+// long-window item (nmx_k_timeosc_long.h, at the end of this file)
+NMX_DEV void nmx_time_osc_long_item(const NmxTimeOscArgs& A, int w, int c, float* smem, float* slab);
+
 NMX_DEV void nmx_time_osc_item(const NmxTimeOscArgs& A, int w, int c, float* smem) {
+#ifdef NMX_HOST_EMU
+  // the emulator's launch interface carries no kernel choice: a long-window plan's items go to their own code, on slab 0
+  // (on the device NMX_TO_LONG launches nmx_kern_timeosc_long, which hands every workgroup its slab)
+  if (A.long_mode) { nmx_time_osc_long_item(A, w, c, smem, A.slab); return; }
+#endif
   float* xs = smem + A.off_x;
   float2* bufA = (float2*)(smem + A.off_a);
   float2* bufB = (float2*)(smem + A.off_b);
@@ -396,3 +404,5 @@ NMX_DEV void nmx_time_osc_item(const NmxTimeOscArgs& A, int w, int c, float* sme
       }
   }
 }
+
+#include "nmx_k_timeosc_long.h"

@@ -301,7 +301,8 @@ class _Pinned:
 
 
 MAX_PLAN_WINDOW = 16384   # nmx_plan_create: window in [4, 16384] samples for a plan in general; the stand-alone filter objects cut longer
-                          # recordings into segments of this length (a sharp-wave-only plan may be built up to 40 000 samples)
+                          # recordings into segments of this length (a plan of raw_hjorth, return_raw, linelength, fft, welch and
+                          # sharpwave_analysis, without raw normaliser or resampling, may be built up to 40 000 samples)
 
 
 def long_segments(n_samples: int, halo: int, window: int = MAX_PLAN_WINDOW):
