@@ -9,6 +9,8 @@
 
 #include "nmx_k_bank.h"
 #include "nmx_k_bank_w64.h"
+#include "nmx_k_bank_w64d.h"   // (host predicates of the channel-pair and M = 4096 kernels: the plan chooses with them)
+#include "nmx_k_bank_w64e.h"
 #include "nmx_k_bursts.h"
 #include "nmx_k_burst_fill.h"
 #include "nmx_k_kalman.h"
@@ -488,47 +490,38 @@ static void be_launch_bank(const NmxBankArgs& A, int n_items, int nt, size_t lds
   hipLaunchKernelGGL(nmx_kern_bank, dim3(grid), dim3(nt), lds, s, A, n_items);
   nmxi_note_kernel("nmx_kern_bank");
 }
-extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args*, int, size_t, hipStream_t);
-extern "C" int nmx_w64p_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
-extern "C" int nmx_w64q_launch_notch_rd64(const NmxBankW64Args*, int, hipStream_t);
-extern "C" int nmx_w64x2_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
-extern "C" int nmx_w64c_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
-extern "C" int nmx_w64d_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
-extern "C" int nmx_w64e_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
+extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args*, int, size_t, int, hipStream_t);
+extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
+extern "C" void nmx_w64c_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
+extern "C" void nmx_w64d_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
+extern "C" void nmx_w64e_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
 extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, size_t lds, const unsigned char* todo,
                                            hipStream_t s);
-// One-wave FIR kernels (nmx_w64.hip), one kernel per shape class:
-//   M = 4096 (windows + filter half-length in (2048, 4096])            nmx_kern_bank_w64x2
-//   channel pairs, M = 1536 / 1024 (every filter that fits)            nmx_kern_bank_w64c / w64d
-//   channel pairs, M = 2048 (longer filters; the notch)                nmx_kern_bank_w64e<0 / 1>
+// One-wave FIR kernels (nmx_w64.hip).  A.kernel is the plan's choice for this launch (NmxFirKernel, set where its tables
+// were built: build_fir_stage, build_bank, build_notch); a shape a kernel does not take never gets that kind.
+//   NMX_FIR_X2      M = 4096 (windows + filter half-length in (2048, 4096])          nmx_kern_bank_w64x2
+//   NMX_FIR_PAIR_C  channel pairs, M = 1536 (every filter that fits)                  nmx_kern_bank_w64c
+//   NMX_FIR_PAIR_D  channel pairs, M = 1024 (short windows)                           nmx_kern_bank_w64d
+//   NMX_FIR_PAIR_E  channel pairs, M = 2048 (longer filters; the notch)               nmx_kern_bank_w64e<0 / 1>
 //   ... the notch with those filters behind it in one item             nmx_kern_notch_bank_w64e (be_launch_notch_bank_fused)
-//   M = 2048, >= 4096 items: persistent 8-wave workgroups, pipelined   nmx_kern_bank_w64pp
-//   notch (odd-reflected window), >= 1024 items: four items / workgroup nmx_kern_notch_w64q
-//   a window or two (nmx_process_window): one wave per workgroup        nmx_kern_bank_w64 / nmx_kern_notch_w64
+//   NMX_FIR_ONE     one channel per M = 2048 transform; by batch size (nmx_w64_launch_rd64):
+//     >= 4096 items, A.pipelined: persistent 8-wave workgroups            nmx_kern_bank_w64pp
+//     notch, >= 1024 items: four items / workgroup, or persistent         nmx_kern_notch_w64q / w64qp
+//     a window or two (nmx_process_window): one wave per workgroup        nmx_kern_bank_w64 / nmx_kern_notch_w64
 static void be_launch_bank_w64(const NmxBankW64Args& A, int n_items, size_t lds, int n_cu, be_stream_t s) {
-  if (A.tw2) {
-    if (!nmx_w64x2_launch_rd64(&A, n_items, n_cu, s)) g_be_rc = nmx_fail(NMX_E_INVALID, "M = 4096 FIR path: LDS budget");
-    return;
+  switch ((NmxFirKernel)A.kernel) {
+    case NMX_FIR_X2: nmx_w64x2_launch_rd64(&A, n_items, n_cu, s); return;
+    case NMX_FIR_PAIR_C: nmx_w64c_launch_rd64(&A, n_items, n_cu, s); return;
+    case NMX_FIR_PAIR_D: nmx_w64d_launch_rd64(&A, n_items, n_cu, s); return;
+    case NMX_FIR_PAIR_E: nmx_w64e_launch_rd64(&A, n_items, n_cu, s); return;
+    case NMX_FIR_ONE: nmx_w64_launch_rd64(&A, n_items, lds, n_cu, s); return;
   }
-  if (A.hc && A.pair_m == 2048) {
-    if (nmx_w64e_launch_rd64(&A, n_items, n_cu, s)) return;   // else: the one-channel M = 2048 kernels below
-  } else if (A.hc && (A.pair_m == 1024 ? nmx_w64d_launch_rd64(&A, n_items, n_cu, s) : nmx_w64c_launch_rd64(&A, n_items, n_cu, s))) return;
-  if (n_items >= 4096 && nmx_w64p_launch_rd64(&A, n_items, n_cu, s)) return;
-  if (A.b.pad_mode != 0 && n_items >= 1024 && nmx_w64q_launch_notch_rd64(&A, n_items, s)) return;
-  nmx_w64_launch_rd64(&A, n_items, lds, s);
 }
-extern "C" int nmx_w64_takes_dc_rd64(const NmxBankW64Args*, int);
-static bool be_bank_w64_takes_dc(const NmxBankW64Args& A, int n_items) { return nmx_w64_takes_dc_rd64(&A, n_items) != 0; }
-// the notch N with the PAD = 0 filters F behind it in one kernel (nmx_kern_notch_bank_w64e): waves per workgroup, 0 = no
-extern "C" int nmx_w64e_fused_waves_rd64(const NmxBankW64Args*, const NmxBankW64Args*, int);
-extern "C" int nmx_w64e_launch_fused_rd64(const NmxBankW64Args*, const NmxBankW64Args*, int, int, int, hipStream_t);
-static int be_notch_bank_fused_waves(const NmxBankW64Args& F, const NmxBankW64Args& N, bool g_lds) {
-  return nmx_w64e_fused_waves_rd64(&F, &N, g_lds ? 1 : 0);
-}
+// the notch N with the PAD = 0 filters F behind it in one kernel (nmx_kern_notch_bank_w64e)
+extern "C" void nmx_w64e_launch_fused_rd64(const NmxBankW64Args*, const NmxBankW64Args*, int, int, int, hipStream_t);
 static void be_launch_notch_bank_fused(const NmxBankW64Args& F, const NmxBankW64Args& N, bool g_lds, int n_items, int n_cu,
                                        be_stream_t s) {
-  if (!nmx_w64e_launch_fused_rd64(&F, &N, g_lds ? 1 : 0, n_items, n_cu, s))
-    g_be_rc = nmx_fail(NMX_E_INVALID, "fused notch + filter launch: the plan chose it for a shape it does not take");
+  nmx_w64e_launch_fused_rd64(&F, &N, g_lds ? 1 : 0, n_items, n_cu, s);
 }
 extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s);
 static void be_launch_sharp_dense(const NmxSharpArgs& A, int n_items, be_stream_t s) {

@@ -209,6 +209,10 @@ struct NmxTimeOscArgs {
 // the time / oscillatory and Hilbert kernels a plan launches, chosen when it is built (build_timeosc, build_hilbert)
 enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC, NMX_TO_LONG };
 enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128 };
+// the one-wave FIR kernels of one launch of a FIR stage (nmx_w64.hip), chosen where its tables are built (build_fir_stage,
+// build_bank, build_notch): M = 4096; channel pairs at M = 1536 / 1024 / 2048 (2048: bank filters, or the notch); one
+// channel per M = 2048 transform (nmx_kern_bank_w64 / _w64pp, nmx_kern_notch_w64 / _w64q / _w64qp: by batch size)
+enum NmxFirKernel { NMX_FIR_ONE, NMX_FIR_X2, NMX_FIR_PAIR_C, NMX_FIR_PAIR_D, NMX_FIR_PAIR_E };
 
 #define NMXD_F_HJORTH (1u << 0)
 #define NMXD_F_RAW (1u << 1)

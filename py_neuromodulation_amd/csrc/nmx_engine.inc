@@ -60,13 +60,14 @@ struct Buf {
 
 // A FIR stage -- a preprocessing_filter stage, the notch or the band-pass bank -- with its kernels decided at plan time
 // (nmx_engine_plan_fir.inc: build_fir_stage, launch_fir_stage).  One launch of its one-wave kernels: the filters of
-// `mask` with the channel-pair tables of nmx_k_bank_w64c/d/e.h (hc = nullptr: one channel per transform).
+// `mask` on kernel `kernel`; the channel-pair kinds come with the tables of nmx_k_bank_w64c/d/e.h (build_pair_tables).
 struct FirLaunch {
   unsigned mask = 0;
+  int stage = 3;       // timer / kernel-name stage it reports under (6: the bank's second launch)
+  NmxFirKernel kernel = NMX_FIR_ONE;
+  bool pipelined = false;   // NMX_FIR_ONE: large batches may run the pipelined persistent form (nmx_w64p_ok)
   const float* hc = nullptr;
   const float* twc = nullptr;
-  int pair_m = 0;
-  int stage = 3;       // timer / kernel-name stage it reports under (6: the bank's second launch)
   bool fused = false;  // runs inside the notch's kernel (choose_notch_bank_fuse): the stage's own launches skip it
 };
 struct FirStage {
@@ -74,6 +75,8 @@ struct FirStage {
   bool w64 = false;    // one-wave kernels (M = 2048 / 4096) ...
   NmxBankW64Args w{};  // ... and their template
   std::vector<FirLaunch> launches;   // (the LDS kernels: one entry, for its stage)
+  bool takes_dc = true;   // its kernels add the carried offset on load (NmxBankArgs::dcf; else run_chunk hands them a copy of
+                          // the windows with the offset added back): set by fir_stage_finish
 };
 
 struct Plan {

@@ -186,6 +186,7 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
 #ifndef NMX_HOST_EMU
   choose_notch_bank_fuse(*P);   // (behind every stage's own choice: it reads the notch's, the bank's and what sits between them)
 #endif
+  P->bank.takes_dc = fir_stage_takes_dc(P->bank);   // (behind the fuse choice: a launch inside the notch kernel takes it)
   if ((P->d.features & NMX_F_BANDPOWER) && !P->have_bank) {
     nmx_plan_destroy((nmx_plan*)P);
     return nmx_fail(NMX_E_INVALID, "bandpass_filter enabled without filters");

@@ -117,7 +117,8 @@ int build_w64x2(Plan& P, const NmxBankArgs& A, const std::vector<std::vector<flo
 // k = lane + 64 reg), two registers per 8-byte entry.  Twiddles: pass A exp(-2 pi i l ka / M) by [register 8 r + p:
 // ka = R p + r][lane] with R = 3 (M = 1024 / 1536: the M = 1024 kernel reads twl instead) or 4, then exp(-2 pi i a b / 64);
 // the M = 2048 ones are shared by every use.
-int build_pair_tables(Plan& P, int M, unsigned mask, const std::vector<std::vector<float>>& H, FirLaunch* L) {
+int build_pair_tables(Plan& P, NmxFirKernel kind, unsigned mask, const std::vector<std::vector<float>>& H, FirLaunch* L) {
+  const int M = kind == NMX_FIR_PAIR_D ? 1024 : kind == NMX_FIR_PAIR_C ? 1536 : 2048;
   std::vector<float> hc;
   int n_sel = 0;
   for (int fi = 0; fi < (int)H.size(); ++fi) {
@@ -133,7 +134,8 @@ int build_pair_tables(Plan& P, int M, unsigned mask, const std::vector<std::vect
         }
   }
   L->mask = mask;
-  L->pair_m = M;
+  L->kernel = kind;
+  L->pipelined = false;
   L->hc = (const float*)upload(P, hc.data(), hc.size() * sizeof(float));
   if (!L->hc) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
   if (M == 2048 && P.w64e_tw) {
@@ -175,17 +177,18 @@ static NmxBankW64Args fir_launch_args(const NmxBankW64Args& W, const FirLaunch& 
   B.b.n_filters = n;
   B.hc = L.hc;
   B.twc = L.twc;
-  B.pair_m = L.pair_m;
+  B.kernel = L.kernel;
+  B.pipelined = L.pipelined;
   return B;
 }
 
-// do the kernels launch_fir_stage would launch take the carried offset on load (NmxBankArgs::dcf)?
-static bool fir_stage_takes_dc(const FirStage& S, int n_items) {
+// Do the kernels launch_fir_stage launches take the carried offset on load (NmxBankArgs::dcf)?  The LDS kernels do; of the
+// one-wave kernels the channel-pair items of nmx_k_bank_w64c.h and nmx_k_bank_w64e.h (PAD = 0) -- and a launch inside the
+// notch kernel, whose condition it is.  Computed once, behind choose_notch_bank_fuse (FirStage::takes_dc).
+static bool fir_stage_takes_dc(const FirStage& S) {
   if (!S.w64) return true;
-  NmxBankW64Args W = S.w;
-  W.b = S.a;
   for (const FirLaunch& L : S.launches)
-    if (!L.fused && !be_bank_w64_takes_dc(fir_launch_args(W, L), n_items)) return false;   // (a fused launch takes it: its condition)
+    if (!L.fused && L.kernel != NMX_FIR_PAIR_C && !(L.kernel == NMX_FIR_PAIR_E && S.a.pad_mode == 0)) return false;
   return true;
 }
 
@@ -224,9 +227,9 @@ static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, i
 // (stage 6: the 1651-tap sharp-wave pre-filters at the default settings) are two instantiations of one item -- same M,
 // tile, twiddles, workgroup shape, one wave per (window, channel pair) -- and the window the notch stores sits in the
 // registers the filters load it into.  The plan moves that launch into the notch kernel when
-//   * the notch is the pair kernel of the compile-time shape and the launch is the M = 2048 PAD = 0 pair kernel taking the
-//     carried offset on load (be_notch_bank_fused_waves), none of its filters a burst band (their series tensor and the
-//     Hilbert kernel belong to the bank stage);
+//   * the notch is the M = 2048 pair kernel of the compile-time shape (nmx_w64e_notch_w1000) and the launch the M = 2048
+//     PAD = 0 pair kernel over the same windows, its spectra (NMX_NOTCH_SW_FUSE=2: and the notch's) fitting next to the
+//     tiles, none of its filters a burst band (their series tensor and the Hilbert kernel belong to the bank stage);
 //   * nothing sits between notch and bank (no resampler, no raw normaliser).
 // y_notch is still written: the M = 1536 launch, the time / oscillatory kernel, coherence and the tap read it.
 // NMX_NOTCH_SW_FUSE: 1 (default) the notch's spectrum from global memory -- the tiles of the two launches, seven waves per
@@ -236,13 +239,12 @@ void choose_notch_bank_fuse(Plan& P) {
   if (!want || !P.have_notch || !P.have_bank || P.have_resample || P.have_rawnorm) return;
   if (!P.notch.w64 || !P.bank.w64 || P.notch.launches.size() != 1 || P.bank.launches.size() != 2) return;
   FirLaunch& L = P.bank.launches[1];
-  if (L.stage != 6 || L.pair_m != 2048 || !L.hc) return;
+  if (L.stage != 6 || L.kernel != NMX_FIR_PAIR_E) return;
+  if (P.notch.launches[0].kernel != NMX_FIR_PAIR_E || !nmx_w64e_notch_w1000(P.notch.a)) return;
+  if (P.bank.a.W != P.notch.a.W || P.bank.a.n_channels != P.notch.a.n_channels) return;
+  if (!nmx_w64e_fits(__builtin_popcount(L.mask) + (want == 2 ? 1 : 0))) return;
   for (int i = 0; i < P.bank.a.n_filters; ++i)
     if (((L.mask >> i) & 1u) && P.bank.a.f[i].burst_index >= 0) return;
-  NmxBankW64Args N = P.notch.w, F = P.bank.w;
-  N.b = P.notch.a;
-  F.b = P.bank.a;
-  if (!be_notch_bank_fused_waves(fir_launch_args(F, L), fir_launch_args(N, P.notch.launches[0]), want == 2)) return;
   L.fused = true;
   P.notch_bank_fuse = want == 2 ? 2 : 1;
 }
@@ -409,6 +411,13 @@ struct FirRules {
   int stage;      // timer / kernel-name stage of its launches
 };
 
+// a launch of the filters of `mask` on the one-channel M = 2048 kernels (NMX_FIR_ONE); S.w is built
+static FirLaunch fir_one_launch(const FirStage& S, unsigned mask, int stage) {
+  FirLaunch L{mask, stage};
+  L.pipelined = nmx_w64p_ok(S.a, __builtin_popcount(mask), S.w.lds_floats);
+  return L;
+}
+
 // The decisions every FIR stage makes: kernel family, convolution length M, tap spectra and the kernels' tables.  The
 // caller has filled S->a but for those (W, pad mode, epilogue; per filter all but H, f[i].half = half-length of the live
 // taps[i]).  Hhost: the filters' real spectra at M (none in partitioned mode).
@@ -416,7 +425,8 @@ int build_fir_stage(Plan& P, const std::vector<const double*>& taps, const FirRu
                     std::vector<std::vector<float>>* Hhost = nullptr) {
   NmxBankArgs& A = S->a;
   A.n_filters = (int)taps.size();
-  S->launches = {FirLaunch{(1u << A.n_filters) - 1u, nullptr, nullptr, 0, r.stage}};
+  NMX_REQUIRE(!A.pad_mode || A.n_filters == 1, "internal: a reflected FIR stage has one filter");
+  S->launches = {FirLaunch{(1u << A.n_filters) - 1u, r.stage}};
   const int need = A.W + r.reach;
   const bool on = env_int("NMX_BANK_W64", 1) == 1;
   const bool w64 = on && need > r.w64_lo && need <= 2048;
@@ -436,8 +446,17 @@ int build_fir_stage(Plan& P, const std::vector<const double*>& taps, const FirRu
     if ((rc = filter_spectrum(P, taps[i], 2 * A.f[i].half + 1, A.M, &A.f[i].H, &H[i]))) return rc;
   if ((rc = bank_lds(A, r.hilbert))) return rc;
   S->w64 = w64 || w64x2;
-  if (w64x2) return build_w64x2(P, A, H, &S->w);
-  return w64 ? build_w64(P, A, H, &S->w) : 0;
+  if (!S->w64) return 0;
+  if ((rc = w64x2 ? build_w64x2(P, A, H, &S->w) : build_w64(P, A, H, &S->w))) return rc;
+#ifndef NMX_HOST_EMU
+  if (w64x2) {
+    NMX_REQUIRE(nmx_w64x2_lds_tables(S->w.lds_floats) >= 0, "internal: M = 4096 FIR path: LDS budget");
+    S->launches[0].kernel = NMX_FIR_X2;
+    return 0;
+  }
+#endif
+  S->launches[0] = fir_one_launch(*S, S->launches[0].mask, r.stage);
+  return 0;
 }
 
 int build_bank(Plan& P) {
@@ -492,7 +511,7 @@ int build_bank(Plan& P) {
   // the one-wave and partitioned kernels leave burst bands as series: the stand-alone Hilbert kernel follows (run_chunk)
   if (hil && (S.w64 || A.partitioned) && (rc = build_hilbert(P))) return rc;
 #ifndef NMX_HOST_EMU   // (device only, like the M = 4096 path)
-  if (S.w64 && A.M == 2048 && d.window <= 1024 && !(d.bp_features & 6u)) {
+  if (S.w64 && A.M == 2048 && nmx_w64_pair_shape_ok(A)) {
     // M = 1536, two channels per transform, for every filter with W + (L - 1) / 2 <= 1536 (the default band-pass taps:
     // 999), M = 1024 when all of them fit it; longer ones (the default sharp-wave taps: 1651) go to a second launch: the
     // M = 2048 channel-pair kernel (nmx_k_bank_w64e.h), or the one-channel M = 2048 kernels
@@ -502,24 +521,29 @@ int build_bank(Plan& P) {
     if (env_int("NMX_BANK_W64C", 1) == 1) {
       int n_sel = 0, need = 0;
       for (int i = 0; i < d.n_filters; ++i)
-        if (d.window + A.f[i].half <= 1536) { mask |= 1u << i; ++n_sel; need = std::max(need, d.window + A.f[i].half); }
-      // (a second launch repeats the forward transform: not for one filter out of many)
-      if ((n_sel >= 2 || n_sel == d.n_filters) && n_sel >= 1 && n_sel <= 11) {
+        if (d.window + A.f[i].half <= NMX_W64C_M) { mask |= 1u << i; ++n_sel; need = std::max(need, d.window + A.f[i].half); }
+      // (a second launch repeats the forward transform: not for one filter out of many.  The count the M = 1536 kernel
+      // holds in LDS bounds the M = 1024 kernel's too, whose tables are smaller)
+      if ((n_sel >= 2 || n_sel == d.n_filters) && nmx_w64c_fits(n_sel)) {
         // short windows (the taps that touch them end at 2 W - 1): the 1024-point channel-pair kernel
-        const int M = (need <= 1024 && (d.window & 1) == 0 && env_int("NMX_BANK_W64D", 1) == 1) ? 1024 : 1536;
+        const NmxFirKernel kind = (need <= 1024 && (d.window & 1) == 0 && env_int("NMX_BANK_W64D", 1) == 1) ? NMX_FIR_PAIR_D : NMX_FIR_PAIR_C;
+        NMX_REQUIRE(kind != NMX_FIR_PAIR_D || nmx_w64d_fits(n_sel, S.w.lds_floats), "internal: M = 1024 FIR path: LDS budget");
+        const int M = kind == NMX_FIR_PAIR_D ? 1024 : NMX_W64C_M;
         std::vector<std::vector<float>> HM(d.n_filters);
         for (int i = 0; i < d.n_filters; ++i)
           if (((mask >> i) & 1u) && (rc = host_spectrum(live[i], 2 * A.f[i].half + 1, M, &HM[i]))) return rc;
         S.launches.emplace_back();
-        if ((rc = build_pair_tables(P, M, mask, HM, &S.launches.back()))) return rc;
+        if ((rc = build_pair_tables(P, kind, mask, HM, &S.launches.back()))) return rc;
       } else {
         mask = 0;
       }
     }
-    FirLaunch rest{all & ~mask, nullptr, nullptr, 0, mask ? 6 : 3};
-    if (rest.mask) {
-      if (env_int("NMX_BANK_W64E", 1) == 1 && __builtin_popcount(rest.mask) <= 8 &&
-          (rc = build_pair_tables(P, 2048, rest.mask, H, &rest))) return rc;
+    if (all & ~mask) {
+      FirLaunch rest = fir_one_launch(S, all & ~mask, mask ? 6 : 3);
+      // (one spectrum's room is left free: the notch's, when the launch moves into the notch kernel with it in LDS --
+      // choose_notch_bank_fuse, NMX_NOTCH_SW_FUSE=2)
+      if (env_int("NMX_BANK_W64E", 1) == 1 && nmx_w64e_fits(__builtin_popcount(rest.mask) + 1) &&
+          (rc = build_pair_tables(P, NMX_FIR_PAIR_E, rest.mask, H, &rest))) return rc;
       S.launches.push_back(rest);
     }
   }
@@ -561,8 +585,8 @@ int build_notch(Plan& P) {
   if (rc) return rc;
 #ifndef NMX_HOST_EMU
   // two channels per 2048-point complex transform (nmx_k_bank_w64e.h, PAD = 1)
-  if (S.w64 && env_int("NMX_BANK_W64E", 1) == 1 && P.w_in <= 1024 &&
-      (rc = build_pair_tables(P, 2048, 1u, H, &S.launches[0]))) return rc;
+  if (S.w64 && env_int("NMX_BANK_W64E", 1) == 1 && nmx_w64e_notch_ok(A) &&
+      (rc = build_pair_tables(P, NMX_FIR_PAIR_E, 1u, H, &S.launches[0]))) return rc;
 #endif
   P.have_notch = true;
   return 0;

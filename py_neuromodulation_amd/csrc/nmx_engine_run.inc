@@ -171,7 +171,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
     A.out = d_out; A.clean_on_load = clean;
     A.dcf = dcf;
-    if (dcf && !fir_stage_takes_dc(P.bank, nw * C)) {
+    if (dcf && !P.bank.takes_dc) {
       if ((rc = with_dc())) return rc;
       A.x = src_dc; A.ch_stride = W; A.win_stride = (long long)C * W; A.starts = nullptr; A.clean_on_load = 0; A.dcf = nullptr;
     }

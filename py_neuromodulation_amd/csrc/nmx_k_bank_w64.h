@@ -81,8 +81,9 @@ struct NmxBankW64Args {
   const float* hc;        // M = 1536 channel-pair path (nmx_k_bank_w64c.h): [n_filters][12][64] pairs of the REAL spectrum in
                           // register order; twc = [24][64] complex pass-A twiddles, then [8][8] complex exp(-2 pi i a b / 64)
   const float* twc;
-  int pair_m;             // 1536 (nmx_k_bank_w64c.h) or 1024 (nmx_k_bank_w64d.h: hc = [n_filters][8][64] pairs in natural order,
-                          // twiddles = twl)
+                          // (nmx_k_bank_w64d.h, M = 1024: hc = [n_filters][8][64] pairs in natural order, twiddles = twl)
+  int kernel;             // NmxFirKernel: the plan's choice for this launch (be_launch_bank_w64 switches on it) ...
+  int pipelined;          // ... NMX_FIR_ONE: batches of >= 4096 items may run the pipelined persistent form (nmx_w64p_ok)
   const float* tw2;       // M = 4096 path (nmx_k_bank_w64x2.h): [1024] complex exp(-2 pi i k / 2048); Hs[f] then holds the
                           // INTERLEAVED (A_k, B_k) table of filter f, 2048 pairs
   int off_Z, off_X, off_red, lds_floats;
@@ -186,6 +187,17 @@ NMX_UNROLL
 #define NMX_W64_TWB_N (15 * 16)
 #define NMX_W64_TWC_N (12 * 64)
 #define NMX_W64_TWL_FLOATS (2 * (NMX_W64_TWB_N + NMX_W64_TWC_N))
+// floats of the 160 KiB of LDS a workgroup of the one-wave FIR kernels may opt in to
+#define NMX_W64_LDS_FLOATS (160 * 1024 / 4)
+// waves per workgroup of the pipelined persistent bank kernel (nmx_k_bank_w64p.h): 8 leaves the 256-VGPR budget (2 waves /
+// SIMD) that the packed-complex formulation needs to stay out of scratch
+#define NMX_W64P_WAVES 8
+// May a launch of `n_filters` filters run nmx_kern_bank_w64pp (host side, when the plan is built)?  Activity-only band
+// power, no reflection, an even window (8-byte row accesses), and the filters' tables next to one tile (x_floats) per wave.
+static inline bool nmx_w64p_ok(const NmxBankArgs& b, int n_filters, int x_floats) {
+  if ((b.bp_features & 6u) || b.pad_mode != 0 || (b.W & 1)) return false;
+  return (NMX_W64_LDS_FLOATS - n_filters * 2 * NMX_W64_N - NMX_W64_TWL_FLOATS) / x_floats >= NMX_W64P_WAVES;
+}
 #if defined(NMX_LDS_ASM) && !defined(NMX_HOST_EMU)
 #include <utility>
 // pass C order: v[4 t + q] = X[lane + 64 t + 256 q]

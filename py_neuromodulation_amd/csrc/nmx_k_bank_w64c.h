@@ -38,13 +38,24 @@
 
 #include "nmx_k_bank_w64.h"
 
-#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
-
 #define NMX_W64C_M 1536
 #define NMX_W64C_TILE_FLOATS (2 * 24 * 72)        // one exchange tile (complex points: 24 rows of 64 + 8 pad)
 #define NMX_W64C_TWA_FLOATS (2 * 24 * 64)         // exp(-2 pi i l ka(reg) / 1536), [reg][lane]
 #define NMX_W64C_TWB_FLOATS (2 * 8 * 8)           // exp(-2 pi i a b / 64), [a][b]
 #define NMX_W64C_H_FLOATS 1536                    // per filter: [12][64] pairs (H[k(lane, 2 i)], H[k(lane, 2 i + 1)])
+
+// ---- what the plan asks before it builds channel-pair tables (host side: build_bank, build_notch) ----------------------
+// the shapes every channel-pair kernel (this one, nmx_k_bank_w64d.h, nmx_k_bank_w64e.h) takes
+static inline bool nmx_w64_pair_shape_ok(const NmxBankArgs& b) { return b.W <= 1024 && !(b.bp_features & 6u); }
+// exchange tiles (= waves) that fit a workgroup's LDS next to `fixed` floats of tables
+static inline int nmx_w64_pair_waves(int fixed, int tile) { return (NMX_W64_LDS_FLOATS - fixed) / tile; }
+// M = 1536: the filters' spectra and the pass-A twiddles; at least six waves per workgroup
+static inline int nmx_w64c_fixed(int n_filters) { return n_filters * NMX_W64C_H_FLOATS + NMX_W64C_TWA_FLOATS; }
+static inline bool nmx_w64c_fits(int n_filters) {
+  return n_filters >= 1 && nmx_w64_pair_waves(nmx_w64c_fixed(n_filters), NMX_W64C_TILE_FLOATS) >= 6;
+}
+
+#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
 
 template <int OFF>
 NMX_DEV void nmx_ds_write_b64(unsigned addr, nmx_c2 v) {
@@ -300,9 +311,6 @@ NMX_DEV void nmx_w64c_epilogue(const NmxBankW64Args& AA, const NmxFilterDev& F, 
   for (int dst = 0; dst < 2; ++dst) {
     float* d = dst ? dyb : dsw;
     if (!d) continue;
-#ifdef NMX_DEBUG_NO_YB   // (bound experiment, tools/exp_fuse_bound.sh: the launcher nulls yb_out after a few launches --
-    if (dst == 1 && !AA.yb_out) continue;   // the band series of the previous, identical step stay in place)
-#endif
     const long long next = (long long)(dst ? A.n_burst_bands : A.n_sw_filters) * W;   // the same band of channel c + 1
     const nmx_rsrc s1 = nmx_make_rsrc(d, 4 * W);
     const nmx_rsrc s2 = nmx_make_rsrc(d + next, two ? 4 * W : 0);

@@ -15,9 +15,16 @@
 #include "nmx_k_bank_w64c.h"
 #include "nmx_k_bank_w64x2.h"
 
-#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
-
 #define NMX_W64D_H_FLOATS 1024   // per filter: [8][64] pairs (H[l + 64 (2 i)], H[l + 64 (2 i + 1)]), natural order
+
+// M = 1024 (host side, build_bank): the filters' spectra and the pass B / C twiddles next to at least six of the one-wave
+// kernels' tiles (x_floats = NmxBankW64Args::lds_floats)
+static inline int nmx_w64d_fixed(int n_filters) { return n_filters * NMX_W64D_H_FLOATS + NMX_W64_TWL_FLOATS; }
+static inline bool nmx_w64d_fits(int n_filters, int x_floats) {
+  return n_filters >= 1 && nmx_w64_pair_waves(nmx_w64d_fixed(n_filters), x_floats) >= 6;
+}
+
+#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
 
 // HALF: W <= 512 -- only the output registers 4 t + r, r < 2 (samples l + 64 t + 256 r < 512) are formed
 template <int HALF>

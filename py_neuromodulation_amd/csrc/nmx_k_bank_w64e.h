@@ -35,12 +35,26 @@
 
 #include "nmx_k_bank_w64c.h"
 
-#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
-
 #define NMX_W64E_M 2048
 #define NMX_W64E_TILE_FLOATS (2 * 32 * 72)        // one exchange tile (complex points: 32 rows of 64 + 8 pad)
 #define NMX_W64E_TWA_FLOATS (2 * 32 * 64)         // exp(-2 pi i l ka(reg) / 2048), [reg][lane]
 #define NMX_W64E_H_FLOATS 2048                    // per filter: [16][64] pairs (H[k(lane, 2 i)], H[k(lane, 2 i + 1)])
+
+// M = 2048 (host side: build_bank, build_notch, choose_notch_bank_fuse): `n_spectra` spectra and the pass-A twiddles next to
+// at least four waves' tiles; the notch (PAD = 1): one filter whose two reflected flanks stay apart, W + 2 h <= M
+static inline int nmx_w64e_fixed(int n_spectra) { return n_spectra * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS; }
+static inline bool nmx_w64e_fits(int n_spectra) {
+  return n_spectra >= 1 && nmx_w64_pair_waves(nmx_w64e_fixed(n_spectra), NMX_W64E_TILE_FLOATS) >= 4;
+}
+static inline bool nmx_w64e_notch_ok(const NmxBankArgs& b) {
+  return nmx_w64_pair_shape_ok(b) && b.pad_mode != 0 && b.n_filters == 1 && b.W + 2 * b.pad_half <= NMX_W64E_M && nmx_w64e_fits(1);
+}
+// the notch shape that is compiled in (WC, HC): 1 kHz x 1 s windows, 999 taps -- the default
+static inline bool nmx_w64e_notch_w1000(const NmxBankArgs& b) {
+  return b.pad_mode != 0 && b.W == 1000 && b.pad_half == 499 && b.n_edge >= 499;
+}
+
+#if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
 
 // a * exp(DIR 2 pi i MM / 32), MM = ja * r <= 21
 template <int DIR, int MM>

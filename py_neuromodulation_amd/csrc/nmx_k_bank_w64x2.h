@@ -19,6 +19,12 @@
 
 #include "nmx_k_bank_w64.h"
 
+// M = 4096 (host side, build_fir_stage): filters whose 16 KiB (A_k, B_k) tables fit a workgroup's LDS next to the pass B / C
+// twiddles, w^k and the eight waves' tiles (x_floats = NmxBankW64Args::lds_floats); the others are read from L2
+#define NMX_W64X2_WAVES 8
+static inline int nmx_w64x2_fixed(int x_floats) { return NMX_W64_TWL_FLOATS + 2048 + NMX_W64X2_WAVES * x_floats; }
+static inline int nmx_w64x2_lds_tables(int x_floats) { return (NMX_W64_LDS_FLOATS - nmx_w64x2_fixed(x_floats)) / 4096; }
+
 #if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
 
 typedef float nmx_f4 __attribute__((ext_vector_type(4)));

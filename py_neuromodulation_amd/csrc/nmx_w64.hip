@@ -1,7 +1,10 @@
 // nmx_w64.hip -- translation unit of the one-wave FIR kernels (nmx_k_bank_w64*.h): notch, band-pass bank
 // (M = 1024 / 1536 channel pairs, M = 2048, M = 4096).  Built ONCE by __graft_entry__.build_lib() with
-// -fno-slp-vectorize -DNMX_LDS_ASM=1 -DNMX_W64_NAME=rd64: complex arithmetic is packed explicitly (inline asm with
+// -fno-slp-vectorize -DNMX_LDS_ASM=1: complex arithmetic is packed explicitly (inline asm with
 // operand modifiers, unpaired ds_read_b64); clang's SLP vectoriser on top of that spills.
+// Which launcher runs is the plan's choice (NmxBankW64Args::kernel, be_launch_bank_w64 in nmx_api.hip): no launcher here
+// tests whether a shape fits -- the plan asked the predicates beside each kernel's constants.  What depends on the batch
+// size (waves per workgroup, grid, the form of the one-channel kernels) is decided here.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -13,29 +16,43 @@
 #include "nmx_k_bank_w64d.h"
 #include "nmx_k_bank_w64e.h"
 
-#if !defined(NMX_W64_NAME) || !defined(NMX_LDS_ASM)
-#error "compile with -DNMX_W64_NAME=rd64 -DNMX_LDS_ASM=1"
+#if !defined(NMX_LDS_ASM)
+#error "compile with -DNMX_LDS_ASM=1"
 #endif
-// waves per persistent workgroup (= per CU): 8 leaves the 256-VGPR budget (2 waves/SIMD) that the
-// packed-complex formulation needs to stay out of scratch
-#ifndef NMX_W64P_WAVES
-#define NMX_W64P_WAVES 8
-#endif
-#define NMX_CAT2(a, b) a##b
-#define NMX_CAT(a, b) NMX_CAT2(a, b)
-#define NMX_STR2(a) #a
-#define NMX_STR(a) NMX_STR2(a)
-#define NMX_KNAME(stem, tail) nmxi_note_kernel(stem NMX_STR(NMX_W64_NAME) tail)
 
 extern __shared__ __attribute__((aligned(16))) float nmx_smem_w64[];
 
+// every kernel here may use the 160 KiB of LDS: the opt-in, once per device (defined behind the kernels)
+static void nmx_w64_allow_lds();
+
+// Launch geometry of the channel-pair kernels (M = 1024 / 1536 / 2048 and the fused notch + filters): `fixed` floats of
+// tables and one tile of `tile` floats per wave, at most `cap` waves per workgroup -- two when the batch is a hop or two, to
+// spread the few items over many CUs.  One workgroup per CU; a wave walks `chunk` consecutive (channel pair, window) items.
+struct NmxW64PairGeom {
+  int nw, grid, chunk, n_windows, n_pairs;
+  size_t lds;
+};
+static NmxW64PairGeom nmx_w64_pair_geom(int fixed, int tile, int cap, int n_items, int C, int n_cu) {
+  NmxW64PairGeom g;
+  g.n_windows = n_items / C;
+  g.n_pairs = g.n_windows * ((C + 1) / 2);
+  g.nw = nmx_w64_pair_waves(fixed, tile);
+  if (g.nw > cap) g.nw = cap;
+  if (g.n_pairs < 2048) g.nw = 2;
+  g.lds = (size_t)(fixed + g.nw * tile) * 4;
+  g.grid = n_cu > 0 ? n_cu : 256;
+  if (g.grid * g.nw > g.n_pairs) g.grid = (g.n_pairs + g.nw - 1) / g.nw;
+  g.chunk = (g.n_pairs + g.grid * g.nw - 1) / (g.grid * g.nw);
+  return g;
+}
+
 // register budgets: the FIR-bank instantiation fits 168 VGPRs (3 waves/SIMD, 12 per CU, 5 spilled
 // dwords); the notch instantiation (odd-reflection staging) needs the 256-VGPR budget.
-__global__ void __launch_bounds__(64, 3) NMX_CAT(nmx_kern_bank_w64_, NMX_W64_NAME)(const NmxBankW64Args A) {
+__global__ void __launch_bounds__(64, 3) nmx_kern_bank_w64_rd64(const NmxBankW64Args A) {
   const int item = blockIdx.x;
   nmx_bank_w64_item<0, 0, 1>(A, item / A.b.n_channels, item % A.b.n_channels, nmx_smem_w64, nullptr);
 }
-__global__ void __launch_bounds__(64, 2) NMX_CAT(nmx_kern_notch_w64_, NMX_W64_NAME)(const NmxBankW64Args A) {
+__global__ void __launch_bounds__(64, 2) nmx_kern_notch_w64_rd64(const NmxBankW64Args A) {
   const int item = blockIdx.x;
   nmx_bank_w64_item<1, 0, 0>(A, item / A.b.n_channels, item % A.b.n_channels, nmx_smem_w64, nullptr);
 }
@@ -48,8 +65,7 @@ __global__ void __launch_bounds__(64, 2) NMX_CAT(nmx_kern_notch_w64_, NMX_W64_NA
 // Pipelined persistent kernel (nmx_k_bank_w64p.h): the A / B tables are staged INTERLEAVED ((A_k, B_k) pairs: one
 // 8-byte read per point), everything else as below.
 template <int HALF>
-__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_NAME)(const NmxBankW64Args A0, int n_items,
-                                                                                    int x_floats) {
+__global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64pp_rd64(const NmxBankW64Args A0, int n_items, int x_floats) {
   // (kernel-argument pointer laundered once per item: the plan is re-read with s_load, not hoisted into scalar
   // registers that spill to lanes of a VGPR)
   typedef const NmxBankW64Args __attribute__((address_space(4)))* nmx_karg_p;
@@ -78,8 +94,7 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_
 // Notch, four items per workgroup: the filter's A / B tables and the twiddles are staged in LDS once per
 // FOUR items (the one-wave-per-workgroup kernel fetches ~27 KB of tables from L2 per item); no item loop,
 // so none of the scalar-register pressure of the persistent form.
-__global__ void __launch_bounds__(256, 3) NMX_CAT(nmx_kern_notch_w64q_, NMX_W64_NAME)(const NmxBankW64Args A, int n_items,
-                                                                                      int x_floats) {
+__global__ void __launch_bounds__(256, 3) nmx_kern_notch_w64q_rd64(const NmxBankW64Args A, int n_items, int x_floats) {
   float* tab = nmx_smem_w64;
   const int n = NMX_W64_N, tab_floats = 2 * n;
   for (int i = threadIdx.x; i < tab_floats; i += 256) tab[i] = i < n ? A.Hs[0][i] : A.Hd[0][i - n];
@@ -103,8 +118,8 @@ __global__ void __launch_bounds__(256, 3) NMX_CAT(nmx_kern_notch_w64q_, NMX_W64_
 // per workgroup instead of once per four items (the staging + its barrier + the workgroup launch were a quarter of
 // the four-item kernel's time).  The kernel-argument pointer is laundered once per iteration so that the plan is
 // re-read with s_load instead of being hoisted into (spilled) scalar registers (nmx_wave.hip).
-__global__ void __launch_bounds__(64 * NMX_NOTCH_QP_WAVES, 3) NMX_CAT(nmx_kern_notch_w64qp_, NMX_W64_NAME)(const NmxBankW64Args A0, int n_items,
-                                                                                       int x_floats) {
+__global__ void __launch_bounds__(64 * NMX_NOTCH_QP_WAVES, 3) nmx_kern_notch_w64qp_rd64(const NmxBankW64Args A0, int n_items,
+                                                            int x_floats) {
   typedef const NmxBankW64Args __attribute__((address_space(4)))* nmx_karg_p;
   nmx_karg_p Ap = (nmx_karg_p)__builtin_amdgcn_kernarg_segment_ptr();
   float* tab = nmx_smem_w64;
@@ -131,8 +146,7 @@ __global__ void __launch_bounds__(64 * NMX_NOTCH_QP_WAVES, 3) NMX_CAT(nmx_kern_n
 // M = 4096 (nmx_k_bank_w64x2.h): persistent workgroups of `nw` waves; LDS = tables of the first n_tab filters,
 // pass B / C twiddles, w^k, one exchange tile per wave
 template <int HALF>
-__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_NAME)(const NmxBankW64Args A0, int n_items,
-                                                                                    int x_floats, int n_tab) {
+__global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64x2_rd64(const NmxBankW64Args A0, int n_items, int x_floats, int n_tab) {
   // (the kernel-argument pointer is laundered once per item: the plan -- eight filters' worth of descriptors -- is then
   // re-read with s_load instead of being hoisted into scalar registers that spill to v_writelane / v_readlane, 108 of
   // them in the first form of this loop)
@@ -157,39 +171,27 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_
   }
 }
 
-extern "C" int NMX_CAT(nmx_w64x2_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_NAME)<0>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_NAME)<1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  static int nw_env = 0;
-  if (!nw_env) nw_env = 8;
-  const int nw = nw_env, x_floats = A->lds_floats;
-  int n_tab = (160 * 1024 / 4 - NMX_W64_TWL_FLOATS - 2048 - nw * x_floats) / 4096;
-  if (n_tab > A->b.n_filters) n_tab = A->b.n_filters;
-  if (n_tab < 0) return 0;
-  const size_t lds = (size_t)(n_tab * 4096 + NMX_W64_TWL_FLOATS + 2048 + nw * x_floats) * 4;
+extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
+  nmx_w64_allow_lds();
+  const int nw = NMX_W64X2_WAVES, x_floats = A->lds_floats;
+  const int n_tab = nmx_w64x2_lds_tables(x_floats) < A->b.n_filters ? nmx_w64x2_lds_tables(x_floats) : A->b.n_filters;
+  const size_t lds = (size_t)(n_tab * 4096 + nmx_w64x2_fixed(x_floats)) * 4;
   int grid = n_cu > 0 ? n_cu : 256;
   if (grid * nw > n_items) grid = (n_items + nw - 1) / nw;
   if (A->b.W <= 2048) {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_NAME)<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
-    NMX_KNAME("nmx_kern_bank_w64x2_", "<1>");
+    hipLaunchKernelGGL((nmx_kern_bank_w64x2_rd64<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
+    nmxi_note_kernel("nmx_kern_bank_w64x2_rd64<1>");
   } else {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64x2_, NMX_W64_NAME)<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
-    NMX_KNAME("nmx_kern_bank_w64x2_", "<0>");
+    hipLaunchKernelGGL((nmx_kern_bank_w64x2_rd64<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
+    nmxi_note_kernel("nmx_kern_bank_w64x2_rd64<0>");
   }
-  return 1;
 }
 
 // M = 1536, one wave per (window, channel pair) (nmx_k_bank_w64c.h): workgroups of `nw` waves; LDS = the real spectra of
 // all filters, the pass-A twiddles, one exchange tile per wave.  A wave walks a CONTIGUOUS run of `chunk` items in the
 // order (channel pair, window): consecutive items are consecutive hops of the same two channels, whose windows
 // overlap by W - hop samples -- after the first item of a run most of the window comes from L2.
-__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64c_, NMX_W64_NAME)(const NmxBankW64Args A, int n_windows,
-                                                                                   int n_pairs, int chunk) {
+__global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64c_rd64(const NmxBankW64Args A, int n_windows, int n_pairs, int chunk) {
   float* tab = nmx_smem_w64;
   const int hf = A.b.n_filters * NMX_W64C_H_FLOATS;
   for (int i = threadIdx.x; i < hf; i += blockDim.x) tab[i] = A.hc[i];
@@ -211,8 +213,8 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64c_, NMX_W64_N
 // M = 1024, one wave per (window, channel pair) (nmx_k_bank_w64d.h): LDS = real spectra of all filters, pass B / C
 // twiddles, one exchange tile per wave; the same contiguous runs of hops per wave
 template <int HALF>
-__global__ void __launch_bounds__(64 * (HALF ? 12 : 8)) NMX_CAT(nmx_kern_bank_w64d_, NMX_W64_NAME)(const NmxBankW64Args A, int n_windows,
-                                                                                   int n_pairs, int chunk, int x_floats) {
+__global__ void __launch_bounds__(64 * (HALF ? 12 : 8)) nmx_kern_bank_w64d_rd64(const NmxBankW64Args A, int n_windows,
+                                                            int n_pairs, int chunk, int x_floats) {
   float* tab = nmx_smem_w64;
   const int hf = A.b.n_filters * NMX_W64D_H_FLOATS;
   for (int i = threadIdx.x; i < hf; i += blockDim.x) tab[i] = A.hc[i];
@@ -229,42 +231,25 @@ __global__ void __launch_bounds__(64 * (HALF ? 12 : 8)) NMX_CAT(nmx_kern_bank_w6
   }
 }
 
-extern "C" int NMX_CAT(nmx_w64d_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64d_, NMX_W64_NAME)<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64d_, NMX_W64_NAME)<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int C = A->b.n_channels, n_windows = n_items / C, n_pairs = n_windows * ((C + 1) / 2);
+extern "C" void nmx_w64d_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
+  nmx_w64_allow_lds();
   const int x_floats = A->lds_floats;
-  const int fixed = A->b.n_filters * NMX_W64D_H_FLOATS + NMX_W64_TWL_FLOATS;
-  int nw = (160 * 1024 / 4 - fixed) / x_floats;
-  if (nw < 6) return 0;
-  static int want = 0;
-  if (!want) want = 12;
-  const int cap = A->b.W <= 512 ? want : (want < 8 ? want : 8);   // W <= 512: 114 VGPRs, three waves per SIMD fit
-  if (nw > cap) nw = cap;
-  if (n_pairs < 2048) nw = 2;
-  const size_t lds = (size_t)(fixed + nw * x_floats) * 4;
-  int grid = n_cu > 0 ? n_cu : 256;
-  if (grid * nw > n_pairs) grid = (n_pairs + nw - 1) / nw;
-  const int chunk = (n_pairs + grid * nw - 1) / (grid * nw);
+  // W <= 512: 114 VGPRs, three waves per SIMD fit
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64d_fixed(A->b.n_filters), x_floats, A->b.W <= 512 ? 12 : 8, n_items, A->b.n_channels, n_cu);
   if (A->b.W <= 512) {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64d_, NMX_W64_NAME)<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk, x_floats);
-    NMX_KNAME("nmx_kern_bank_w64d_", "<1>");
+    hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
+    nmxi_note_kernel("nmx_kern_bank_w64d_rd64<1>");
   } else {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64d_, NMX_W64_NAME)<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk, x_floats);
-    NMX_KNAME("nmx_kern_bank_w64d_", "<0>");
+    hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
+    nmxi_note_kernel("nmx_kern_bank_w64d_rd64<0>");
   }
-  return 1;
 }
 
 // M = 2048, one wave per (window, channel pair) (nmx_k_bank_w64e.h): PAD = 0 the "same" FIR bank of the filters the
 // M = 1536 kernel cannot take, PAD = 1 the notch (odd-reflected window, one filter, the window back to HBM).  LDS = the
 // real spectra of the filters, the pass-A twiddles, one 18 KiB exchange tile per wave; contiguous runs of hops per wave.
 template <int PAD, int WC = 0, int HC = 0>
-__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)(const NmxBankW64Args A0, int n_windows,
-                                                                                   int n_pairs, int chunk) {
+__global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64e_rd64(const NmxBankW64Args A0, int n_windows, int n_pairs, int chunk) {
   // (kernel-argument pointer laundered once per item: the plan is re-read with s_load, not hoisted into scalar
   // registers that spill to lanes of a VGPR)
   typedef const NmxBankW64Args __attribute__((address_space(4)))* nmx_karg_p;
@@ -299,8 +284,8 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_N
 // twiddles, one exchange tile per wave; FUSE = 1 reads the notch's spectrum from global memory, which leaves the seven
 // tiles of the two launches it replaces.
 template <int WC, int HC, int FUSE>
-__global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)(const NmxW64eFusedArgs A0, int n_windows,
-                                                                                         int n_pairs, int chunk) {
+__global__ void __launch_bounds__(64 * 8) nmx_kern_notch_bank_w64e_rd64(const NmxW64eFusedArgs A0, int n_windows,
+                                                            int n_pairs, int chunk) {
   typedef const NmxW64eFusedArgs __attribute__((address_space(4)))* nmx_karg_p;
   nmx_karg_p Ap = (nmx_karg_p)__builtin_amdgcn_kernarg_segment_ptr();
   float* tab = nmx_smem_w64;
@@ -329,198 +314,93 @@ __global__ void __launch_bounds__(64 * 8) NMX_CAT(nmx_kern_notch_bank_w64e_, NMX
   }
 }
 
-// Waves per workgroup of the fused launch of notch Nn and PAD = 0 filters F (g_lds: the notch's spectrum in LDS too), or 0
-// when they do not fuse: only the compile-time notch shape, both on the M = 2048 pair kernels over the same windows, the
-// filters taking the carried offset on load.  Decided when the plan is built (nmx_engine_plan_fir.inc).
-extern "C" int NMX_CAT(nmx_w64_takes_dc_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items);
-extern "C" int NMX_CAT(nmx_w64e_fused_waves_, NMX_W64_NAME)(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds) {
-  if (!Nn->b.pad_mode || Nn->b.n_filters != 1 || Nn->b.W != 1000 || Nn->b.pad_half != 499 || Nn->b.n_edge < 499) return 0;
-  if (!Nn->hc || !Nn->twc || Nn->pair_m != 2048 || Nn->tw2) return 0;
-  if (F->b.W != Nn->b.W || F->b.n_channels != Nn->b.n_channels || F->twc != Nn->twc) return 0;
-  if (!NMX_CAT(nmx_w64_takes_dc_, NMX_W64_NAME)(F, 0) || F->pair_m != 2048) return 0;
-  const int fixed = (F->b.n_filters + (g_lds ? 1 : 0)) * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS;
-  int nw = (160 * 1024 / 4 - fixed) / NMX_W64E_TILE_FLOATS;
-  if (nw > 8) nw = 8;
-  return nw >= 4 ? nw : 0;
-}
-
-// the fused launch: F and Nn as their own launches would get them (per-call fields patched in)
-extern "C" int NMX_CAT(nmx_w64e_launch_fused_, NMX_W64_NAME)(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds,
-                                                           int n_items, int n_cu, hipStream_t s) {
-  int nw = NMX_CAT(nmx_w64e_fused_waves_, NMX_W64_NAME)(F, Nn, g_lds);
-  if (!nw) return 0;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+// the fused launch (the plan's choice: choose_notch_bank_fuse): F and Nn as their own launches would get them (per-call
+// fields patched in); g_lds: the notch's spectrum in LDS too
+extern "C" void nmx_w64e_launch_fused_rd64(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds, int n_items, int n_cu,
+                                           hipStream_t s) {
+  nmx_w64_allow_lds();
   NmxW64eFusedArgs A;
   A.f = *F;
   A.n.x = Nn->b.x; A.n.ch_stride = Nn->b.ch_stride; A.n.win_stride = Nn->b.win_stride; A.n.starts = Nn->b.starts;
   A.n.y_out = Nn->b.y_out; A.n.hg = Nn->hc; A.n.clean_on_load = Nn->b.clean_on_load; A.n.residual = Nn->b.residual;
-  const int C = F->b.n_channels, n_windows = n_items / C, n_pairs = n_windows * ((C + 1) / 2);
-  const int fixed = (F->b.n_filters + (g_lds ? 1 : 0)) * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS;
-  if (n_pairs < 2048) nw = 2;   // a hop or two: spread the few items over many CUs
-  const size_t lds = (size_t)(fixed + nw * NMX_W64E_TILE_FLOATS) * 4;
-  int grid = n_cu > 0 ? n_cu : 256;
-  if (grid * nw > n_pairs) grid = (n_pairs + nw - 1) / nw;
-  const int chunk = (n_pairs + grid * nw - 1) / (grid * nw);
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(F->b.n_filters + (g_lds ? 1 : 0)), NMX_W64E_TILE_FLOATS, 8, n_items,
+                                             F->b.n_channels, n_cu);
   if (g_lds) {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 2>), dim3(grid), dim3(64 * nw), lds, s, A, n_windows, n_pairs, chunk);
-    NMX_KNAME("nmx_kern_notch_bank_w64e_", "<1000, 499, 2>");
+    hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
+    nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>");
   } else {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_notch_bank_w64e_, NMX_W64_NAME)<1000, 499, 1>), dim3(grid), dim3(64 * nw), lds, s, A, n_windows, n_pairs, chunk);
-    NMX_KNAME("nmx_kern_notch_bank_w64e_", "<1000, 499, 1>");
+    hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
+    nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>");
   }
-  return 1;
 }
 
-// Would the dispatcher of nmx_api.hip (be_launch_bank_w64) end up in a kernel that adds the carried offset on load
-// (NmxBankArgs::dcf: the channel-pair kernels of nmx_k_bank_w64c.h / nmx_k_bank_w64e.h)?  The same conditions as the
-// launchers below; anything else reads a copy of the windows with the offset added back (nmx_engine_run.inc).
-extern "C" int NMX_CAT(nmx_w64_takes_dc_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items) {
-  (void)n_items;
-  if (A->tw2 || !A->hc || A->b.pad_mode != 0 || A->b.n_filters < 1) return 0;
-  if (A->pair_m == 2048) {
-    if (A->b.W > 1024 || (A->b.bp_features & 6u) || !A->twc) return 0;
-    return (160 * 1024 / 4 - (A->b.n_filters * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS)) / NMX_W64E_TILE_FLOATS >= 4;
-  }
-  if (A->pair_m == 1536)
-    return (160 * 1024 / 4 - (A->b.n_filters * NMX_W64C_H_FLOATS + NMX_W64C_TWA_FLOATS)) / NMX_W64C_TILE_FLOATS >= 6;
-  return 0;
-}
-
-// returns 0 when the configuration does not fit (caller falls back to the one-channel M = 2048 kernels)
-extern "C" int NMX_CAT(nmx_w64e_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  const bool pad = A->b.pad_mode != 0;
-  if (A->b.W > 1024 || (A->b.bp_features & 6u) || !A->hc || !A->twc || A->b.n_filters < 1) return 0;
-  if (pad && (A->b.n_filters != 1 || A->b.W + 2 * A->b.pad_half > NMX_W64E_M)) return 0;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<1, 1000, 499>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int C = A->b.n_channels, n_windows = n_items / C, n_pairs = n_windows * ((C + 1) / 2);
-  const int fixed = A->b.n_filters * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS;
-  int nw = (160 * 1024 / 4 - fixed) / NMX_W64E_TILE_FLOATS;
-  if (nw < 4) return 0;
-  static int want = 0;
-  if (!want) want = 8;
-  if (nw > want) nw = want;
-  if (n_pairs < 2048) nw = 2;   // a hop or two: spread the few items over many CUs
-  const size_t lds = (size_t)(fixed + nw * NMX_W64E_TILE_FLOATS) * 4;
-  int grid = n_cu > 0 ? n_cu : 256;
-  if (grid * nw > n_pairs) grid = (n_pairs + nw - 1) / nw;
-  const int chunk = (n_pairs + grid * nw - 1) / (grid * nw);
-  if (pad && A->b.W == 1000 && A->b.pad_half == 499 && A->b.n_edge >= 499) {   // the default notch: 1 kHz x 1 s windows, 999 taps
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<1, 1000, 499>), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk);
-    NMX_KNAME("nmx_kern_bank_w64e_", "<1, 1000, 499>");
-  } else if (pad) {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk);
-    NMX_KNAME("nmx_kern_bank_w64e_", "<1>");
+extern "C" void nmx_w64e_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
+  nmx_w64_allow_lds();
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(A->b.n_filters), NMX_W64E_TILE_FLOATS, 8, n_items, A->b.n_channels, n_cu);
+  if (nmx_w64e_notch_w1000(A->b)) {
+    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1, 1000, 499>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1, 1000, 499>");
+  } else if (A->b.pad_mode != 0) {
+    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1>");
   } else {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64e_, NMX_W64_NAME)<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk);
-    NMX_KNAME("nmx_kern_bank_w64e_", "<0>");
+    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<0>");
   }
-  return 1;
 }
 
-// returns 0 when the tables do not fit next to at least six tiles (caller falls back to the M = 2048 kernels)
-extern "C" int NMX_CAT(nmx_w64c_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen))
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64c_, NMX_W64_NAME),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const int C = A->b.n_channels, n_windows = n_items / C, n_pairs = n_windows * ((C + 1) / 2);
-  const int fixed = A->b.n_filters * NMX_W64C_H_FLOATS + NMX_W64C_TWA_FLOATS;
-  int nw = (160 * 1024 / 4 - fixed) / NMX_W64C_TILE_FLOATS;
-  if (nw < 6) return 0;
-  if (nw > 8) nw = 8;
-  if (n_pairs < 2048) nw = 2;   // a hop or two: spread the few items over many CUs
-  const size_t lds = (size_t)(fixed + nw * NMX_W64C_TILE_FLOATS) * 4;
-  int grid = n_cu > 0 ? n_cu : 256;
-  if (grid * nw > n_pairs) grid = (n_pairs + nw - 1) / nw;
-  const int chunk = (n_pairs + grid * nw - 1) / (grid * nw);
-#ifdef NMX_DEBUG_NO_YB
-  static int launches = 0;
-  NmxBankW64Args B = *A;
-  if (++launches > 6) B.yb_out = nullptr;
-  A = &B;
-#endif
-  hipLaunchKernelGGL(NMX_CAT(nmx_kern_bank_w64c_, NMX_W64_NAME), dim3(grid), dim3(64 * nw), lds, s, *A, n_windows, n_pairs, chunk);
-  NMX_KNAME("nmx_kern_bank_w64c_", "");
-  return 1;
+extern "C" void nmx_w64c_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
+  nmx_w64_allow_lds();
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64c_fixed(A->b.n_filters), NMX_W64C_TILE_FLOATS, 8, n_items, A->b.n_channels, n_cu);
+  hipLaunchKernelGGL(nmx_kern_bank_w64c_rd64, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+  nmxi_note_kernel("nmx_kern_bank_w64c_rd64");
 }
 
-// returns 0 when the configuration does not fit (caller falls back to one wave per workgroup)
-extern "C" int NMX_CAT(nmx_w64q_launch_notch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, hipStream_t s) {
-  if (A->b.pad_mode == 0 || A->b.n_filters != 1 || !A->twl) return 0;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_w64q_, NMX_W64_NAME),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int x_floats = A->lds_floats;
-  const size_t lds = (size_t)(2 * NMX_W64_N + NMX_W64_TWL_FLOATS + 4 * x_floats) * 4;
-  if (n_items >= 3 * 256 * 4 * 8) {   // eight items or more per wave: persistent workgroups
-    static unsigned long long seen_p = 0;
-    if (nmx_first_on_device(seen_p))
-      (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_w64qp_, NMX_W64_NAME),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// One channel per M = 2048 transform; `lds`: one item's LDS (the one-wave-per-workgroup kernels).  The form follows the
+// batch: >= 4096 items the persistent pipelined bank (nmx_k_bank_w64p.h) where the plan allows it; the notch from 1024 items
+// four items per workgroup, from eight items per wave of a full device its persistent form; else a workgroup per item.
+extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args* A, int n_items, size_t lds, int n_cu, hipStream_t s) {
+  nmx_w64_allow_lds();
+  const int x_floats = A->lds_floats;   // per-wave exchange tile (+ scratch)
+  if (n_items >= 4096 && A->pipelined) {
+    const int nw = NMX_W64P_WAVES, tab_floats = A->b.n_filters * 2 * NMX_W64_N;
+    const size_t ldsp = (size_t)(tab_floats + NMX_W64_TWL_FLOATS + nw * x_floats) * 4;
+    int grid = n_cu > 0 ? n_cu : 256;
+    if (grid * nw > n_items) grid = (n_items + nw - 1) / nw;
+    if (A->b.W <= 1024) {   // the upper half of every inverse transform's outputs is never formed
+      hipLaunchKernelGGL((nmx_kern_bank_w64pp_rd64<1>), dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
+      nmxi_note_kernel("nmx_kern_bank_w64pp_rd64<1>");
+    } else {
+      hipLaunchKernelGGL((nmx_kern_bank_w64pp_rd64<0>), dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
+      nmxi_note_kernel("nmx_kern_bank_w64pp_rd64<0>");
+    }
+  } else if (A->b.pad_mode != 0 && n_items >= 3 * 256 * 4 * 8) {
     const size_t ldsp = (size_t)(2 * NMX_W64_N + NMX_W64_TWL_FLOATS + 1024 + NMX_NOTCH_QP_WAVES * x_floats) * 4;
-    hipLaunchKernelGGL(NMX_CAT(nmx_kern_notch_w64qp_, NMX_W64_NAME), dim3((12 / NMX_NOTCH_QP_WAVES) * 256), dim3(64 * NMX_NOTCH_QP_WAVES), ldsp, s, *A, n_items, x_floats);
-    NMX_KNAME("nmx_kern_notch_w64qp_", "");
-    return 1;
+    hipLaunchKernelGGL(nmx_kern_notch_w64qp_rd64, dim3((12 / NMX_NOTCH_QP_WAVES) * 256), dim3(64 * NMX_NOTCH_QP_WAVES), ldsp, s, *A, n_items, x_floats);
+    nmxi_note_kernel("nmx_kern_notch_w64qp_rd64");
+  } else if (A->b.pad_mode != 0 && n_items >= 1024) {
+    const size_t ldsq = (size_t)(2 * NMX_W64_N + NMX_W64_TWL_FLOATS + 4 * x_floats) * 4;
+    hipLaunchKernelGGL(nmx_kern_notch_w64q_rd64, dim3((n_items + 3) / 4), dim3(256), ldsq, s, *A, n_items, x_floats);
+    nmxi_note_kernel("nmx_kern_notch_w64q_rd64");
+  } else if (A->b.pad_mode == 0) {
+    hipLaunchKernelGGL(nmx_kern_bank_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
+    nmxi_note_kernel("nmx_kern_bank_w64_rd64");
+  } else {
+    hipLaunchKernelGGL(nmx_kern_notch_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
+    nmxi_note_kernel("nmx_kern_notch_w64_rd64");
   }
-  hipLaunchKernelGGL(NMX_CAT(nmx_kern_notch_w64q_, NMX_W64_NAME), dim3((n_items + 3) / 4), dim3(256), lds, s, *A, n_items,
-                     x_floats);
-  NMX_KNAME("nmx_kern_notch_w64q_", "");
-  return 1;
 }
 
-// M = 2048 band-pass bank, persistent 8-wave workgroups with the software-pipelined item (nmx_k_bank_w64p.h).
-// Returns 0 when the configuration does not fit (caller falls back to one wave per workgroup).
-extern "C" int NMX_CAT(nmx_w64p_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  if ((A->b.bp_features & 6u) || A->b.pad_mode != 0 || !A->twl || (A->b.W & 1)) return 0;
-  const int x_floats = A->lds_floats;                  // per-wave exchange tile (+ scratch)
-  const int tab_floats = A->b.n_filters * 2 * NMX_W64_N;
-  const int nw = 8;
-  if ((160 * 1024 / 4 - tab_floats - NMX_W64_TWL_FLOATS) / x_floats < nw) return 0;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_NAME)<0>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_NAME)<1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const size_t lds = (size_t)(tab_floats + NMX_W64_TWL_FLOATS + nw * x_floats) * 4;
-  int grid = n_cu > 0 ? n_cu : 256;
-  if (grid * nw > n_items) grid = (n_items + nw - 1) / nw;
-  if (A->b.W <= 1024) {   // the upper half of every inverse transform's outputs is never formed
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_NAME)<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats);
-    NMX_KNAME("nmx_kern_bank_w64pp_", "<1>");
-  } else {
-    hipLaunchKernelGGL((NMX_CAT(nmx_kern_bank_w64pp_, NMX_W64_NAME)<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats);
-    NMX_KNAME("nmx_kern_bank_w64pp_", "<0>");
-  }
-  return 1;
-}
-
-extern "C" void NMX_CAT(nmx_w64_launch_, NMX_W64_NAME)(const NmxBankW64Args* A, int n_items, size_t lds,
-                                                       hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_bank_w64_, NMX_W64_NAME),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_notch_w64_, NMX_W64_NAME),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  if (A->b.pad_mode == 0) {
-    hipLaunchKernelGGL(NMX_CAT(nmx_kern_bank_w64_, NMX_W64_NAME), dim3(n_items), dim3(64), lds, s, *A);
-    NMX_KNAME("nmx_kern_bank_w64_", "");
-  } else {
-    hipLaunchKernelGGL(NMX_CAT(nmx_kern_notch_w64_, NMX_W64_NAME), dim3(n_items), dim3(64), lds, s, *A);
-    NMX_KNAME("nmx_kern_notch_w64_", "");
-  }
+static void nmx_w64_allow_lds() {
+  static unsigned long long seen = 0;   // per device: the opt-in is a per-device attribute
+  if (!nmx_first_on_device(seen)) return;
+  const void* kernels[] = {(const void*)nmx_kern_bank_w64_rd64, (const void*)nmx_kern_notch_w64_rd64,
+                           (const void*)nmx_kern_bank_w64pp_rd64<0>, (const void*)nmx_kern_bank_w64pp_rd64<1>,
+                           (const void*)nmx_kern_notch_w64q_rd64, (const void*)nmx_kern_notch_w64qp_rd64,
+                           (const void*)nmx_kern_bank_w64x2_rd64<0>, (const void*)nmx_kern_bank_w64x2_rd64<1>,
+                           (const void*)nmx_kern_bank_w64c_rd64, (const void*)nmx_kern_bank_w64d_rd64<0>,
+                           (const void*)nmx_kern_bank_w64d_rd64<1>, (const void*)nmx_kern_bank_w64e_rd64<0>,
+                           (const void*)nmx_kern_bank_w64e_rd64<1>, (const void*)nmx_kern_bank_w64e_rd64<1, 1000, 499>,
+                           (const void*)nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>, (const void*)nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>};
+  for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

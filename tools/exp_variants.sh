@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of build variants / knobs on the bench workload: per-kernel HIP-event times + output equality.
-#   gpurun -- 'bash tools/exp_variants.sh "NMX_W64_VARIANT=scalar" "NMX_W64_VARIANT=rd64" ...'
+#   bash tools/exp_variants.sh "NMX_BANK_W64C=0" "NMX_BANK_W64E=0" ...
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/exp
