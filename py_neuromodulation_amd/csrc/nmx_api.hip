@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(1024) nmx_kern_burst_thr_wide(const NmxBurstTh
 extern "C" void nmx_timeosc_fixed_launch128(const NmxTimeOscArgs* A, int n_items, size_t lds, hipStream_t s);
 extern "C" void nmx_hilbert_fixed_launch128(const NmxHilbertArgs* A, long long n_items, size_t lds, hipStream_t s);
 // one-item-per-wave kernels live in nmx_wave.hip (compile-time workgroup size)
-extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, int n_items, size_t lds, hipStream_t s);
+extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, NmxBurstStatKind kind, int n_items, size_t lds, hipStream_t s);
 extern "C" void nmx_wave_launch_sharp(const NmxSharpArgs* A, int n_items, size_t lds, hipStream_t s);
 __global__ void __launch_bounds__(256) nmx_kern_reref(const NmxRerefArgs A) {
   nmx_reref_tile(A, (long long)blockIdx.x * 256 + threadIdx.x, (int)blockIdx.y * NMX_REREF_ROWS);
@@ -523,14 +523,17 @@ static void be_launch_notch_bank_fused(const NmxBankW64Args& F, const NmxBankW64
                                        be_stream_t s) {
   nmx_w64e_launch_fused_rd64(&F, &N, g_lds ? 1 : 0, n_items, n_cu, s);
 }
-extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s);
-static void be_launch_sharp_dense(const NmxSharpArgs& A, int n_items, be_stream_t s) {
+extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, NmxSharpKind kind, int n_items, hipStream_t s);
+extern "C" void nmx_wave_launch_sharp_slab(const NmxSharpArgs* A, int n_items, const unsigned char* todo, hipStream_t s);
+// `kind`: the plan's choice (build_sharp).  A dense-first kind flags the items it leaves to the list kernel in A.todo.
+static void be_launch_sharp(const NmxSharpArgs& A, NmxSharpKind kind, int n_items, size_t lds, be_stream_t s) {
   be_init_once();
-  nmx_wave_launch_sharp_dense(&A, n_items, s);
-}
-static void be_launch_sharp_todo(const NmxSharpArgs& A, int n_items, size_t lds, const unsigned char* todo, be_stream_t s) {
-  be_init_once();
-  nmx_wave_launch_sharp_todo(&A, n_items, lds, todo, s);
+  switch (kind) {
+    case NMX_SHARP_LIST: nmx_wave_launch_sharp(&A, n_items, lds, s); return;
+    case NMX_SHARP_SLAB: nmx_wave_launch_sharp_slab(&A, n_items, nullptr, s); return;
+    case NMX_SHARP_DENSE_LIST: nmx_wave_launch_sharp_dense(&A, kind, n_items, s); nmx_wave_launch_sharp_todo(&A, n_items, lds, A.todo, s); return;
+    case NMX_SHARP_DENSE_SLAB: nmx_wave_launch_sharp_dense(&A, kind, n_items, s); nmx_wave_launch_sharp_slab(&A, n_items, A.todo, s); return;
+  }
 }
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
@@ -540,14 +543,13 @@ static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind kind, long
   else if (kind == NMX_HIL_W1000) nmx_wave_launch_hilbert_w1000(&A, n_items, s);
   else nmx_hilbert_fixed_launch128(&A, n_items, lds, s);
 }
-extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen, bool list_lds);
-// windows_seen: hops every sequence has absorbed before this batch (-1: always the workgroup kernel); list_lds: the one-wave
-// walk may keep its top-K list in LDS
-static void be_launch_burst_thr(const NmxBurstThrArgs& A, int n_items, int nt, size_t lds, be_stream_t s, long long windows_seen,
-                                bool list_lds) {
+extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, int nr, bool list_lds, size_t lds, hipStream_t s);
+// One segment of the walk schedule (nmx_burst_walk_schedule) that is not the fill phase's.  NMX_WALK_WAVE: the ring is full at
+// its first hop -- the barrier-free one-wave walk, its list in L2 or (g.list_lds) in LDS; else the workgroup kernel
+static void be_launch_burst_thr(const NmxBurstThrArgs& A, const NmxBurstWalk& K, const NmxBurstWalkSeg& g, int n_items, int nt, size_t lds,
+                                be_stream_t s) {
   be_init_once();
-  // ring already full at the first hop: the barrier-free one-wave walk over the list in L2
-  if (windows_seen > 0 && nmx_burst_thr_wave_ok(A, windows_seen)) { nmx_wave_launch_burst_thr(&A, n_items, s, windows_seen, list_lds); return; }
+  if (g.kind == NMX_WALK_WAVE) { nmx_wave_launch_burst_thr(&A, n_items, K.nr, g.list_lds, g.list_lds ? K.lds_list : K.lds, s); return; }
   const int chunk = (A.K + nt - 1) / nt;
   if (nt > 256) { hipLaunchKernelGGL(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_wide"); }
   else if (chunk <= 32) { hipLaunchKernelGGL(nmx_kern_burst_thr<32>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<32>"); }
@@ -571,13 +573,9 @@ static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n_items, unsigned
   hipLaunchKernelGGL(nmx_kern_burst_fill, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_lds(n2), s, A, n2, slots);
   nmxi_note_kernel("nmx_kern_burst_fill");
 }
-static void be_launch_burst_stat(const NmxBurstStatArgs& A, int n_items, size_t lds, be_stream_t s) {
+static void be_launch_burst_stat(const NmxBurstStatArgs& A, NmxBurstStatKind kind, int n_items, size_t lds, be_stream_t s) {
   be_init_once();
-  nmx_wave_launch_burst_stat(&A, n_items, lds, s);
-}
-static void be_launch_sharp(const NmxSharpArgs& A, int n_items, size_t lds, be_stream_t s) {
-  be_init_once();
-  nmx_wave_launch_sharp(&A, n_items, lds, s);
+  nmx_wave_launch_burst_stat(&A, kind, n_items, lds, s);
 }
 static void be_launch_reref(const NmxRerefArgs& A, be_stream_t s) {
   dim3 grid((unsigned)((A.T + 255) / 256), (unsigned)((A.C + NMX_REREF_ROWS - 1) / NMX_REREF_ROWS));

@@ -209,6 +209,12 @@ struct NmxTimeOscArgs {
 // the time / oscillatory and Hilbert kernels a plan launches, chosen when it is built (build_timeosc, build_hilbert)
 enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC, NMX_TO_LONG };
 enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128 };
+// the run statistics of the bursts chain (build_bursts): the envelope in the registers of a wave, 16 / 32 chunks per lane, all rows
+// or only those the Hilbert kernel stored whole (NmxBurstStatArgs::full); or the LDS kernel
+enum NmxBurstStatKind { NMX_BSTAT_REG16, NMX_BSTAT_REG16_SPARSE, NMX_BSTAT_REG32, NMX_BSTAT_REG32_SPARSE, NMX_BSTAT_GENERIC };
+// the sharp-wave launches (build_sharp): the list kernel over every item, or the compact-LDS dense launch + the list kernel over the
+// items it flagged; the list kernel's lists in LDS, or (long windows) in slabs of device memory (nmx_wave_slab.hip)
+enum NmxSharpKind { NMX_SHARP_LIST, NMX_SHARP_DENSE_LIST, NMX_SHARP_SLAB, NMX_SHARP_DENSE_SLAB };
 // the one-wave FIR kernels of one launch of a FIR stage (nmx_w64.hip), chosen where its tables are built (build_fir_stage,
 // build_bank, build_notch): M = 4096; channel pairs at M = 1536 / 1024 / 2048 (2048: bank filters, or the notch); one
 // channel per M = 2048 transform (nmx_kern_bank_w64 / _w64pp, nmx_kern_notch_w64 / _w64q / _w64qp: by batch size)

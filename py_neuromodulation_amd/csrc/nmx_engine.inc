@@ -1,5 +1,5 @@
-// nmx_engine.inc -- host side of the engine: the Plan, scratch management and the parts below (plan building:
-// nmx_engine_plan_*.inc; C ABI: nmx_engine_abi.inc, nmx_engine_run.inc, nmx_engine_norm.inc).
+// nmx_engine.inc -- host side of the engine: the Plan, scratch management and the parts below (plan building and the
+// stages' launchers: nmx_engine_plan_*.inc; C ABI: nmx_engine_abi.inc, nmx_engine_run.inc, nmx_engine_norm.inc).
 // Included by nmx_api.hip (HIP backend: the product) and by
 // tests/emu/nmx_emu.cpp (single-thread logic emulator used by the CPU-only tests).  The
 // includer provides the be_* backend (allocation, copies, launches, events).
@@ -40,12 +40,14 @@ static int nmx_fail(int code, const std::string& msg) {
 static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind, int n, int nt, size_t lds, int, be_stream_t s) { be_launch_timeosc(A, n, nt, lds, s); }
 static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind, long long n, size_t lds, be_stream_t s) { be_launch_hilbert(A, n, 128, lds, s); }
 static void be_launch_bank_w64(const NmxBankW64Args& A, int n, size_t lds, int, be_stream_t s) { be_launch_bank_w64(A, n, lds, s); }
-static void be_launch_burst_thr(const NmxBurstThrArgs& A, int n, int nt, size_t lds, be_stream_t s, long long seen, bool) {
-  be_launch_burst_thr(A, n, nt, lds, s, seen);
+static void be_launch_burst_thr(const NmxBurstThrArgs& A, const NmxBurstWalk&, const NmxBurstWalkSeg&, int n, int nt, size_t lds, be_stream_t s) {
+  be_launch_burst_thr(A, n, nt, lds, s);
 }
 static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n, unsigned short* slots, float* sorted, bool, be_stream_t s) {
   be_launch_burst_fill(A, n, slots, sorted, s);
 }
+static void be_launch_burst_stat(const NmxBurstStatArgs& A, NmxBurstStatKind, int n, size_t lds, be_stream_t s) { be_launch_burst_stat(A, n, lds, s); }
+static void be_launch_sharp(const NmxSharpArgs& A, NmxSharpKind, int n, size_t lds, be_stream_t s) { be_launch_sharp(A, n, lds, s); }
 static int be_cu_count(int) { return 256; }
 #endif
 
@@ -77,6 +79,44 @@ struct FirStage {
   std::vector<FirLaunch> launches;   // (the LDS kernels: one entry, for its stage)
   bool takes_dc = true;   // its kernels add the carried offset on load (NmxBankArgs::dcf; else run_chunk hands them a copy of
                           // the windows with the offset added back): set by fir_stage_finish
+};
+
+// The bursts chain -- Hilbert envelope (where the bank leaves band series), threshold walk, run statistics -- with its kernels
+// and its walk schedule decided at plan time (nmx_engine_plan_bursts.inc: build_hilbert, build_bursts, launch_burst_stage).
+struct BurstStage {
+  NmxHilbertArgs hil{};       // argument templates (per-call fields are patched in by launch_burst_stage)
+  NmxBurstThrArgs bthr{};
+  NmxBurstStatArgs bstat{};
+  NmxHilbertKind hil_kind = NMX_HIL_FIXED128;
+  bool own_hilbert = false;   // the bank leaves the band series (one-wave / partitioned kernels): the stand-alone Hilbert kernel runs
+  bool sparse = false;        // ... and stores a row below the threshold floor as its tail only (one-wave kernels; NMX_BURST_ENV_SPARSE)
+  bool sparse_count = false;  // ... = 2: and every chunk's flags are read back and counted (nmx_last_kernels(4) reports them)
+  long long env_tail_rows = 0, env_rows = 0;
+  NmxBurstStatKind stat_kind = NMX_BSTAT_GENERIC;
+  NmxBurstWalk walk{};        // the walk's schedule constants (nmx_k_bursts.h; NMX_THR_FILL, NMX_THR_WAVE, NMX_THR_LIST_LDS)
+  bool fill_split = true;     // the fill phase as two launches (sort, one-wave walk; NMX_FILL_SPLIT)
+  int nt_thr = 256;           // threads of the workgroup walk
+  // state
+  long long seen = 0;         // host mirror of the per-sequence window counter (all sequences advance together)
+  float* d_top = nullptr;
+  long long* d_counts = nullptr;
+  size_t top_bytes = 0, counts_bytes = 0;
+  float* d_floor = nullptr;   // [C][Bb] lower bound of each sequence's future thresholds (NmxBurstThrArgs::floor): derived from the
+                              // state, never exported; -INFINITY whenever the state is new to this plan
+  // hand-off
+  Buf env[2], thr[2];         // read on the side stream: one set per chunk parity
+  Buf env_full[2];            // ... and which rows of env[] are whole (NmxHilbertArgs::full), with it
+  Buf yb;                     // band series for the stand-alone Hilbert kernel (exists once)
+  Buf slots;                  // scratch of the fill phase
+  // a fresh stream sorts the whole fill phase at once (nmx_k_burst_fill.h): how many of `nw` hops that takes, else 0
+  int fill_hops(int nw) const { return walk.fill && seen == 0 ? nmx_burst_fill_hops(bthr, nw) : 0; }
+};
+// The sharp-wave analysis, its launches decided at plan time (nmx_engine_plan_state.inc: build_sharp, launch_sharp_stage).
+struct SharpStage {
+  NmxSharpArgs a{};           // argument template
+  NmxSharpKind kind = NMX_SHARP_LIST;
+  Buf swy[2], todo[2];        // filtered series and the dense launch's flags: read on a side stream, one set per chunk parity
+  Buf slab;                   // list slabs of the long-window kinds (one stream runs every sharp-wave launch of a plan)
 };
 
 struct Plan {
@@ -122,13 +162,10 @@ struct Plan {
                                       // spectrum in LDS as well, one exchange tile fewer -- kept for measurement)
   std::vector<FirStage> pre;          // preprocessing_filter stages (one filter each)
   const float* w64e_tw = nullptr;     // twiddles of the M = 2048 channel-pair kernel (nmx_k_bank_w64e.h): notch and bank
-  NmxHilbertArgs hil{};
-  NmxHilbertKind hil_kind = NMX_HIL_FIXED128;
   const float* w500_tab = nullptr;
-  NmxBurstThrArgs bthr{};
-  NmxBurstStatArgs bstat{};
+  BurstStage bursts;                  // bursts chain: behind the bank
   bool have_bursts = false;
-  NmxSharpArgs sharp{};
+  SharpStage sharp;                   // sharp-wave analysis: likewise
   bool have_sharp = false;
   NmxCohArgs coh{};        // coherence between channel pairs (nmx_k_coh.h)
   bool have_coh = false;
@@ -137,35 +174,17 @@ struct Plan {
   float car_diag = 0.f, car_off = 0.f;
   bool rs_ok = false;    // taps + group-sum structure found in R (nmx_k_prep.h: NmxRerefStructArgs)
   NmxRerefStructArgs rst{};
-  int nt_timeosc = 64, nt_bank = 256, nt_thr = 256;
+  int nt_timeosc = 64, nt_bank = 256;
   int chunk_windows = 1024;
-  bool sharp_dense_first = false;   // compact-LDS dense launch + generic launch over the flagged items
-  bool thr_wave = true;             // one-wave threshold walk once the burst ring is full (nmx_k_bursts.h)
-  bool thr_fill = true;             // fresh stream: sort-once walk of the fill phase (nmx_k_burst_fill.h) ...
-  bool fill_split = true;           // ... as two launches (sort, one-wave walk)
-  bool thr_list_lds = true;         // the one-wave walk may keep its top-K list in LDS while the stream is young
-  bool env_sparse = true;           // the one-wave Hilbert kernels store a row below the threshold floor as its tail only (NMX_BURST_ENV_SPARSE)
-  bool env_sparse_count = false;    // ... = 2: and every chunk's flags are read back and counted (nmx_last_kernels(4) reports them)
-  long long env_tail_rows = 0, env_rows = 0;
   bool tiny_inline = true;          // host batches of a few hops on ONE stream (nmx_engine_run.inc)
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
-  long long burst_windows_seen = 0; // host mirror of the per-sequence window counter (all sequences advance together)
   // scratch
-  Buf thr_slots;
   Buf to_todo;        // flags of the matrix-pipe spectrum kernel (NmxTimeOscArgs::todo)
   Buf rn_qt, rn_qn;   // raw "quantile" tables / "power" parameters of a chunk
   Buf tap;            // pre-processed windows of a chunk on their way to a host caller (nmx_process_batch_tap)
-  Buf x_in, x_in2[2], x_ref, x_rs, x_rn, rn_mean, rn_scale, x_pf[2], y_notch, yb, out, starts, mask;
+  Buf x_in, x_in2[2], x_ref, x_rs, x_rn, rn_mean, rn_scale, x_pf[2], y_notch, out, starts, mask;
   Buf win_pin;        // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
-  Buf env[2], swy[2], thr[2], sw_todo[2];   // read on the side streams: one set per chunk parity
-  Buf env_full[2];    // ... and which rows of env[] are whole (NmxHilbertArgs::full), with it
-  Buf sw_slab;        // list slabs of the long-window sharp-wave kernel (one stream runs every sharp-wave launch of a plan)
   // state
-  float* d_top = nullptr;
-  long long* d_counts = nullptr;
-  size_t top_bytes = 0, counts_bytes = 0;
-  float* d_floor = nullptr;   // [C][Bb] lower bound of each sequence's future thresholds (NmxBurstThrArgs::floor): derived from the
-                              // state, never exported; -INFINITY whenever the state is new to this plan
   NmxKalmanArgs kal{};
   bool have_kalman = false;
   NmxResampleArgs rs{};
@@ -239,6 +258,7 @@ int env_int(const char* name, int dflt) {
 }
 
 #include "nmx_engine_plan_spectral.inc"
+#include "nmx_engine_plan_bursts.inc"
 #include "nmx_engine_plan_fir.inc"
 #include "nmx_engine_plan_state.inc"
 #include "nmx_engine_dc.inc"

@@ -16,11 +16,10 @@ int nmx_plan_destroy(nmx_plan* plan) {
   be_sync(P->stream_d);
   be_sync(P->stream_f);
   for (void* t : P->tables) be_free(t);
-  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->thr_slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sw_todo[0], &P->sw_todo[1], &P->sw_slab, &P->y_notch, &P->env[0], &P->env[1], &P->env_full[0], &P->env_full[1], &P->swy[0], &P->swy[1], &P->yb, &P->thr[0], &P->thr[1], &P->out, &P->starts, &P->mask})
+  for (Buf* b : {&P->tap, &P->rn_qt, &P->rn_qn, &P->bursts.slots, &P->to_todo, &P->x_dc, &P->x_in, &P->x_ref, &P->x_rs, &P->x_rn, &P->rn_mean, &P->rn_scale, &P->x_pf[0], &P->x_pf[1], &P->sharp.todo[0], &P->sharp.todo[1], &P->sharp.slab, &P->y_notch, &P->bursts.env[0], &P->bursts.env[1], &P->bursts.env_full[0], &P->bursts.env_full[1], &P->sharp.swy[0], &P->sharp.swy[1], &P->bursts.yb, &P->bursts.thr[0], &P->bursts.thr[1], &P->out, &P->starts, &P->mask})
     if (b->p) be_free(b->p);
-  if (P->d_top) be_free(P->d_top);
-  if (P->d_counts) be_free(P->d_counts);
-  if (P->d_floor) be_free(P->d_floor);
+  for (void* p : {(void*)P->bursts.d_top, (void*)P->bursts.d_counts, (void*)P->bursts.d_floor})
+    if (p) be_free(p);
   if (P->d_R) be_free(P->d_R);
   if (P->d_dc_sub) be_free(P->d_dc_sub);
   if (P->d_dc_pref) be_free(P->d_dc_pref);
@@ -167,11 +166,6 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   }
   P->nt_timeosc = desc->window <= 1024 ? 128 : 256;
   P->nt_bank = 256;
-  P->nt_thr = 256;
-  P->thr_wave = env_int("NMX_THR_WAVE", 1) != 0;
-  P->thr_fill = env_int("NMX_THR_FILL", 1) != 0;
-  P->fill_split = env_int("NMX_FILL_SPLIT", 1) != 0;
-  P->thr_list_lds = env_int("NMX_THR_LIST_LDS", 1) != 0;
   P->tiny_inline = env_int("NMX_TINY_INLINE", 1) != 0;
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
@@ -255,6 +249,7 @@ int nmx_plan_n_outputs(const nmx_plan* plan, int64_t* n) {
 static size_t rn_state_bytes_cap(const Plan& P, long long cap) {
   return 2 * sizeof(long long) + (size_t)P.d.n_channels * (size_t)cap * sizeof(float) + P.rn_cnt_bytes + P.rn_len_bytes;
 }
+static size_t burst_state_bytes(const Plan& P) { return P.bursts.top_bytes + P.bursts.counts_bytes; }   // burst ring | counts
 static size_t rn_state_bytes(const Plan& P) { return P.have_rawnorm ? rn_state_bytes_cap(P, P.rn.cap) : 0; }
 
 int nmx_state_reset(nmx_plan* plan) {
@@ -270,10 +265,11 @@ int nmx_state_reset(nmx_plan* plan) {
   be_sync(P->stream_f);
   if (P->have_rawnorm) rawnorm_reset(*P);
   if (P->have_bursts) {
-    be_memset_sync(P->d_top, 0, P->top_bytes);
-    be_memset_sync(P->d_counts, 0, P->counts_bytes);
+    BurstStage& B = P->bursts;
+    be_memset_sync(B.d_top, 0, B.top_bytes);
+    be_memset_sync(B.d_counts, 0, B.counts_bytes);
     burst_floor_reset(*P);
-    P->burst_windows_seen = 0;
+    B.seen = 0;
   }
   if (P->have_kalman) kalman_reset(*P);
   return 0;
@@ -282,28 +278,28 @@ int nmx_state_reset(nmx_plan* plan) {
 int nmx_state_size(const nmx_plan* plan, int64_t* n_bytes) {
   const Plan* P = (const Plan*)plan;
   if (!P || !n_bytes) return nmx_fail(NMX_E_INVALID, "null argument");
-  *n_bytes = (int64_t)(P->top_bytes + P->counts_bytes + P->kf_bytes + dc_state_bytes(*P) + rn_state_bytes(*P));   // burst ring | counts | Kalman | offsets | raw normaliser
+  *n_bytes = (int64_t)(burst_state_bytes(*P) + P->kf_bytes + dc_state_bytes(*P) + rn_state_bytes(*P));   // burst ring | counts | Kalman | offsets | raw normaliser
   return 0;
 }
 
 int nmx_state_export(nmx_plan* plan, void* dst, int64_t n_bytes) {
   Plan* P = (Plan*)plan;
   if (!P || (!dst && n_bytes)) return nmx_fail(NMX_E_INVALID, "null argument");
-  NMX_REQUIRE((size_t)n_bytes == P->top_bytes + P->counts_bytes + P->kf_bytes + dc_state_bytes(*P) + rn_state_bytes(*P), "state size mismatch");
+  NMX_REQUIRE((size_t)n_bytes == burst_state_bytes(*P) + P->kf_bytes + dc_state_bytes(*P) + rn_state_bytes(*P), "state size mismatch");
   if (!n_bytes) return 0;
-  dc_state_export(*P, (char*)dst + P->top_bytes + P->counts_bytes + P->kf_bytes);   // (never next to a raw normaliser)
+  dc_state_export(*P, (char*)dst + burst_state_bytes(*P) + P->kf_bytes);   // (never next to a raw normaliser)
   be_set_device(P->device);
   be_sync(P->stream);
   if (P->last_stream && P->last_stream != P->stream) be_sync(P->last_stream);   // batch launched on a caller's stream
   be_sync(P->stream_b);
   be_sync(P->stream_f);
   if (P->have_bursts) {
-    be_d2h_sync(dst, P->d_top, P->top_bytes);
-    be_d2h_sync((char*)dst + P->top_bytes, P->d_counts, P->counts_bytes);
+    be_d2h_sync(dst, P->bursts.d_top, P->bursts.top_bytes);
+    be_d2h_sync((char*)dst + P->bursts.top_bytes, P->bursts.d_counts, P->bursts.counts_bytes);
   }
-  if (P->have_kalman) be_d2h_sync((char*)dst + P->top_bytes + P->counts_bytes, P->d_kf, P->kf_bytes);
+  if (P->have_kalman) be_d2h_sync((char*)dst + burst_state_bytes(*P), P->d_kf, P->kf_bytes);
   if (P->have_rawnorm) {
-    char* q = (char*)dst + P->top_bytes + P->counts_bytes + P->kf_bytes;
+    char* q = (char*)dst + burst_state_bytes(*P) + P->kf_bytes;
     const long long cap = P->rn.cap;
     memcpy(q, &P->rn_hops, sizeof(long long)); q += sizeof(long long);
     memcpy(q, &cap, sizeof(long long)); q += sizeof(long long);
@@ -317,28 +313,29 @@ int nmx_state_export(nmx_plan* plan, void* dst, int64_t n_bytes) {
 int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes) {
   Plan* P = (Plan*)plan;
   if (!P || (!src && n_bytes)) return nmx_fail(NMX_E_INVALID, "null argument");
-  const size_t fixed = P->top_bytes + P->counts_bytes + P->kf_bytes + dc_state_bytes(*P);
+  const size_t fixed = burst_state_bytes(*P) + P->kf_bytes + dc_state_bytes(*P);
   long long src_cap = P->have_rawnorm ? P->rn.cap : 0;
   if (P->have_rawnorm && (size_t)n_bytes >= fixed + 2 * sizeof(long long))   // the exporting plan's ring capacity
     memcpy(&src_cap, (const char*)src + fixed + sizeof(long long), sizeof(long long));
   NMX_REQUIRE(!P->have_rawnorm || (src_cap > 0 && src_cap < (1ll << 31)), "state blob: bad raw-normaliser header");
   NMX_REQUIRE((size_t)n_bytes == fixed + (P->have_rawnorm ? rn_state_bytes_cap(*P, src_cap) : 0), "state size mismatch");
   if (!n_bytes) return 0;
-  dc_state_import(*P, (const char*)src + P->top_bytes + P->counts_bytes + P->kf_bytes);
+  dc_state_import(*P, (const char*)src + burst_state_bytes(*P) + P->kf_bytes);
   be_set_device(P->device);
   be_sync(P->stream);
   if (P->last_stream && P->last_stream != P->stream) be_sync(P->last_stream);
   be_sync(P->stream_b);
   be_sync(P->stream_f);
   if (P->have_bursts) {
-    be_h2d_sync(P->d_top, src, P->top_bytes);
-    be_h2d_sync(P->d_counts, (const char*)src + P->top_bytes, P->counts_bytes);
-    memcpy(&P->burst_windows_seen, (const char*)src + P->top_bytes + sizeof(long long), sizeof(long long));   // counts[0][1]
+    BurstStage& B = P->bursts;
+    be_h2d_sync(B.d_top, src, B.top_bytes);
+    be_h2d_sync(B.d_counts, (const char*)src + B.top_bytes, B.counts_bytes);
+    memcpy(&B.seen, (const char*)src + B.top_bytes + sizeof(long long), sizeof(long long));   // counts[0][1]
     burst_floor_reset(*P);   // (a bound of the history this plan had, not of the imported one: the next steady walk writes it anew)
   }
-  if (P->have_kalman) be_h2d_sync(P->d_kf, (const char*)src + P->top_bytes + P->counts_bytes, P->kf_bytes);
+  if (P->have_kalman) be_h2d_sync(P->d_kf, (const char*)src + burst_state_bytes(*P), P->kf_bytes);
   if (P->have_rawnorm) {
-    const char* q = (const char*)src + P->top_bytes + P->counts_bytes + P->kf_bytes;
+    const char* q = (const char*)src + burst_state_bytes(*P) + P->kf_bytes;
     memcpy(&P->rn_hops, q, sizeof(long long)); q += 2 * sizeof(long long);
     const int C = P->d.n_channels, cap = P->rn.cap;
     const float* ring_src = (const float*)q;

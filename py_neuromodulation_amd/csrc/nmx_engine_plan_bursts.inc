@@ -1,0 +1,221 @@
+// nmx_engine_plan_bursts.inc -- the bursts chain as a stage: its plan-time choices (build_hilbert, build_bursts) and its launch
+// sequence for one chunk (launch_burst_stage).  Included by nmx_engine.inc.
+
+// the stand-alone Hilbert kernel of a bank that leaves its burst bands as series (build_bank calls this)
+int build_hilbert(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  NmxHilbertArgs& H = P.bursts.hil;
+  H.W = d.window;
+  H.hil_full = d.window & 1;
+  int rc;
+  if ((rc = build_fft(P, H.hil_full ? d.window : d.window / 2, &H.hil_r, true))) return rc;
+  if ((rc = build_fft(P, d.window, &H.hil_c, true))) return rc;
+  H.off_a = 0;
+  if (H.hil_full) {
+    H.off_b = al4(2 * d.window);
+    H.off_y = H.off_b;
+    H.lds_floats = H.off_b + al4(2 * d.window);
+  } else {   // even W: two half-length complex buffers (W / 2 + 1 bins) + a copy of the series
+    H.off_b = al4(d.window + 2);
+    H.off_y = H.off_b + al4(d.window + 2);
+    H.lds_floats = H.off_y + al4(d.window);
+  }
+  NMX_REQUIRE(H.lds_floats * 4 <= 160 * 1024, "window too long for the Hilbert kernel");
+  H.w500_tab = nullptr;
+  H.w1000_tab = nullptr;
+  if (d.window == 1000) {
+    if ((rc = build_w500_tab(P))) return rc;
+    H.w500_tab = P.w500_tab;
+  }
+#ifndef NMX_HOST_EMU
+  if (d.window == 2000) {   // tables of the 1000-point wave-level transform (layout: nmx_k_fft500.h)
+    std::vector<float> t(NMX_W1000_TAB_FLOATS);
+    auto put = [&](int i, double ang, double scale) {
+      t[2 * i] = (float)(scale * std::cos(ang));
+      t[2 * i + 1] = (float)(scale * std::sin(ang));
+    };
+    for (int lane = 0; lane < 64; ++lane) {
+      const int l = lane < 50 ? lane : 0, k = l % 10;
+      for (int r = 1; r < 10; ++r) {
+        put((r - 1) * 64 + lane, -2.0 * kPi * ((10 * k * r) % 1000) / 1000.0, 1.0);
+        put((8 + r) * 64 + lane, -2.0 * kPi * ((l * r) % 1000) / 1000.0, 1.0);
+        put((17 + r) * 64 + lane, -2.0 * kPi * (((l + 50) * r) % 1000) / 1000.0, 1.0);
+      }
+    }
+    for (int k = 0; k < NMX_W1000_CS_N; ++k) put(NMX_W1000_TW_N + k, 2.0 * kPi * k / 2000.0, k ? 2.0 / 2000.0 : 0.0);
+    H.w1000_tab = (const float*)upload(P, t.data(), t.size() * sizeof(float));
+    if (!H.w1000_tab) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+  }
+#endif
+  // the kernel (be_launch_hilbert): one wave per series at W = 1000 / 2000, else the 128-thread workgroup kernel
+  const bool wave = env_int("NMX_HILBERT_W500", 1) != 0;
+  P.bursts.hil_kind = wave && d.window == 1000 ? NMX_HIL_W500 : wave && H.w1000_tab ? NMX_HIL_W1000 : NMX_HIL_FIXED128;
+  return 0;
+}
+
+// no bound for any sequence: plan creation, state reset, state import (the caller has drained the plan's streams)
+void burst_floor_reset(Plan& P) {
+  const std::vector<float> f((size_t)P.d.n_channels * P.d.n_burst_bands, -INFINITY);
+  be_h2d_sync(P.bursts.d_floor, f.data(), f.size() * sizeof(float));
+}
+
+int build_bursts(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  if (!(d.features & NMX_F_BURSTS)) return 0;
+  NMX_REQUIRE(d.n_burst_bands > 0, "bursts enabled without burst bands");
+  int nb = 0;
+  for (int i = 0; i < d.n_filters; ++i) nb += d.filters[i].burst_index >= 0;
+  NMX_REQUIRE(nb == d.n_burst_bands, "every burst band needs exactly one filter");
+  BurstStage& B = P.bursts;
+  NmxBurstThrArgs& T = B.bthr;
+  T.n_channels = d.n_channels;
+  T.n_bands = d.n_burst_bands;
+  T.W = d.window;
+  T.q = d.burst_threshold / 100.0;
+  NMX_REQUIRE(T.q >= 0.0 && T.q <= 1.0, "burst threshold must be a percentile in [0, 100]");
+  T.n_ring = (int)(d.sfreq * d.burst_time_duration_s);
+  NMX_REQUIRE(T.n_ring >= 2, "burst ring buffer too short");
+  const double seg_s = d.segment_length_s > 0 ? d.segment_length_s : (double)d.window / d.sfreq;  // segment_length_features_ms / 1000
+  T.overlap = (int)(d.sfreq * seg_s / d.feat_hz);
+  // samples_overlap = 0 (30 kHz, 17 ms windows at a 1 kHz feature rate: int(0.51)): the reference's slice
+  // filtered_data[:, :, -0:] is the WHOLE window -- every hop appends all W envelope samples (features/bursts.py:155-166)
+  // samples_overlap > W (a 16 kHz recording resampled to 1000-sample windows with the raw-rate design): the slice
+  // filtered_data[:, :, -1600:] of a 1000-sample array is the whole window as well
+  if (T.overlap == 0 || T.overlap > d.window) T.overlap = d.window;
+  NMX_REQUIRE(T.overlap >= 1 && T.overlap <= d.window, "burst overlap (sfreq * seg_s / feat_hz) out of range");
+  T.K = (int)std::floor((1.0 - T.q) * (double)(T.n_ring - 1)) + 2;
+  T.K = std::min(T.K, T.n_ring);
+  int p2 = 1;
+  while (p2 < std::max(std::max(d.window, T.overlap) + 4, 1024)) p2 <<= 1;   // >= NMX_THR_P (flush staging)
+  T.P2 = p2;
+  // NMX_THR_LIST_GLOBAL=1: the sorted top-K list is not copied to LDS (workgroups of ~20 KB instead of
+  // ~50 KB leave room for the kernels that run next to the walk); every list access then goes to L2
+  // It is also the fallback when the list does not fit (2 kHz x 30 s at the 50th percentile: 30 001 entries).
+  T.list_in_global = env_int("NMX_THR_LIST_GLOBAL", 0);
+  for (int pass = 0; pass < 2; ++pass) {
+    T.off_l0 = 0;
+    T.off_l1 = 0;                          // (single list: the merge is in place)
+    T.off_p = T.list_in_global ? 0 : al4(T.K);   // pc[P2], ps[P2], ins[P2]
+    T.off_red = T.off_p + 3 * p2 + 2 * 512 + 1024 + 8;   // + fringe x2, pending list, counters
+    T.lds_floats = T.off_red + 64;
+    if (T.lds_floats * 4 <= 160 * 1024 || T.list_in_global) break;
+    T.list_in_global = 1;
+  }
+  if ((T.K + B.nt_thr - 1) / B.nt_thr > 128) B.nt_thr = 1024;   // nmx_kern_burst_thr_wide: 64 entries per thread
+  NMX_REQUIRE((T.K + B.nt_thr - 1) / B.nt_thr <= (B.nt_thr > 256 ? 64 : 128), "burst top-K list too long for the merge kernel "
+              "(sfreq x time_duration_s x (1 - threshold / 100) > 65 536 samples)");
+  NMX_REQUIRE(T.lds_floats * 4 <= 160 * 1024,
+              "burst threshold state does not fit in 160 KiB LDS (ring x (1 - q) too large)");
+  NmxBurstStatArgs& S = B.bstat;
+  S.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
+  S.n_channels = d.n_channels;
+  S.n_bands = d.n_burst_bands;
+  S.W = d.window;
+  S.sfreq = (float)d.sfreq;
+  S.seg_s = (float)seg_s;
+  S.out_mask = d.burst_out_mask;
+  S.cols = cv(d.burst_cols);
+  S.off_e = 0;
+  S.off_red = al4(d.window + d.window / 16 + 1);   // padded series (NMX_EP)
+  S.lds_floats = S.off_red + 64;
+  const size_t n_state = (size_t)d.n_channels * d.n_burst_bands;
+  B.top_bytes = n_state * T.K * sizeof(float);
+  B.counts_bytes = n_state * 2 * sizeof(long long);
+  B.d_top = (float*)be_alloc(B.top_bytes);
+  B.d_counts = (long long*)be_alloc(B.counts_bytes);
+  B.d_floor = (float*)be_alloc(n_state * sizeof(float));
+  if (!B.d_top || !B.d_counts || !B.d_floor) return nmx_fail(NMX_E_NOMEM, "burst state allocation failed");
+  be_memset_sync(B.d_top, 0, B.top_bytes);
+  be_memset_sync(B.d_counts, 0, B.counts_bytes);
+  burst_floor_reset(P);
+  // ---- the chain's kernels and the walk's schedule (launch_burst_stage only dispatches on them) ----
+  B.own_hilbert = P.bank.w64 || P.bank.a.partitioned;   // (build_bank, which ran before, has called build_hilbert for it)
+  B.fill_split = env_int("NMX_FILL_SPLIT", 1) != 0;
+  bool wave = env_int("NMX_THR_WAVE", 1) != 0;
+#ifdef NMX_HOST_EMU   // (the emulator runs the item code of the workgroup walk and the generic Hilbert item, which stores every row)
+  wave = false;
+#else
+  const int sparse = env_int("NMX_BURST_ENV_SPARSE", 1);
+  B.sparse = sparse != 0 && B.own_hilbert && (B.hil_kind == NMX_HIL_W500 || B.hil_kind == NMX_HIL_W1000);
+  B.sparse_count = sparse == 2;
+#endif
+  B.walk = nmx_burst_walk_plan(T, env_int("NMX_THR_FILL", 1) != 0, wave, env_int("NMX_THR_LIST_LDS", 1) != 0);
+  B.stat_kind = (d.window & 3) || d.window > 2048 ? NMX_BSTAT_GENERIC
+                : d.window <= 1024 ? (B.sparse ? NMX_BSTAT_REG16_SPARSE : NMX_BSTAT_REG16)
+                                   : (B.sparse ? NMX_BSTAT_REG32_SPARSE : NMX_BSTAT_REG32);
+  P.have_bursts = true;
+  return 0;
+}
+
+// The bursts chain of one chunk (nw hops, parity `par`) behind the bank on the main stream `s`: Hilbert envelope, threshold walk,
+// run statistics.  Its sequential, latency-bound part (walk -> run statistics: a few waves) runs on the high-priority side
+// stream stream_b next to the throughput kernels that follow on `s` (NMX_OVERLAP >= 2; 1: Hilbert too; 0: one stream), and
+// ev_join[par] marks its end.
+static int launch_burst_stage(Plan& P, int par, int nw, float* d_out, be_stream_t s, bool tev) {
+  BurstStage& B = P.bursts;
+  const int n_seq = P.d.n_channels * P.d.n_burst_bands, W = P.d.window;
+  Buf& B_env = B.env[par];
+  Buf& B_thr = B.thr[par];
+  int rc;
+  if ((rc = ensure(B_thr, (size_t)nw * n_seq * sizeof(float)))) return rc;
+  be_stream_t sb = s;
+  auto fork = [&]() {
+    sb = P.stream_b;
+    be_event_record(P.ev_fork, s);
+    be_stream_wait(sb, P.ev_fork);
+  };
+  if (P.overlap == 1) fork();
+  if (tev) be_timer_start(P.timers[4], sb);
+  const unsigned char* env_full = nullptr;
+  if (B.own_hilbert) {
+    NmxHilbertArgs H = B.hil;
+    H.y = (const float*)B.yb.p; H.env = (float*)B_env.p;
+    // Rows that cannot reach their threshold leave only the tail the walk reads (B.sparse).
+    // No event orders this launch behind the previous chunk's walk, which may still run on the side stream: the kernel
+    // reads whatever floor is there.  That is safe because EVERY value ever stored there -- -INFINITY, or the s[lo] some
+    // finished walk of this state left -- is a lower bound of all thresholds of the hops behind that walk, this chunk's
+    // included (NmxBurstThrArgs::floor); a 4-byte store is seen whole or not at all.  State reset / import drain the
+    // streams before they put -INFINITY back.
+    if (B.sparse) {
+      if ((rc = ensure(B.env_full[par], (size_t)nw * n_seq))) return rc;
+      H.floor = B.d_floor; H.full = (unsigned char*)B.env_full[par].p;
+      H.n_seq = n_seq; H.overlap = B.bthr.overlap;
+      env_full = H.full;
+    }
+    be_launch_hilbert(H, B.hil_kind, (long long)nw * n_seq, (size_t)H.lds_floats * 4, sb);
+    if (env_full && B.sparse_count) {   // NMX_BURST_ENV_SPARSE=2 (tests, measurements): read the flags back, at the price of a sync
+      std::vector<unsigned char> f((size_t)nw * n_seq);
+      if ((rc = be_sync(sb))) return rc;
+      be_d2h_sync(f.data(), env_full, f.size());
+      for (unsigned char v : f) B.env_tail_rows += v == 0;
+      B.env_rows += (long long)f.size();
+    }
+  }
+  if (P.overlap >= 2) fork();
+  NmxBurstThrArgs T = B.bthr;
+  T.top = B.d_top; T.counts = B.d_counts; T.floor = B.d_floor;
+  NmxBurstWalkSeg seg[3];
+  const int n_seg = nmx_burst_walk_schedule(B.walk, T, B.seen, nw, seg);
+  for (int i = 0; i < n_seg; ++i) {
+    const NmxBurstWalkSeg& g = seg[i];
+    T.env = (const float*)B_env.p + (size_t)g.first * n_seq * W;
+    T.thr = (float*)B_thr.p + (size_t)g.first * n_seq;
+    T.n_windows = g.n;
+    if (g.kind == NMX_WALK_FILL) {   // scratch: the 16-bit slot of every sample, per sequence, and (two-launch form) the sorted samples
+      const size_t n_slot = (size_t)n_seq * NMX_FILL_MAX;
+      if ((rc = ensure(B.slots, n_slot * (sizeof(unsigned short) + sizeof(float))))) return rc;
+      float* sorted = (float*)B.slots.p;   // (the floats first: 4-byte aligned whatever n_slot)
+      be_launch_burst_fill(T, n_seq, (unsigned short*)(sorted + n_slot), sorted, B.fill_split, sb);
+    } else {
+      be_launch_burst_thr(T, B.walk, g, n_seq, B.nt_thr, (size_t)T.lds_floats * 4, sb);
+    }
+  }
+  B.seen += nw;
+  NmxBurstStatArgs S = B.bstat;
+  S.env = (const float*)B_env.p; S.thr = (const float*)B_thr.p; S.out = d_out; S.n_windows = nw;
+  S.full = env_full;
+  be_launch_burst_stat(S, B.stat_kind, nw * n_seq, (size_t)S.lds_floats * 4, sb);
+  if (tev) be_timer_stop(P.timers[4], sb);
+  if (P.overlap) be_event_record(P.ev_join[par], sb);
+  return 0;
+}

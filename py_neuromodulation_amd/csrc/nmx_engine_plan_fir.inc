@@ -260,57 +260,6 @@ static void launch_notch_bank_fused(Plan& P, const NmxBankArgs& An, const NmxBan
 }
 #endif
 
-int build_hilbert(Plan& P) {
-  const nmx_plan_desc& d = P.d;
-  NmxHilbertArgs& H = P.hil;
-  H.W = d.window;
-  H.hil_full = d.window & 1;
-  int rc;
-  if ((rc = build_fft(P, H.hil_full ? d.window : d.window / 2, &H.hil_r, true))) return rc;
-  if ((rc = build_fft(P, d.window, &H.hil_c, true))) return rc;
-  H.off_a = 0;
-  if (H.hil_full) {
-    H.off_b = al4(2 * d.window);
-    H.off_y = H.off_b;
-    H.lds_floats = H.off_b + al4(2 * d.window);
-  } else {   // even W: two half-length complex buffers (W / 2 + 1 bins) + a copy of the series
-    H.off_b = al4(d.window + 2);
-    H.off_y = H.off_b + al4(d.window + 2);
-    H.lds_floats = H.off_y + al4(d.window);
-  }
-  NMX_REQUIRE(H.lds_floats * 4 <= 160 * 1024, "window too long for the Hilbert kernel");
-  H.w500_tab = nullptr;
-  H.w1000_tab = nullptr;
-  if (d.window == 1000) {
-    if ((rc = build_w500_tab(P))) return rc;
-    H.w500_tab = P.w500_tab;
-  }
-#ifndef NMX_HOST_EMU
-  if (d.window == 2000) {   // tables of the 1000-point wave-level transform (layout: nmx_k_fft500.h)
-    std::vector<float> t(NMX_W1000_TAB_FLOATS);
-    auto put = [&](int i, double ang, double scale) {
-      t[2 * i] = (float)(scale * std::cos(ang));
-      t[2 * i + 1] = (float)(scale * std::sin(ang));
-    };
-    for (int lane = 0; lane < 64; ++lane) {
-      const int l = lane < 50 ? lane : 0, k = l % 10;
-      for (int r = 1; r < 10; ++r) {
-        put((r - 1) * 64 + lane, -2.0 * kPi * ((10 * k * r) % 1000) / 1000.0, 1.0);
-        put((8 + r) * 64 + lane, -2.0 * kPi * ((l * r) % 1000) / 1000.0, 1.0);
-        put((17 + r) * 64 + lane, -2.0 * kPi * (((l + 50) * r) % 1000) / 1000.0, 1.0);
-      }
-    }
-    for (int k = 0; k < NMX_W1000_CS_N; ++k) put(NMX_W1000_TW_N + k, 2.0 * kPi * k / 2000.0, k ? 2.0 / 2000.0 : 0.0);
-    H.w1000_tab = (const float*)upload(P, t.data(), t.size() * sizeof(float));
-    if (!H.w1000_tab) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  }
-#endif
-  // the kernel (be_launch_hilbert): one wave per series at W = 1000 / 2000, else the 128-thread workgroup kernel
-  const bool wave = env_int("NMX_HILBERT_W500", 1) != 0;
-  P.hil_kind = wave && d.window == 1000 ? NMX_HIL_W500 : wave && H.w1000_tab ? NMX_HIL_W1000 : NMX_HIL_FIXED128;
-  return 0;
-}
-
 int choose_M(int need) {
   int M = need + (need & 1);
   while (!smooth5(M / 2)) M += 2;

@@ -112,90 +112,6 @@ int build_prefilters(Plan& P) {
   return 0;
 }
 
-// no bound for any sequence: plan creation, state reset, state import (the caller has drained the plan's streams)
-void burst_floor_reset(Plan& P) {
-  const std::vector<float> f((size_t)P.d.n_channels * P.d.n_burst_bands, -INFINITY);
-  be_h2d_sync(P.d_floor, f.data(), f.size() * sizeof(float));
-}
-
-int build_bursts(Plan& P) {
-  const nmx_plan_desc& d = P.d;
-  if (!(d.features & NMX_F_BURSTS)) return 0;
-  NMX_REQUIRE(d.n_burst_bands > 0, "bursts enabled without burst bands");
-  int nb = 0;
-  for (int i = 0; i < d.n_filters; ++i) nb += d.filters[i].burst_index >= 0;
-  NMX_REQUIRE(nb == d.n_burst_bands, "every burst band needs exactly one filter");
-  NmxBurstThrArgs& T = P.bthr;
-  T.n_channels = d.n_channels;
-  T.n_bands = d.n_burst_bands;
-  T.W = d.window;
-  T.q = d.burst_threshold / 100.0;
-  NMX_REQUIRE(T.q >= 0.0 && T.q <= 1.0, "burst threshold must be a percentile in [0, 100]");
-  T.n_ring = (int)(d.sfreq * d.burst_time_duration_s);
-  NMX_REQUIRE(T.n_ring >= 2, "burst ring buffer too short");
-  const double seg_s = d.segment_length_s > 0 ? d.segment_length_s : (double)d.window / d.sfreq;  // segment_length_features_ms / 1000
-  T.overlap = (int)(d.sfreq * seg_s / d.feat_hz);
-  // samples_overlap = 0 (30 kHz, 17 ms windows at a 1 kHz feature rate: int(0.51)): the reference's slice
-  // filtered_data[:, :, -0:] is the WHOLE window -- every hop appends all W envelope samples (features/bursts.py:155-166)
-  // samples_overlap > W (a 16 kHz recording resampled to 1000-sample windows with the raw-rate design): the slice
-  // filtered_data[:, :, -1600:] of a 1000-sample array is the whole window as well
-  if (T.overlap == 0 || T.overlap > d.window) T.overlap = d.window;
-  NMX_REQUIRE(T.overlap >= 1 && T.overlap <= d.window, "burst overlap (sfreq * seg_s / feat_hz) out of range");
-  T.K = (int)std::floor((1.0 - T.q) * (double)(T.n_ring - 1)) + 2;
-  T.K = std::min(T.K, T.n_ring);
-  int p2 = 1;
-  while (p2 < std::max(std::max(d.window, T.overlap) + 4, 1024)) p2 <<= 1;   // >= NMX_THR_P (flush staging)
-  T.P2 = p2;
-  // NMX_THR_LIST_GLOBAL=1: the sorted top-K list is not copied to LDS (workgroups of ~20 KB instead of
-  // ~50 KB leave room for the kernels that run next to the walk); every list access then goes to L2
-  // It is also the fallback when the list does not fit (2 kHz x 30 s at the 50th percentile: 30 001 entries).
-  T.list_in_global = env_int("NMX_THR_LIST_GLOBAL", 0);
-  for (int pass = 0; pass < 2; ++pass) {
-    T.off_l0 = 0;
-    T.off_l1 = 0;                          // (single list: the merge is in place)
-    T.off_p = T.list_in_global ? 0 : al4(T.K);   // pc[P2], ps[P2], ins[P2]
-    T.off_red = T.off_p + 3 * p2 + 2 * 512 + 1024 + 8;   // + fringe x2, pending list, counters
-    T.lds_floats = T.off_red + 64;
-    if (T.lds_floats * 4 <= 160 * 1024 || T.list_in_global) break;
-    T.list_in_global = 1;
-  }
-  if ((T.K + P.nt_thr - 1) / P.nt_thr > 128) P.nt_thr = 1024;   // nmx_kern_burst_thr_wide: 64 entries per thread
-  NMX_REQUIRE((T.K + P.nt_thr - 1) / P.nt_thr <= (P.nt_thr > 256 ? 64 : 128), "burst top-K list too long for the merge kernel "
-              "(sfreq x time_duration_s x (1 - threshold / 100) > 65 536 samples)");
-  NMX_REQUIRE(T.lds_floats * 4 <= 160 * 1024,
-              "burst threshold state does not fit in 160 KiB LDS (ring x (1 - q) too large)");
-  NmxBurstStatArgs& S = P.bstat;
-  S.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
-  S.n_channels = d.n_channels;
-  S.n_bands = d.n_burst_bands;
-  S.W = d.window;
-  S.sfreq = (float)d.sfreq;
-  S.seg_s = (float)seg_s;
-  S.out_mask = d.burst_out_mask;
-  S.cols = cv(d.burst_cols);
-  S.off_e = 0;
-  S.off_red = al4(d.window + d.window / 16 + 1);   // padded series (NMX_EP)
-  S.lds_floats = S.off_red + 64;
-  const size_t n_state = (size_t)d.n_channels * d.n_burst_bands;
-  P.top_bytes = n_state * T.K * sizeof(float);
-  P.counts_bytes = n_state * 2 * sizeof(long long);
-  P.d_top = (float*)be_alloc(P.top_bytes);
-  P.d_counts = (long long*)be_alloc(P.counts_bytes);
-  P.d_floor = (float*)be_alloc(n_state * sizeof(float));
-  if (!P.d_top || !P.d_counts || !P.d_floor) return nmx_fail(NMX_E_NOMEM, "burst state allocation failed");
-  be_memset_sync(P.d_top, 0, P.top_bytes);
-  be_memset_sync(P.d_counts, 0, P.counts_bytes);
-  burst_floor_reset(P);
-#ifdef NMX_HOST_EMU
-  P.env_sparse = false;   // (the emulator runs the generic Hilbert item, which stores every row)
-#else
-  P.env_sparse = env_int("NMX_BURST_ENV_SPARSE", 1) != 0;
-  P.env_sparse_count = env_int("NMX_BURST_ENV_SPARSE", 1) == 2;
-#endif
-  P.have_bursts = true;
-  return 0;
-}
-
 int build_resample(Plan& P) {
   const nmx_plan_desc& d = P.d;
   if (d.raw_window <= 0) return 0;
@@ -296,7 +212,7 @@ int build_sharp(Plan& P) {
   NMX_REQUIRE(d.sw_distance_peaks >= 1 && d.sw_distance_troughs >= 1, "`distance` must be greater or equal to 1");
   NMX_REQUIRE(!(d.sw_between && !(d.sw_estimate_peaks && d.sw_estimate_troughs)),
               "apply_estimator_between_peaks_and_troughs needs both polarities estimated");
-  NmxSharpArgs& A = P.sharp;
+  NmxSharpArgs& A = P.sharp.a;
   A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.n_filters = d.n_sw_filters;
@@ -398,9 +314,38 @@ int build_sharp(Plan& P) {
   for (int i = 0; i < d.n_filters; ++i) ns += d.filters[i].sw_index >= 0;
   NMX_REQUIRE(ns == d.n_sw_filters, "every sharp-wave filter needs exactly one FIR");
   P.have_sharp = true;
-#ifndef NMX_HOST_EMU   // (the register-resident path exists on the device only)
-  P.sharp_dense_first = A.dense_ok != 0;
+  bool dense = A.dense_ok != 0;
+#ifdef NMX_HOST_EMU   // (the register-resident path exists on the device only)
+  dense = false;
 #endif
+  P.sharp.kind = A.slab_mode ? (dense ? NMX_SHARP_DENSE_SLAB : NMX_SHARP_SLAB) : (dense ? NMX_SHARP_DENSE_LIST : NMX_SHARP_LIST);
+  return 0;
+}
+
+// the sharp-wave analysis of one chunk (nw hops, parity `par`: the bank has filled swy[par]) on stream `ss`
+static int launch_sharp_stage(Plan& P, int par, int nw, float* d_out, be_stream_t ss, bool tev) {
+  if (!P.have_sharp) return 0;
+  SharpStage& S = P.sharp;
+  const int n_items = nw * P.d.n_channels * P.d.n_sw_filters;
+  int rc;
+  NmxSharpArgs A = S.a;
+  A.y = (const float*)S.swy[par].p; A.out = d_out; A.n_windows = nw;
+  if (A.slab_blocks > 0) {   // long-window kinds: the list kernel's slabs, sized by its grid (nmx_wave_slab.hip)
+    const double scale = g_ensure_scale;   // (a fixed size: not one to grow with the chunks that follow)
+    g_ensure_scale = 1.0;
+    rc = ensure(S.slab, (size_t)A.slab_blocks * A.slab_floats * sizeof(float));
+    g_ensure_scale = scale;
+    if (rc) return rc;
+    A.slab = (float*)S.slab.p;
+  }
+  if (S.kind == NMX_SHARP_DENSE_LIST || S.kind == NMX_SHARP_DENSE_SLAB) {
+    if ((rc = ensure(S.todo[par], (size_t)n_items))) return rc;
+    A.todo = (unsigned char*)S.todo[par].p;
+  }
+  be_stage(5);
+  if (tev) be_timer_start(P.timers[5], ss);
+  be_launch_sharp(A, S.kind, n_items, (size_t)A.lds_floats * 4, ss);
+  if (tev) be_timer_stop(P.timers[5], ss);
   return 0;
 }
 

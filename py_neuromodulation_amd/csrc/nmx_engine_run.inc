@@ -71,11 +71,8 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   }
   if (P.overlap == 1 && P.chunk_seq >= 1)   // (this schedule runs the Hilbert kernel on the side stream too: it reads the
     be_stream_wait(s, P.ev_join[par ^ 1]);  // band series `yb`, which exists once)
-  Buf& B_env = P.env[par];
-  Buf& B_full = P.env_full[par];
-  Buf& B_swy = P.swy[par];
-  Buf& B_thr = P.thr[par];
-  Buf& B_todo = P.sw_todo[par];
+  Buf& B_env = P.bursts.env[par];
+  Buf& B_swy = P.sharp.swy[par];
   // ---- pre-processing -------------------------------------------------------------------
   const float* src = d_x;
   long long ch_stride = ldx, win_stride = 0;
@@ -183,9 +180,9 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       if ((rc = ensure(B_swy, (size_t)nw * C * d.n_sw_filters * W * sizeof(float)))) return rc;
       A.sw_out = (float*)B_swy.p;
     }
-    if (P.have_bursts && (P.bank.w64 || A.partitioned)) {   // band series for the stand-alone Hilbert kernel
-      if ((rc = ensure(P.yb, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
-      A.yb_out = (float*)P.yb.p;
+    if (P.have_bursts && P.bursts.own_hilbert) {   // band series for the stand-alone Hilbert kernel
+      if ((rc = ensure(P.bursts.yb, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
+      A.yb_out = (float*)P.bursts.yb.p;
     }
     launch_fir_stage(P, P.bank, A, nw * C, s, tev);
     if (P.have_kalman) {   // sequential over the hops of the chunk; chunks run in order on `s`
@@ -194,137 +191,15 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       be_launch_kalman(K, s);
     }
   }
-  auto launch_sharp = [&](be_stream_t ss) -> int {
-    if (!P.have_sharp) return 0;
-    NmxSharpArgs A = P.sharp;
-    A.y = (const float*)B_swy.p; A.out = d_out; A.n_windows = nw;
-    if (A.slab_blocks > 0) {   // long-window mode: the list kernel's slabs, sized by its grid (nmx_wave_slab.hip)
-      const double scale = g_ensure_scale;   // (a fixed size: not one to grow with the chunks that follow)
-      g_ensure_scale = 1.0;
-      const int rc3 = ensure(P.sw_slab, (size_t)A.slab_blocks * A.slab_floats * sizeof(float));
-      g_ensure_scale = scale;
-      if (rc3) return rc3;
-      A.slab = (float*)P.sw_slab.p;
-    }
-    be_stage(5);
-    if (tev) be_timer_start(P.timers[5], ss);
-    if (P.sharp_dense_first) {
-      { const int rc3 = ensure(B_todo, (size_t)nw * C * d.n_sw_filters); if (rc3) return rc3; }
-      A.todo = (unsigned char*)B_todo.p;
-      be_launch_sharp_dense(A, nw * C * d.n_sw_filters, ss);
-      be_launch_sharp_todo(A, nw * C * d.n_sw_filters, (size_t)A.lds_floats * 4, A.todo, ss);
-    } else {
-      be_launch_sharp(A, nw * C * d.n_sw_filters, (size_t)A.lds_floats * 4, ss);
-    }
-    if (tev) be_timer_stop(P.timers[5], ss);
-    return 0;
-  };
   const bool sharp_side = P.overlap == 4 && P.have_sharp;
   if (sharp_side) {
     be_event_record(P.ev_fork_d, s);
     be_stream_wait(P.stream_d, P.ev_fork_d);
-    if ((rc = launch_sharp(P.stream_d))) return rc;
+    if ((rc = launch_sharp_stage(P, par, nw, d_out, P.stream_d, tev))) return rc;
     be_event_record(P.ev_join_d[par], P.stream_d);
   }
-  be_stream_t sb = s;
   be_stage(4);
-  if (P.have_bursts) {
-    if ((rc = ensure(B_thr, (size_t)nw * C * d.n_burst_bands * sizeof(float)))) return rc;
-    if (P.overlap == 1) {
-      sb = P.stream_b;
-      be_event_record(P.ev_fork, s);
-      be_stream_wait(sb, P.ev_fork);
-    }
-    if (tev) be_timer_start(P.timers[4], sb);
-    const unsigned char* env_full = nullptr;
-    if (P.bank.w64 || P.bank.a.partitioned) {
-      NmxHilbertArgs H = P.hil;
-      H.y = (const float*)P.yb.p; H.env = (float*)B_env.p;
-      // Rows that cannot reach their threshold leave only the tail the walk reads (one-wave kernels; NMX_BURST_ENV_SPARSE).
-      // No event orders this launch behind the previous chunk's walk, which may still run on the side stream: the kernel
-      // reads whatever floor is there.  That is safe because EVERY value ever stored there -- -INFINITY, or the s[lo] some
-      // finished walk of this state left -- is a lower bound of all thresholds of the hops behind that walk, this chunk's
-      // included (NmxBurstThrArgs::floor); a 4-byte store is seen whole or not at all.  State reset / import drain the
-      // streams before they put -INFINITY back.
-      if (P.env_sparse && (P.hil_kind == NMX_HIL_W500 || P.hil_kind == NMX_HIL_W1000)) {
-        if ((rc = ensure(B_full, (size_t)nw * C * d.n_burst_bands))) return rc;
-        H.floor = P.d_floor; H.full = (unsigned char*)B_full.p;
-        H.n_seq = C * d.n_burst_bands; H.overlap = P.bthr.overlap;
-        env_full = H.full;
-      }
-      be_launch_hilbert(H, P.hil_kind, (long long)nw * C * d.n_burst_bands, (size_t)H.lds_floats * 4, sb);
-      if (env_full && P.env_sparse_count) {   // NMX_BURST_ENV_SPARSE=2 (tests, measurements): read the flags back, at the price of a sync
-        std::vector<unsigned char> f((size_t)nw * C * d.n_burst_bands);
-        if ((rc = be_sync(sb))) return rc;
-        be_d2h_sync(f.data(), env_full, f.size());
-        for (unsigned char v : f) P.env_tail_rows += v == 0;
-        P.env_rows += (long long)f.size();
-      }
-    }
-    if (P.overlap >= 2) {
-      sb = P.stream_b;
-      be_event_record(P.ev_fork, s);
-      be_stream_wait(sb, P.ev_fork);
-    }
-    NmxBurstThrArgs T = P.bthr;
-    T.env = (const float*)B_env.p; T.thr = (float*)B_thr.p; T.top = P.d_top; T.counts = P.d_counts;
-    T.floor = P.d_floor;
-    T.n_windows = nw;
-    // The workgroup kernel handles the hops that still FILL the history (the first 291 of a stream at the default
-    // settings); from the hop at which the ring is full the one-wave walk takes over -- also in the middle of a chunk
-    const int n_seq = C * d.n_burst_bands;
-    auto hops = [&](int first, int n) {   // the walk arguments for hops [first, first + n) of this chunk
-      NmxBurstThrArgs X = T;
-      X.env = T.env + (size_t)first * n_seq * W;
-      X.thr = T.thr + (size_t)first * n_seq;
-      X.n_windows = n;
-      return X;
-    };
-    int done = 0;
-    // A FRESH stream: the hops that fill the history are one sort + a barrier-free walk (nmx_k_burst_fill.h; the
-    // workgroup kernel spent 7.1 ms on the 291 fill hops of the default settings)
-    if (P.thr_fill && P.burst_windows_seen == 0 && nw >= 2) {
-      int n = nmx_burst_fill_hops(T, nw);
-#ifndef NMX_HOST_EMU
-      if (P.thr_wave)   // stop where the one-wave walk can take over
-        for (int k = 1; k < n; ++k)
-          if (nmx_burst_thr_wave_ok(T, k)) { n = k; break; }
-#endif
-      if (n >= 2) {   // scratch: the 16-bit slot of every sample, per sequence, and (two-launch form) the sorted samples
-        const size_t n_slot = (size_t)n_seq * NMX_FILL_MAX;
-        if ((rc = ensure(P.thr_slots, n_slot * (sizeof(unsigned short) + sizeof(float))))) return rc;
-        float* sorted = (float*)P.thr_slots.p;   // (the floats first: 4-byte aligned whatever n_slot)
-        be_launch_burst_fill(hops(0, n), n_seq, (unsigned short*)(sorted + n_slot), sorted, P.fill_split, sb);
-        done = n;
-      }
-    }
-    if (done < nw) {
-      const long long seen = P.burst_windows_seen + done;
-      const int rem = nw - done;
-      int k_fill = 0;
-#ifndef NMX_HOST_EMU
-      if (P.thr_wave && !nmx_burst_thr_wave_ok(T, seen)) {
-        k_fill = rem;
-        for (int k = 1; k < rem; ++k)
-          if (nmx_burst_thr_wave_ok(T, seen + k)) { k_fill = k; break; }
-      }
-#endif
-      if (k_fill > 0 && k_fill < rem) {
-        be_launch_burst_thr(hops(done, k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, -1, P.thr_list_lds);
-        be_launch_burst_thr(hops(done + k_fill, rem - k_fill), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, seen + k_fill,
-                            P.thr_list_lds);
-      } else {
-        be_launch_burst_thr(hops(done, rem), n_seq, P.nt_thr, (size_t)T.lds_floats * 4, sb, P.thr_wave ? seen : -1, P.thr_list_lds);
-      }
-    }
-    P.burst_windows_seen += nw;
-    NmxBurstStatArgs S = P.bstat;
-    S.env = (const float*)B_env.p; S.thr = (const float*)B_thr.p; S.out = d_out; S.n_windows = nw;
-    S.full = env_full;
-    be_launch_burst_stat(S, nw * C * d.n_burst_bands, (size_t)S.lds_floats * 4, sb);
-    if (tev) be_timer_stop(P.timers[4], sb);
-    if (P.overlap) be_event_record(P.ev_join[par], sb);
-  }
+  if (P.have_bursts && (rc = launch_burst_stage(P, par, nw, d_out, s, tev))) return rc;
   if (P.have_to) {
     NmxTimeOscArgs A = P.to;
     A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
@@ -356,7 +231,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     be_launch_coh(A, nw * A.n_pairs, s);
     if (tev) be_timer_stop(P.timers[7], s);
   }
-  if (!sharp_side && (rc = launch_sharp(s))) return rc;
+  if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
   // (no join on the main stream: the chunk is finished by chunk_finalize below, on its own stream)
   be_event_record(P.ev_main[par], s);
   be_stage(0);
@@ -470,8 +345,8 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   // copy runs under the chunk before it
   const int64_t host_big = std::min<int64_t>(P.chunk_windows, P.host_chunk_windows);
   int64_t host_first = std::min<int64_t>(host_big, P.host_first_chunk);
-  if (host && P.have_bursts && P.thr_fill && P.burst_windows_seen == 0)   // a fresh stream: the whole fill phase of the burst
-    host_first = std::max<int64_t>(host_first, nmx_burst_fill_hops(P.bthr, (int)host_big));   // history in ONE sort (nmx_k_burst_fill.h)
+  if (host && P.have_bursts)   // a fresh stream: the whole fill phase of the burst history in ONE sort (nmx_k_burst_fill.h)
+    host_first = std::max<int64_t>(host_first, P.bursts.fill_hops((int)host_big));
   auto chunk_at = [&](int64_t w0_) { return host ? (w0_ == 0 ? host_first : host_big) : dev_chunk; };
   be_timer_start(P.timers[0], s);
   int64_t prev_w0 = -1, prev_nw = 0;
@@ -711,17 +586,17 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   for (int c = 0; c < C; ++c)
     for (int i = 0; i < W; ++i) xf[(size_t)c * W + i] = (float)x[(size_t)c * ldx + i];
   if ((rc = ensure(P.x_in, xf.size() * sizeof(float)))) return rc;
-  if ((rc = ensure(P.swy[0], yf.size() * sizeof(float)))) return rc;
+  if ((rc = ensure(P.sharp.swy[0], yf.size() * sizeof(float)))) return rc;
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
   NmxBankArgs A = P.bank.a;
   A.x = (const float*)P.x_in.p; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr;
   A.clean_on_load = 0; A.out = nullptr;
-  A.n_sw_filters = NF; A.sw_out = (float*)P.swy[0].p;
+  A.n_sw_filters = NF; A.sw_out = (float*)P.sharp.swy[0].p;
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
   }
   launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
-  be_d2h_async(yf.data(), P.swy[0].p, yf.size() * sizeof(float), s);
+  be_d2h_async(yf.data(), P.sharp.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];
   return be_check_launch();
@@ -857,8 +732,8 @@ int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
   if (!P || !buf || n < 1 || which < 1 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
   std::string k = P->kernels[which];
-  if (which == 4 && P->env_sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
-    k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->env_tail_rows) + "/" + std::to_string(P->env_rows);
+  if (which == 4 && P->bursts.sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
+    k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->bursts.env_tail_rows) + "/" + std::to_string(P->bursts.env_rows);
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
   memcpy(buf, k.data(), m);
   buf[m] = 0;

@@ -42,6 +42,28 @@ static inline int nmx_burst_fill_hops(const NmxBurstThrArgs& A, int n_windows) {
   return (int)(n_windows < maxn ? n_windows : maxn);
 }
 
+// The launches of the walk for hops [0, nw) of a chunk, `seen` = the hops every sequence has absorbed before it: at most
+// three consecutive segments.  A fresh stream's fill phase is one sort + a barrier-free walk (FILL: the workgroup kernel
+// spent 7.1 ms on the 291 fill hops of the default settings), and stops where the one-wave walk can take over; the
+// workgroup kernel handles what else still FILLS the history; from the hop at which the ring is full the one-wave walk
+// takes over -- also in the middle of a chunk -- with its list in LDS while the stream is young at the segment's first hop.
+enum NmxBurstWalkKind { NMX_WALK_FILL, NMX_WALK_WORKGROUP, NMX_WALK_WAVE };
+struct NmxBurstWalkSeg { int first, n; NmxBurstWalkKind kind; bool list_lds; };
+static inline int nmx_burst_walk_schedule(const NmxBurstWalk& K, const NmxBurstThrArgs& A, long long seen, int nw, NmxBurstWalkSeg seg[3]) {
+  int n_seg = 0, done = 0;
+  if (K.fill && seen == 0 && nw >= 2) {
+    const long long n = nmx_burst_fill_hops(A, nw) < K.wave_from ? nmx_burst_fill_hops(A, nw) : K.wave_from;
+    if (n >= 2) { seg[n_seg++] = NmxBurstWalkSeg{0, (int)n, NMX_WALK_FILL, false}; done = (int)n; }
+  }
+  if (done < nw && K.wave_from > seen + done) {
+    const long long n = K.wave_from - (seen + done) < nw - done ? K.wave_from - (seen + done) : nw - done;
+    seg[n_seg++] = NmxBurstWalkSeg{done, (int)n, NMX_WALK_WORKGROUP, false};
+    done += (int)n;
+  }
+  if (done < nw) seg[n_seg++] = NmxBurstWalkSeg{done, nw - done, NMX_WALK_WAVE, seen + done < K.list_lds_until};
+  return n_seg;
+}
+
 #ifndef NMX_HOST_EMU
 // ---- the rank pointer -----------------------------------------------------------------------------------------
 // The threshold of a hop is the arrived slot of rank r (r grows by ~(1 - q) x overlap per hop).  Instead of

@@ -361,7 +361,6 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
   }
 }
 
-#ifndef NMX_HOST_EMU
 // ---------------------------------------------------------------------------------------
 // Steady regime of the threshold walk with ONE WAVE per (channel, band).
 //
@@ -387,6 +386,56 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
 #define NMX_THRW_LDS_FLOATS_NR(NR) NMX_THRW_LDS_FLOATS_OF(NR, false)
 #define NMX_THRW_LDS_FLOATS NMX_THRW_LDS_FLOATS_NR(2)
 
+// ---- what the plan asks when it is built (host side: build_bursts) -------------------------------------------------------
+// The one-wave walk may take a launch whose first hop finds the ring full: W + (seen - 1) overlap >= n_ring samples
+// absorbed, `seen` = the hops every sequence has absorbed before that hop.  For a plan that is a threshold in `seen`:
+// the smallest such count, or NMX_WALK_NEVER for a shape the kernel does not take.
+#define NMX_WALK_NEVER 0x7fffffffffffffffLL
+static inline int nmx_burst_thrw_nr(const NmxBurstThrArgs& A) { return A.overlap <= 128 ? 2 : 4; }
+static inline long long nmx_burst_wave_from(const NmxBurstThrArgs& A) {
+  const int nr = nmx_burst_thrw_nr(A);   // registers per lane -> fringe capacity 256 nr, refill 192 nr
+  if (A.overlap < 1 || A.overlap > 256 || A.overlap + 8 >= 192 * nr) return NMX_WALK_NEVER;
+  const long long m_ring = A.n_ring;
+  const long long lo_ring = (long long)floor(A.q * (double)(m_ring - 1));
+  const int ia_ring = (int)(m_ring - 1 - lo_ring);
+  if (!(A.K > 2 * 256 * nr && ia_ring >= A.K - 3 && ia_ring < A.K)) return NMX_WALK_NEVER;
+  const long long short_of = m_ring - A.W;   // samples the ring still lacks behind the first hop
+  return short_of <= 0 ? 1 : 1 + (short_of + A.overlap - 1) / A.overlap;
+}
+// dynamic LDS of the one-wave walk, bytes: working set + K / 64 + 2 block counters, and the top-K list itself with `list`
+static inline size_t nmx_burst_thrw_lds(int nr, int K, bool list) {
+  const int f = nr == 2 ? NMX_THRW_LDS_FLOATS_OF(2, list) : NMX_THRW_LDS_FLOATS_OF(4, list);
+  return (size_t)(f + K / 64 + 4) * 4 + (list ? (size_t)K * 4 : 0);
+}
+// The walk of a plan: its selectors and the constants of the one-wave kernel's launches.
+struct NmxBurstWalk {
+  bool fill;                  // fresh stream: sort-once walk of the fill phase (nmx_k_burst_fill.h; NMX_THR_FILL)
+  long long wave_from;        // one-wave walk from this count of absorbed hops on (NMX_WALK_NEVER: NMX_THR_WAVE=0, the emulator, shapes
+                              // the kernel does not take)
+  int nr;                     // ... its registers per lane for a hop's new samples: 2 or 4
+  size_t lds, lds_list;       // ... its dynamic LDS without / with the top-K list
+  long long list_lds_until;   // ... keeps the list in LDS for a launch whose first hop has absorbed fewer hops than this (0: never)
+};
+// The list in LDS pays while the stream is YOUNG: the ring has just filled, a quarter of every hop's samples still enters
+// the list and a flush is due every ~15 hops (a fresh 120 s stream: 25.4 -> 22.2 ms end to end).  After thousands of hops
+// the kept minimum has risen, flushes are rare, and 56 KB of LDS per walk only take occupancy from the throughput
+// kernels running next to it (the bench's steady state: 6.59 -> 6.87 ms per step) -- then the list stays in L2.
+// ... only while the walks still fit the chip in two rounds (the default history: 52 KB, three walks per CU, 1536 series
+// in two rounds), and only for hops of <= 128 samples: config 3 (2 kHz, 200 samples per hop, the four-register walk with
+// its 512-entry pending list) measured 1.46 -> 2.2 ms per 256 hops with its list in LDS
+static inline NmxBurstWalk nmx_burst_walk_plan(const NmxBurstThrArgs& A, bool fill, bool wave, bool list_lds) {
+  NmxBurstWalk K;
+  K.fill = fill;
+  K.wave_from = wave ? nmx_burst_wave_from(A) : NMX_WALK_NEVER;
+  K.nr = nmx_burst_thrw_nr(A);
+  K.lds = nmx_burst_thrw_lds(K.nr, A.K, false);
+  K.lds_list = nmx_burst_thrw_lds(K.nr, A.K, true);
+  const long long per_round = 256LL * (long long)((160 * 1024) / K.lds_list), n_seq = (long long)A.n_channels * A.n_bands;
+  K.list_lds_until = list_lds && K.nr == 2 && K.lds_list <= 80 * 1024 && n_seq <= 2 * per_round ? 4096 : 0;
+  return K;
+}
+
+#ifndef NMX_HOST_EMU
 // number of entries of the DESCENDING list l[0..n) that are >= v
 NMX_DEV int nmx_count_ge_lds(const float* l, int n, float v) {
   int lo = 0, hi = n;
@@ -404,18 +453,6 @@ NMX_DEV int nmx_count_gt_lds(const float* l, int n, float v) {
     if (l[mid] > v) lo = mid + 1; else hi = mid;
   }
   return lo;
-}
-
-// host-side test: may the wave kernel take this batch?  (first hop already in the steady regime)
-static inline bool nmx_burst_thr_wave_ok(const NmxBurstThrArgs& A, long long windows_seen) {
-  const int nr = A.overlap <= 128 ? 2 : 4;   // registers per lane -> fringe capacity 256 nr, refill 192 nr
-  if (windows_seen <= 0 || A.overlap > 256 || A.overlap + 8 >= 192 * nr) return false;
-  const long long total = (long long)A.W + (windows_seen - 1) * (long long)A.overlap;
-  const long long m_ring = A.n_ring;
-  const double pos_ring = A.q * (double)(m_ring - 1);
-  const long long lo_ring = (long long)floor(pos_ring);
-  const int ia_ring = (int)(m_ring - 1 - lo_ring);
-  return A.K > 2 * 256 * nr && total >= m_ring && ia_ring >= A.K - 3 && ia_ring < A.K;
 }
 
 #ifdef NMX_THRW_PROFILE

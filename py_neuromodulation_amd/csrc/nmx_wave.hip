@@ -79,30 +79,17 @@ __global__ void __launch_bounds__(64) nmx_kern_burst_thr_wave(const NmxBurstThrA
   nmx_burst_thr_wave_item<NR, LL>(A, item / A.n_bands, item % A.n_bands, nmx_smem_wave);
 }
 
-extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, hipStream_t s, long long windows_seen, bool lds_list) {
+// nr, list_lds, lds: the plan's constants and the schedule's verdict for this launch (nmx_burst_walk_plan, nmx_burst_walk_schedule)
+extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, int nr, bool list_lds, size_t lds, hipStream_t s) {
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  const int nr = A->overlap <= 128 ? 2 : 4;
-  const size_t base = (size_t)((nr == 2 ? NMX_THRW_LDS_FLOATS_NR(2) : NMX_THRW_LDS_FLOATS_NR(4)) + A->K / 64 + 4) * 4;
-  const size_t with_list = (size_t)((nr == 2 ? NMX_THRW_LDS_FLOATS_OF(2, true) : NMX_THRW_LDS_FLOATS_OF(4, true)) + A->K / 64 + 4) * 4 +
-                           (size_t)A->K * 4;
-  // The list in LDS pays while the stream is YOUNG: the ring has just filled, a quarter of every hop's samples still enters
-  // the list and a flush is due every ~15 hops (a fresh 120 s stream: 25.4 -> 22.2 ms end to end).  After thousands of hops
-  // the kept minimum has risen, flushes are rare, and 56 KB of LDS per walk only take occupancy from the throughput
-  // kernels running next to it (the bench's steady state: 6.59 -> 6.87 ms per step) -- then the list stays in L2.
-  // ... only while the walks still fit the chip in two rounds (the default history: 52 KB, three walks per CU, 1536 series
-  // in two rounds), and only for hops of <= 128 samples: config 3 (2 kHz, 200 samples per hop, the four-register walk with
-  // its 512-entry pending list) measured 1.46 -> 2.2 ms per 256 hops with its list in LDS
-  const long long per_round = 256LL * (long long)((160 * 1024) / with_list);
-  const bool ll = lds_list && nr == 2 && with_list <= 80 * 1024 && windows_seen < 4096 && (long long)n_items <= 2 * per_round;
-  const size_t lds = ll ? with_list : base;
   if (nr == 2) {
-    if (ll) hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, true>), dim3(n_items), dim3(64), lds, s, *A);
+    if (list_lds) hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, true>), dim3(n_items), dim3(64), lds, s, *A);
     else hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, false>), dim3(n_items), dim3(64), lds, s, *A);
-    nmxi_note_kernel(ll ? "nmx_kern_burst_thr_wave<2, true>" : "nmx_kern_burst_thr_wave<2, false>");
+    nmxi_note_kernel(list_lds ? "nmx_kern_burst_thr_wave<2, true>" : "nmx_kern_burst_thr_wave<2, false>");
   } else {
     hipLaunchKernelGGL((nmx_kern_burst_thr_wave<4, false>), dim3(n_items), dim3(64), lds, s, *A);
     nmxi_note_kernel("nmx_kern_burst_thr_wave<4, false>");
@@ -390,11 +377,9 @@ __global__ void __launch_bounds__(256) nmx_kern_sharp_dense(const NmxSharpArgs A
   nmx_sharp_item_dense(A, r / A.n_channels, r % A.n_channels, fi, (long long)item, smem);
 }
 
-// nmx_wave_slab.hip: the list kernel of the long-window mode (todo = nullptr: every item)
-extern "C" void nmx_wave_launch_sharp_slab(const NmxSharpArgs* A, int n_items, const unsigned char* todo, hipStream_t s);
-
-extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s) {
-  if (A->slab_mode) {
+// (the list kernel of the long-window kinds: nmx_wave_slab.hip)
+extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, NmxSharpKind kind, int n_items, hipStream_t s) {
+  if (kind == NMX_SHARP_DENSE_SLAB) {
     static unsigned long long seen = 0;   // (the series alone is beyond the 64 KiB a kernel gets without asking)
     if (nmx_first_on_device(seen)) {
       (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_dense, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -428,7 +413,6 @@ __global__ void __launch_bounds__(64) nmx_kern_sharp_todo(const NmxSharpArgs A, 
 
 extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, size_t lds, const unsigned char* todo,
                                            hipStream_t s) {
-  if (A->slab_mode) { nmx_wave_launch_sharp_slab(A, n_items, todo, s); return; }
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_todo, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -439,22 +423,18 @@ extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, s
   nmxi_note_kernel("nmx_kern_sharp_todo");
 }
 
-extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, int n_items, size_t lds, hipStream_t s) {
+extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, NmxBurstStatKind kind, int n_items, size_t lds, hipStream_t s) {
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_stat, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  if ((A->W & 3) == 0 && A->W <= 2048) {
-    if (A->W <= 1024) {
-      if (A->full) hipLaunchKernelGGL((nmx_kern_burst_stat_reg<16, true>), dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      else hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      nmxi_note_kernel(A->full ? "nmx_kern_burst_stat_reg_sparse<16>" : "nmx_kern_burst_stat_reg<16>");
-    } else {
-      if (A->full) hipLaunchKernelGGL((nmx_kern_burst_stat_reg<32, true>), dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      else hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items);
-      nmxi_note_kernel(A->full ? "nmx_kern_burst_stat_reg_sparse<32>" : "nmx_kern_burst_stat_reg<32>");
-    }
-    return;
+  const dim3 grid4((n_items + 3) / 4);
+  switch (kind) {   // (the register forms: no LDS)
+    case NMX_BSTAT_REG16_SPARSE: hipLaunchKernelGGL((nmx_kern_burst_stat_reg<16, true>), grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg_sparse<16>"); return;
+    case NMX_BSTAT_REG16: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<16>"); return;
+    case NMX_BSTAT_REG32_SPARSE: hipLaunchKernelGGL((nmx_kern_burst_stat_reg<32, true>), grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg_sparse<32>"); return;
+    case NMX_BSTAT_REG32: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<32>"); return;
+    case NMX_BSTAT_GENERIC: break;
   }
   const int k = waves_per_wg(lds);
   const int slice = (int)((lds / 4 + 3) & ~(size_t)3);
@@ -464,7 +444,6 @@ extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, int n_item
 }
 
 extern "C" void nmx_wave_launch_sharp(const NmxSharpArgs* A, int n_items, size_t lds, hipStream_t s) {
-  if (A->slab_mode) { nmx_wave_launch_sharp_slab(A, n_items, nullptr, s); return; }
   static unsigned long long seen = 0;
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_sharp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -1,15 +1,19 @@
-"""Generate tests/golden/fir_kernel_choice.json: for every case of tests/fir_kernel_choice_cases.py the kernels a batch
-launched in stages 1, 3 and 6 and the SHA-256 of the table it returned.
+"""Generate a kernel-choice fixture: for every case of a case module under tests/ what its run_case returns -- the kernels
+the batches launched in the module's stages and the SHA-256 of the tables they returned.
 
-Runs on the GPU, at the commit whose kernel choice is to be kept (the parent of a change to how the one-wave FIR kernels
-are chosen); tests/test_fir_kernel_choice_gpu.py compares a later build against the file.  Every case runs twice on fresh
-engines and must repeat itself bit for bit before it is written.
+    tests/fir_kernel_choice_cases.py (the default)  -> tests/golden/fir_kernel_choice.json    (one-wave FIR kernels)
+    tests/burst_kernel_choice_cases.py              -> tests/golden/burst_kernel_choice.json  (bursts chain, sharp waves)
 
-    python tests/golden/make_fir_kernel_choice.py [output.json]
+Runs on the GPU, at the commit whose kernel choice is to be kept (the parent of a change to how those kernels are chosen);
+tests/test_fir_kernel_choice_gpu.py / tests/test_burst_kernel_choice_gpu.py compare a later build against the file.  Every
+case runs twice on fresh engines and must repeat itself bit for bit before it is written.
+
+    python tests/golden/make_fir_kernel_choice.py [output.json | case module [output.json]]
 """
 
 from __future__ import annotations
 
+import importlib
 import json
 import os
 import sys
@@ -19,10 +23,9 @@ HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE.parents[1]))
 
 from py_neuromodulation_amd import _lib  # noqa: E402
-from tests import fir_kernel_choice_cases as cases  # noqa: E402
 
 
-def main(out: Path) -> None:
+def main(out: Path, cases) -> None:
     lib = _lib.get_library()
     assert lib.device_count() >= 1, "no HIP device visible"
     table = {}
@@ -37,4 +40,6 @@ def main(out: Path) -> None:
 
 
 if __name__ == "__main__":
-    main(Path(sys.argv[1]) if len(sys.argv) > 1 else HERE / "fir_kernel_choice.json")
+    args = sys.argv[1:]
+    module = args.pop(0) if args and not args[0].endswith(".json") else "fir_kernel_choice_cases"
+    main(Path(args[0]) if args else HERE / (module[:-len("_cases")] + ".json"), importlib.import_module("tests." + module))
