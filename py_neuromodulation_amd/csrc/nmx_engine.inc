@@ -55,10 +55,25 @@ namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 
-struct Buf {
+// A block that grows on demand and frees itself with its owner.  Whoever deletes the owner has set the device and drained
+// the streams that read the block (nmx_plan_destroy, nmx_norm_destroy, nmx_proj_destroy).
+template <void* (*Alloc)(size_t), void (*Free)(void*)>
+struct Block {
   void* p = nullptr;
   size_t cap = 0;
+  Block() = default;
+  Block(const Block&) = delete;
+  Block& operator=(const Block&) = delete;
+  ~Block() { if (p) Free(p); }
+  bool regrow(size_t bytes) {   // a fresh block of `bytes` (the contents are not kept); false: no memory, and the block is empty
+    if (p) Free(p);
+    p = Alloc(bytes);
+    cap = p ? bytes : 0;
+    return p != nullptr;
+  }
 };
+using Buf = Block<be_alloc, be_free>;                 // device memory (ensure)
+using HostBuf = Block<be_host_alloc, be_host_free>;   // page-locked host memory
 
 // A FIR stage -- a preprocessing_filter stage, the notch or the band-pass bank -- with its kernels decided at plan time
 // (nmx_engine_plan_fir.inc: build_fir_stage, launch_fir_stage).  One launch of its one-wave kernels: the filters of
@@ -96,7 +111,7 @@ struct BurstStage {
   NmxBurstWalk walk{};        // the walk's schedule constants (nmx_k_bursts.h; NMX_THR_FILL, NMX_THR_WAVE, NMX_THR_LIST_LDS)
   bool fill_split = true;     // the fill phase as two launches (sort, one-wave walk; NMX_FILL_SPLIT)
   int nt_thr = 256;           // threads of the workgroup walk
-  // state
+  // state (the blocks belong to the plan: plan_alloc)
   long long seen = 0;         // host mirror of the per-sequence window counter (all sequences advance together)
   float* d_top = nullptr;
   long long* d_counts = nullptr;
@@ -117,6 +132,21 @@ struct SharpStage {
   NmxSharpKind kind = NMX_SHARP_LIST;
   Buf swy[2], todo[2];        // filtered series and the dense launch's flags: read on a side stream, one set per chunk parity
   Buf slab;                   // list slabs of the long-window kinds (one stream runs every sharp-wave launch of a plan)
+};
+// The Kalman filters behind the band-pass activity (nmx_engine_plan_state.inc: build_kalman, kalman_state_*).
+struct KalmanStage {
+  NmxKalmanArgs a{};          // argument template
+  double* d_state = nullptr;  // [C][bands][6]: x, P per filter (the plan's block: plan_alloc)
+  size_t bytes = 0;
+};
+// The raw normaliser, the last pre-processing stage (nmx_engine_plan_state.inc: build_rawnorm, run_rawnorm, rawnorm_state_*).
+struct RawNormStage {
+  NmxRawNormArgs a{};         // argument template; its rings, counts and sorted copies are the plan's blocks (plan_alloc)
+  long long hops = 0;         // hops normalised so far (NmxRawNormArgs::hop0)
+  bool sorted_valid = false;  // the sorted copies of the order-statistic methods mirror the rings
+  size_t ring_bytes = 0, cnt_bytes = 0, len_bytes = 0;
+  Buf x_rn, mean, scale;      // scratch of a chunk: normalised windows, statistics per (hop, channel)
+  Buf qt, qn;                 // ... "quantile" tables / "power" parameters
 };
 
 struct Plan {
@@ -146,7 +176,8 @@ struct Plan {
   int host_first_chunk = 128;              // ... after a short first one (nmx_engine_run.inc)
   int norm_chunk_windows = 384;           // device-resident batches with an attached normaliser (nmx_engine_run.inc; NMX_NORM_CHUNK_WINDOWS)
   int overlap = 1;
-  std::vector<void*> tables;               // device allocations owned by the plan
+  std::vector<void*> tables;               // device allocations of a fixed size (plan_alloc, upload): freed with the plan
+  ~Plan() { for (void* t : tables) be_free(t); }   // (and every Buf frees itself: nmx_plan_destroy has set the device)
   std::map<int, NmxFft> fft_cache;
   std::map<int, const float2*> twn_cache;   // exp(-2 pi i k / n), k < n, of the long-window kernel's combination step (NmxOsc::tw_n)
   // kernel argument templates (per-call fields are patched in process_batch)
@@ -180,25 +211,19 @@ struct Plan {
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
   // scratch
   Buf to_todo;        // flags of the matrix-pipe spectrum kernel (NmxTimeOscArgs::todo)
-  Buf rn_qt, rn_qn;   // raw "quantile" tables / "power" parameters of a chunk
   Buf tap;            // pre-processed windows of a chunk on their way to a host caller (nmx_process_batch_tap)
-  Buf x_in, x_in2[2], x_ref, x_rs, x_rn, rn_mean, rn_scale, x_pf[2], y_notch, out, starts, mask;
-  Buf win_pin;        // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
+  Buf x_in, x_in2[2], x_ref, x_rs, x_pf[2], y_notch, out, starts, mask;
+  HostBuf win_pin;    // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
   // state
-  NmxKalmanArgs kal{};
+  KalmanStage kalman;
   bool have_kalman = false;
   NmxResampleArgs rs{};
   bool have_resample = false;
-  NmxRawNormArgs rn{};
+  RawNormStage rawnorm;
   bool have_rawnorm = false;
-  bool rn_sorted_valid = false;       // the sorted copies of the order-statistic raw normalisers mirror the rings
-  long long rn_hops = 0;
-  size_t rn_ring_bytes = 0, rn_cnt_bytes = 0, rn_len_bytes = 0;
   std::vector<std::vector<double>> pre_taps;
   int w_in = 0;           // samples per incoming window (raw_window when resampling, else window)
   int nt_resample = 256;
-  double* d_kf = nullptr;
-  size_t kf_bytes = 0;
   be_timer_t timers[9];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence,
                           // 8 grid projection
   std::string kernels[9];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
@@ -233,22 +258,21 @@ struct Plan {
 static thread_local double g_ensure_scale = 1.0;
 int ensure(Buf& b, size_t bytes) {
   if (bytes <= b.cap) return 0;
-  if (b.p) be_free(b.p);
-  b.p = nullptr;
-  b.cap = 0;
   if (g_ensure_scale > 1.0) bytes = (size_t)((double)bytes * g_ensure_scale) + 256;
-  size_t want = bytes + bytes / 8;
-  b.p = be_alloc(want);
-  if (!b.p) return nmx_fail(NMX_E_NOMEM, "device allocation of " + std::to_string(want) + " bytes failed");
-  b.cap = want;
+  const size_t want = bytes + bytes / 8;
+  if (!b.regrow(want)) return nmx_fail(NMX_E_NOMEM, "device allocation of " + std::to_string(want) + " bytes failed");
   return 0;
 }
 
-void* upload(Plan& P, const void* src, size_t bytes) {
+// A device block of a fixed size that lives as long as the plan: P.tables is its only owner.
+void* plan_alloc(Plan& P, size_t bytes) {
   void* d = be_alloc(bytes ? bytes : 4);
-  if (!d) return nullptr;
-  if (bytes) be_h2d_sync(d, src, bytes);
-  P.tables.push_back(d);
+  if (d) P.tables.push_back(d);
+  return d;
+}
+void* upload(Plan& P, const void* src, size_t bytes) {
+  void* d = plan_alloc(P, bytes);
+  if (d && bytes) be_h2d_sync(d, src, bytes);
   return d;
 }
 

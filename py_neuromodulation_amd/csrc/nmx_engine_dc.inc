@@ -75,9 +75,9 @@ static int dc_build(Plan& P) {
   P.dc_sub_h.assign((size_t)Cin, 0.f);
   P.dc_pre_h.assign((size_t)C, 0.0);
   if (!P.dc_ok) return 0;
-  P.d_dc_sub = (float*)be_alloc((size_t)Cin * sizeof(float));
-  P.d_dc_pref = (float*)be_alloc((size_t)C * sizeof(float));
-  P.d_dc_nanv = (float*)be_alloc((size_t)Cin * sizeof(float));
+  P.d_dc_sub = (float*)plan_alloc(P, (size_t)Cin * sizeof(float));
+  P.d_dc_pref = (float*)plan_alloc(P, (size_t)C * sizeof(float));
+  P.d_dc_nanv = (float*)plan_alloc(P, (size_t)Cin * sizeof(float));
   if (!P.d_dc_sub || !P.d_dc_pref || !P.d_dc_nanv) return nmx_fail(NMX_E_NOMEM, "offset tables");
   be_memset_sync(P.d_dc_nanv, 0, (size_t)Cin * sizeof(float));
   be_memset_sync(P.d_dc_sub, 0, (size_t)Cin * sizeof(float));
@@ -133,14 +133,15 @@ static int dc_prepare(Plan& P, const float* x, long long ldx, long long t0, bool
   return 0;
 }
 
-static void dc_reset(Plan& P) {
+// ---- the offsets' section of the state blob: learned flag | host-set flag | sub[C_in] (float, padded to 8 bytes) |
+// host[C_in] (double).  All of it lives on the host: the device tables follow at the next batch (dc_dirty).  Reset forgets
+// the learned constants; the caller's are a setting of the plan (nmx_plan_set_offsets).
+static void dc_state_reset(Plan& P) {
   if (!P.dc_ok) return;
   std::fill(P.dc_sub_h.begin(), P.dc_sub_h.end(), 0.f);
   P.dc_learned = false;
   P.dc_dirty = true;
 }
-
-// state blob section: learned flag | host-set flag | sub[C_in] (float, padded to 8 bytes) | host[C_in] (double)
 static size_t dc_state_bytes(const Plan& P) {
   if (!P.dc_ok) return 0;
   const size_t Cin = (size_t)P.d.n_channels_in;
@@ -156,8 +157,8 @@ static void dc_state_export(const Plan& P, char* q) {
   memcpy(q, P.dc_sub_h.data(), Cin * sizeof(float)); q += (Cin * sizeof(float) + 7) & ~(size_t)7;
   memcpy(q, P.dc_host.data(), Cin * sizeof(double));
 }
-static void dc_state_import(Plan& P, const char* q) {
-  if (!P.dc_ok) return;
+static int dc_state_import(Plan& P, const char* q, size_t) {
+  if (!P.dc_ok) return 0;
   const size_t Cin = (size_t)P.d.n_channels_in;
   long long a = 0, b = 0;
   memcpy(&a, q, sizeof a); q += sizeof a;
@@ -167,4 +168,5 @@ static void dc_state_import(Plan& P, const char* q) {
   P.dc_learned = a != 0;
   P.dc_host_set = b != 0;
   P.dc_dirty = true;
+  return 0;
 }

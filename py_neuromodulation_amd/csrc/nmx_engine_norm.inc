@@ -7,9 +7,9 @@ struct NmxNormHandle {
   float clip = 0.f;
   bool scan_on = true;         // mean / z-score as scans (NMX_NORM_SCAN, read when the normaliser is created)
   long long seq = 0;
-  float* d_ring = nullptr;
-  float* d_sorted = nullptr;   // median methods: scratch, same shape as the ring
-  unsigned char* d_mask = nullptr;
+  Buf ring;                    // float [cap][n_cols]: allocated once (nmx_norm_create), like the two below
+  Buf sorted;                  // median methods: scratch, same shape as the ring
+  Buf mask;                    // unsigned char [n_cols] (empty: every column)
   Buf stage;
   Buf ext, sl;                 // "power": extended history of a batch (raw fp32) and its sign(x) log1p|x| (fp64)
   Buf scan;                    // "mean" / "zscore" as scans (nmx_k_norm.h, NmxNormScan): sums, counts, raw copy of a batch
@@ -30,22 +30,13 @@ int nmx_norm_create(int32_t device, int32_t n_cols, int32_t method, float clip, 
   NmxNormHandle* H = new NmxNormHandle();
   H->device = device; H->n_cols = n_cols; H->method = method; H->cap = n_hist; H->clip = clip;
   H->scan_on = env_int("NMX_NORM_SCAN", 1) != 0;
-  H->d_ring = (float*)be_alloc((size_t)n_hist * n_cols * sizeof(float));
-  if (!H->d_ring) { delete H; return nmx_fail(NMX_E_NOMEM, "device allocation failed"); }
-  if (method >= NMX_NORM_MEDIAN && method != NMX_NORM_POWER) {
-    H->d_sorted = (float*)be_alloc((size_t)n_hist * n_cols * sizeof(float));
-    if (!H->d_sorted) { be_free(H->d_ring); delete H; return nmx_fail(NMX_E_NOMEM, "device allocation failed"); }
+  const size_t ring_bytes = (size_t)n_hist * n_cols * sizeof(float);
+  if (!H->ring.regrow(ring_bytes) || (method >= NMX_NORM_MEDIAN && method != NMX_NORM_POWER && !H->sorted.regrow(ring_bytes)) ||
+      (colmask && !H->mask.regrow((size_t)n_cols))) {
+    delete H;
+    return nmx_fail(NMX_E_NOMEM, "device allocation failed");
   }
-  if (colmask) {
-    H->d_mask = (unsigned char*)be_alloc((size_t)n_cols);
-    if (!H->d_mask) {
-      be_free(H->d_ring);
-      if (H->d_sorted) be_free(H->d_sorted);
-      delete H;
-      return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-    }
-    be_h2d_sync(H->d_mask, colmask, (size_t)n_cols);
-  }
+  if (colmask) be_h2d_sync(H->mask.p, colmask, (size_t)n_cols);
   H->stream = be_stream_create();
   *out = (nmx_norm*)H;
   return be_check_launch();
@@ -56,13 +47,6 @@ int nmx_norm_destroy(nmx_norm* norm) {
   if (!H) return 0;
   be_set_device(H->device);
   be_sync(H->stream);
-  if (H->d_ring) be_free(H->d_ring);
-  if (H->d_sorted) be_free(H->d_sorted);
-  if (H->d_mask) be_free(H->d_mask);
-  if (H->stage.p) be_free(H->stage.p);
-  if (H->ext.p) be_free(H->ext.p);
-  if (H->sl.p) be_free(H->sl.p);
-  if (H->scan.p) be_free(H->scan.p);
   be_stream_destroy(H->stream);
   delete H;
   return 0;
@@ -78,8 +62,8 @@ int nmx_norm_process(nmx_norm* norm, float* rows, int64_t ld, int64_t n_rows, in
   if (rc) return rc;
   be_stream_t s = hip_stream ? (be_stream_t)hip_stream : H->stream;
   NmxNormArgs A;
-  A.n_rows = (int)n_rows; A.n_cols = H->n_cols; A.colmask = H->d_mask; A.ring = H->d_ring;
-  A.cap = H->cap; A.seq0 = H->seq; A.method = H->method; A.clip = H->clip; A.sorted = H->d_sorted;
+  A.n_rows = (int)n_rows; A.n_cols = H->n_cols; A.colmask = (unsigned char*)H->mask.p; A.ring = (float*)H->ring.p;
+  A.cap = H->cap; A.seq0 = H->seq; A.method = H->method; A.clip = H->clip; A.sorted = (float*)H->sorted.p;
   auto launch = [&](const NmxNormArgs& N) -> int {
     if (H->method != NMX_NORM_POWER) {
       // mean / z-score: scans + independent cells (nmx_k_norm.h) in pieces of at most cap - 1 hops; the column walk for
@@ -108,7 +92,7 @@ int nmx_norm_process(nmx_norm* norm, float* rows, int64_t ld, int64_t n_rows, in
     // "power" (nmx_k_power.h): every (hop, column) of the batch is an independent fit over the extended history
     NmxPowerPrepArgs Pp;
     Pp.have = (int)(H->seq < (long long)(H->cap - 1) ? H->seq : (long long)(H->cap - 1));
-    Pp.ring = H->d_ring; Pp.rows = N.rows; Pp.ld = N.ld; Pp.n_rows = N.n_rows; Pp.n_cols = N.n_cols;
+    Pp.ring = (float*)H->ring.p; Pp.rows = N.rows; Pp.ld = N.ld; Pp.n_rows = N.n_rows; Pp.n_cols = N.n_cols;
     Pp.cap = H->cap; Pp.seq0 = H->seq;
     const size_t cells = (size_t)(Pp.have + N.n_rows) * N.n_cols;
     int rc2;
@@ -116,7 +100,7 @@ int nmx_norm_process(nmx_norm* norm, float* rows, int64_t ld, int64_t n_rows, in
     Pp.ext = (float*)H->ext.p; Pp.sl = (double*)H->sl.p;
     NmxPowerArgs Pa;
     Pa.ext = Pp.ext; Pa.sl = Pp.sl; Pa.rows = N.rows; Pa.ld = N.ld; Pa.n_rows = N.n_rows; Pa.n_cols = N.n_cols;
-    Pa.have = Pp.have; Pa.cap = H->cap; Pa.seq0 = H->seq; Pa.colmask = H->d_mask; Pa.clip = H->clip;
+    Pa.have = Pp.have; Pa.cap = H->cap; Pa.seq0 = H->seq; Pa.colmask = (unsigned char*)H->mask.p; Pa.clip = H->clip;
     be_launch_power(Pp, Pa, s);
     return 0;
   };
@@ -125,12 +109,7 @@ int nmx_norm_process(nmx_norm* norm, float* rows, int64_t ld, int64_t n_rows, in
     if ((rc = launch(A))) return rc;
   } else {
     const size_t bytes = (size_t)n_rows * H->n_cols * sizeof(float);
-    if (H->stage.cap < bytes) {
-      if (H->stage.p) be_free(H->stage.p);
-      H->stage.p = be_alloc(bytes);
-      H->stage.cap = H->stage.p ? bytes : 0;
-      if (!H->stage.p) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-    }
+    if (H->stage.cap < bytes && !H->stage.regrow(bytes)) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
     be_h2d_2d_async(H->stage.p, (size_t)H->n_cols * sizeof(float), rows, (size_t)ld * sizeof(float),
                     (size_t)H->n_cols * sizeof(float), (size_t)n_rows, s);
     A.rows = (float*)H->stage.p; A.ld = H->n_cols;
@@ -170,7 +149,7 @@ int nmx_norm_state_export(nmx_norm* norm, void* dst, int64_t n_bytes) {
   if ((rc = be_sync(H->stream))) return rc;
   const int64_t seq = H->seq;
   memcpy(dst, &seq, sizeof(seq));
-  be_d2h_sync((char*)dst + sizeof(int64_t), H->d_ring, (size_t)(need - (int64_t)sizeof(int64_t)));
+  be_d2h_sync((char*)dst + sizeof(int64_t), H->ring.p, (size_t)(need - (int64_t)sizeof(int64_t)));
   return be_check_launch();
 }
 int nmx_norm_state_import(nmx_norm* norm, const void* src, int64_t n_bytes) {
@@ -186,7 +165,7 @@ int nmx_norm_state_import(nmx_norm* norm, const void* src, int64_t n_bytes) {
   memcpy(&seq, src, sizeof(seq));
   NMX_REQUIRE(seq >= 0, "corrupt normaliser state");
   H->seq = seq;
-  be_h2d_sync(H->d_ring, (const char*)src + sizeof(int64_t), (size_t)(need - (int64_t)sizeof(int64_t)));
+  be_h2d_sync(H->ring.p, (const char*)src + sizeof(int64_t), (size_t)(need - (int64_t)sizeof(int64_t)));
   return be_check_launch();
 }
 

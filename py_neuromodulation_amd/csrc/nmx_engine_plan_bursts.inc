@@ -59,6 +59,31 @@ void burst_floor_reset(Plan& P) {
   be_h2d_sync(P.bursts.d_floor, f.data(), f.size() * sizeof(float));
 }
 
+// ---- the bursts' section of the state blob: ring (the sorted top-K lists) | counts
+static size_t burst_state_bytes(const Plan& P) { return P.bursts.top_bytes + P.bursts.counts_bytes; }
+static void burst_state_reset(Plan& P) {
+  if (!P.have_bursts) return;
+  BurstStage& B = P.bursts;
+  be_memset_sync(B.d_top, 0, B.top_bytes);
+  be_memset_sync(B.d_counts, 0, B.counts_bytes);
+  burst_floor_reset(P);
+  B.seen = 0;
+}
+static void burst_state_export(const Plan& P, char* q) {
+  if (!P.have_bursts) return;
+  be_d2h_sync(q, P.bursts.d_top, P.bursts.top_bytes);
+  be_d2h_sync(q + P.bursts.top_bytes, P.bursts.d_counts, P.bursts.counts_bytes);
+}
+static int burst_state_import(Plan& P, const char* q, size_t) {
+  if (!P.have_bursts) return 0;
+  BurstStage& B = P.bursts;
+  be_h2d_sync(B.d_top, q, B.top_bytes);
+  be_h2d_sync(B.d_counts, q + B.top_bytes, B.counts_bytes);
+  memcpy(&B.seen, q + B.top_bytes + sizeof(long long), sizeof(long long));   // counts[0][1]
+  burst_floor_reset(P);   // (a bound of the history this plan had, not of the imported one: the next steady walk writes it anew)
+  return 0;
+}
+
 int build_bursts(Plan& P) {
   const nmx_plan_desc& d = P.d;
   if (!(d.features & NMX_F_BURSTS)) return 0;
@@ -121,13 +146,10 @@ int build_bursts(Plan& P) {
   const size_t n_state = (size_t)d.n_channels * d.n_burst_bands;
   B.top_bytes = n_state * T.K * sizeof(float);
   B.counts_bytes = n_state * 2 * sizeof(long long);
-  B.d_top = (float*)be_alloc(B.top_bytes);
-  B.d_counts = (long long*)be_alloc(B.counts_bytes);
-  B.d_floor = (float*)be_alloc(n_state * sizeof(float));
+  B.d_top = (float*)plan_alloc(P, B.top_bytes);
+  B.d_counts = (long long*)plan_alloc(P, B.counts_bytes);
+  B.d_floor = (float*)plan_alloc(P, n_state * sizeof(float));
   if (!B.d_top || !B.d_counts || !B.d_floor) return nmx_fail(NMX_E_NOMEM, "burst state allocation failed");
-  be_memset_sync(B.d_top, 0, B.top_bytes);
-  be_memset_sync(B.d_counts, 0, B.counts_bytes);
-  burst_floor_reset(P);
   // ---- the chain's kernels and the walk's schedule (launch_burst_stage only dispatches on them) ----
   B.own_hilbert = P.bank.w64 || P.bank.a.partitioned;   // (build_bank, which ran before, has called build_hilbert for it)
   B.fill_split = env_int("NMX_FILL_SPLIT", 1) != 0;
@@ -144,6 +166,7 @@ int build_bursts(Plan& P) {
                 : d.window <= 1024 ? (B.sparse ? NMX_BSTAT_REG16_SPARSE : NMX_BSTAT_REG16)
                                    : (B.sparse ? NMX_BSTAT_REG32_SPARSE : NMX_BSTAT_REG32);
   P.have_bursts = true;
+  burst_state_reset(P);
   return 0;
 }
 

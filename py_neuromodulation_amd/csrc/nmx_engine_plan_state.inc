@@ -1,11 +1,69 @@
-// nmx_engine_plan_state.inc -- plan building, part 3: raw normaliser, preprocessing_filter stages, bursts, resampler,
-// Kalman, sharp waves, re-reference structure.  Included by nmx_engine.inc.
-static void rawnorm_reset(Plan& P) {
-  be_memset_sync(P.rn.ring, 0, P.rn_ring_bytes);
-  be_memset_sync(P.rn.count, 0, P.rn_cnt_bytes);
-  be_memset_sync(P.rn.len, 0, P.rn_len_bytes);
-  P.rn_hops = 0;
-  P.rn_sorted_valid = false;
+// nmx_engine_plan_state.inc -- plan building, part 3: raw normaliser, preprocessing_filter stages, resampler, Kalman,
+// sharp waves, re-reference structure; the state-blob sections of the raw normaliser and the Kalman filters beside their
+// build functions (rawnorm_state_*, kalman_state_*: the table that walks them is in nmx_engine_abi.inc).  Included by nmx_engine.inc.
+// ---- the raw normaliser's section of the state blob: hops seen | ring capacity of the exporting plan | rings | counts | lengths.
+// The capacity depends on the window length; a stream with ragged window lengths hands the blob of one plan to the plan
+// of the other length, which re-lays the histories into its own rings (rawnorm_state_import).
+static size_t rawnorm_state_bytes_cap(const Plan& P, long long cap) {
+  return 2 * sizeof(long long) + (size_t)P.d.n_channels * (size_t)cap * sizeof(float) + P.rawnorm.cnt_bytes + P.rawnorm.len_bytes;
+}
+static size_t rawnorm_state_bytes(const Plan& P) { return P.have_rawnorm ? rawnorm_state_bytes_cap(P, P.rawnorm.a.cap) : 0; }
+// the section's size in a blob that holds `left` bytes from its start `q` on: by the exporting plan's capacity
+static int rawnorm_state_bytes_in(const Plan& P, const char* q, size_t left, size_t* n) {
+  *n = 0;
+  if (!P.have_rawnorm) return 0;
+  long long src_cap = P.rawnorm.a.cap;
+  if (left >= 2 * sizeof(long long)) memcpy(&src_cap, q + sizeof(long long), sizeof(long long));
+  NMX_REQUIRE(src_cap > 0 && src_cap < (1ll << 31), "state blob: bad raw-normaliser header");
+  *n = rawnorm_state_bytes_cap(P, src_cap);
+  return 0;
+}
+static void rawnorm_state_reset(Plan& P) {
+  if (!P.have_rawnorm) return;
+  RawNormStage& S = P.rawnorm;
+  be_memset_sync(S.a.ring, 0, S.ring_bytes);
+  be_memset_sync(S.a.count, 0, S.cnt_bytes);
+  be_memset_sync(S.a.len, 0, S.len_bytes);
+  S.hops = 0;
+  S.sorted_valid = false;
+}
+static void rawnorm_state_export(const Plan& P, char* q) {
+  if (!P.have_rawnorm) return;
+  const RawNormStage& S = P.rawnorm;
+  const long long cap = S.a.cap;
+  memcpy(q, &S.hops, sizeof(long long)); q += sizeof(long long);
+  memcpy(q, &cap, sizeof(long long)); q += sizeof(long long);
+  be_d2h_sync(q, S.a.ring, S.ring_bytes); q += S.ring_bytes;
+  be_d2h_sync(q, S.a.count, S.cnt_bytes); q += S.cnt_bytes;
+  be_d2h_sync(q, S.a.len, S.len_bytes);
+}
+static int rawnorm_state_import(Plan& P, const char* q, size_t n) {   // (n: what rawnorm_state_bytes_in said)
+  if (!P.have_rawnorm) return 0;
+  RawNormStage& S = P.rawnorm;
+  const int C = P.d.n_channels, cap = S.a.cap;
+  const long long src_cap = (long long)((n - rawnorm_state_bytes_cap(P, 0)) / ((size_t)C * sizeof(float)));
+  memcpy(&S.hops, q, sizeof(long long)); q += 2 * sizeof(long long);
+  const float* ring_src = (const float*)q;
+  const char* cnt_src = q + (size_t)C * (size_t)src_cap * sizeof(float);
+  const char* len_src = cnt_src + S.cnt_bytes;
+  if (src_cap == cap) {
+    be_h2d_sync(S.a.ring, ring_src, S.ring_bytes);
+  } else {   // a plan of another window length exported this: the same histories at the same sample counts, re-laid
+    std::vector<float> ring((size_t)C * cap, 0.f);
+    for (int c = 0; c < C; ++c) {
+      long long cnt;
+      int len;
+      memcpy(&cnt, cnt_src + (size_t)c * sizeof(long long), sizeof(long long));
+      memcpy(&len, len_src + (size_t)c * sizeof(int), sizeof(int));
+      NMX_REQUIRE(len >= 0 && len <= cap && len <= src_cap && cnt >= len, "state blob: raw-normaliser history does not fit this plan");
+      for (long long i = cnt - len; i < cnt; ++i) ring[(size_t)c * cap + (size_t)(i % cap)] = ring_src[(size_t)c * src_cap + (size_t)(i % src_cap)];
+    }
+    be_h2d_sync(S.a.ring, ring.data(), S.ring_bytes);
+  }
+  be_h2d_sync(S.a.count, cnt_src, S.cnt_bytes);
+  be_h2d_sync(S.a.len, len_src, S.len_bytes);
+  S.sorted_valid = false;   // the sorted copies are rebuilt from the imported rings
+  return 0;
 }
 
 int build_rawnorm(Plan& P) {
@@ -15,31 +73,30 @@ int build_rawnorm(Plan& P) {
               "raw normalisation method outside 1..8 (mean, zscore, median, zscore-median, robust, minmax, quantile, power)");
   NMX_REQUIRE(d.raw_norm_n >= 2 && d.raw_norm_add >= 1 && d.raw_norm_add <= d.window,
               "raw normalisation: need N >= 2 and 1 <= int(sfreq / feat_hz) <= window");
-  NmxRawNormArgs& A = P.rn;
+  RawNormStage& S = P.rawnorm;
+  NmxRawNormArgs& A = S.a;
   A.n_channels = d.n_channels; A.W = d.window;
   A.add = d.raw_norm_add; A.keep = d.raw_norm_n - 1;
   A.cap = std::max(d.window, A.keep) + A.add + 64;
   A.method = d.raw_norm_method; A.clip = d.raw_norm_clip;
-  P.rn_ring_bytes = (size_t)d.n_channels * A.cap * sizeof(float);
-  P.rn_cnt_bytes = (size_t)d.n_channels * sizeof(long long);
-  P.rn_len_bytes = (size_t)d.n_channels * sizeof(int);
-  A.ring = (float*)be_alloc(P.rn_ring_bytes);
-  A.count = (long long*)be_alloc(P.rn_cnt_bytes);
-  A.len = (int*)be_alloc(P.rn_len_bytes);
+  S.ring_bytes = (size_t)d.n_channels * A.cap * sizeof(float);
+  S.cnt_bytes = (size_t)d.n_channels * sizeof(long long);
+  S.len_bytes = (size_t)d.n_channels * sizeof(int);
+  A.ring = (float*)plan_alloc(P, S.ring_bytes);
+  A.count = (long long*)plan_alloc(P, S.cnt_bytes);
+  A.len = (int*)plan_alloc(P, S.len_bytes);
   if (!A.ring || !A.count || !A.len) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
   if (A.method == NMX_RAWNORM_POWER) {   // sign(x) log1p|x| of every ring sample (rebuilt inside the kernel when stale)
-    A.ring_sl = (double*)be_alloc((size_t)d.n_channels * A.cap * sizeof(double));
+    A.ring_sl = (double*)plan_alloc(P, (size_t)d.n_channels * A.cap * sizeof(double));
     if (!A.ring_sl) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-    P.tables.push_back(A.ring_sl);
   } else if (A.method >= NMX_RAWNORM_MEDIAN) {   // the history sorted, double-buffered; rebuilt from the ring when stale
     if (A.method == NMX_RAWNORM_QUANTILE) {
-      A.sub = (float*)be_alloc((size_t)d.n_channels * NMX_RAWNORM_SUBSAMPLE * sizeof(float));
+      A.sub = (float*)plan_alloc(P, (size_t)d.n_channels * NMX_RAWNORM_SUBSAMPLE * sizeof(float));
       if (!A.sub) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-      P.tables.push_back(A.sub);
       A.seed = (unsigned)env_int("NMX_QUANTILE_SEED", 20250929);
     }
-    A.sorted = (float*)be_alloc((size_t)d.n_channels * 2 * A.cap * sizeof(float));
-    A.cur = (int*)be_alloc((size_t)d.n_channels * sizeof(int));
+    A.sorted = (float*)plan_alloc(P, (size_t)d.n_channels * 2 * A.cap * sizeof(float));
+    A.cur = (int*)plan_alloc(P, (size_t)d.n_channels * sizeof(int));
     if (!A.sorted || !A.cur) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
     be_memset_sync(A.cur, 0, (size_t)d.n_channels * sizeof(int));
     A.max_list = (d.window + A.add + 1) & ~1;
@@ -47,13 +104,12 @@ int build_rawnorm(Plan& P) {
     // samples, in device memory beyond
     A.lists = nullptr;
     if ((size_t)24 * A.max_list + 8 * 1024 > 160 * 1024 || env_int("NMX_RAWNORM_GLOBAL_LISTS", 0)) {
-      A.lists = (float*)be_alloc((size_t)d.n_channels * 6 * A.max_list * sizeof(float));
+      A.lists = (float*)plan_alloc(P, (size_t)d.n_channels * 6 * A.max_list * sizeof(float));
       if (!A.lists) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-      P.tables.push_back(A.lists);
     }
   }
-  rawnorm_reset(P);
   P.have_rawnorm = true;
+  rawnorm_state_reset(P);
   return 0;
 }
 
@@ -61,27 +117,28 @@ int build_rawnorm(Plan& P) {
 static int run_rawnorm(Plan& P, const float*& src, long long& ch_stride, long long& win_stride,
                        const long long*& starts, int nw, int clean, be_stream_t s) {
   const int C = P.d.n_channels, W = P.d.window;
+  RawNormStage& S = P.rawnorm;
   int rc;
-  if ((rc = ensure(P.x_rn, (size_t)nw * C * W * sizeof(float)))) return rc;
-  if ((rc = ensure(P.rn_mean, (size_t)nw * C * sizeof(float)))) return rc;
-  if ((rc = ensure(P.rn_scale, (size_t)nw * C * sizeof(float)))) return rc;
-  NmxRawNormArgs A = P.rn;
+  if ((rc = ensure(S.x_rn, (size_t)nw * C * W * sizeof(float)))) return rc;
+  if ((rc = ensure(S.mean, (size_t)nw * C * sizeof(float)))) return rc;
+  if ((rc = ensure(S.scale, (size_t)nw * C * sizeof(float)))) return rc;
+  NmxRawNormArgs A = S.a;
   A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
-  A.y = (float*)P.x_rn.p; A.n_windows = nw; A.hop0 = P.rn_hops;
-  A.mean = (float*)P.rn_mean.p; A.scale = (float*)P.rn_scale.p; A.clean_on_load = clean;
-  A.sorted_valid = P.rn_sorted_valid ? 1 : 0;
+  A.y = (float*)S.x_rn.p; A.n_windows = nw; A.hop0 = S.hops;
+  A.mean = (float*)S.mean.p; A.scale = (float*)S.scale.p; A.clean_on_load = clean;
+  A.sorted_valid = S.sorted_valid ? 1 : 0;
   if (A.method == NMX_RAWNORM_QUANTILE) {
-    if ((rc = ensure(P.rn_qt, (size_t)nw * C * NMX_RAWNORM_NQ * sizeof(double)))) return rc;
-    if ((rc = ensure(P.rn_qn, (size_t)nw * C * sizeof(int)))) return rc;
-    A.qt = (double*)P.rn_qt.p; A.qn = (int*)P.rn_qn.p;
+    if ((rc = ensure(S.qt, (size_t)nw * C * NMX_RAWNORM_NQ * sizeof(double)))) return rc;
+    if ((rc = ensure(S.qn, (size_t)nw * C * sizeof(int)))) return rc;
+    A.qt = (double*)S.qt.p; A.qn = (int*)S.qn.p;
   } else if (A.method == NMX_RAWNORM_POWER) {
-    if ((rc = ensure(P.rn_qt, (size_t)nw * C * 3 * sizeof(double)))) return rc;
-    A.pw = (double*)P.rn_qt.p;
+    if ((rc = ensure(S.qt, (size_t)nw * C * 3 * sizeof(double)))) return rc;
+    A.pw = (double*)S.qt.p;
   }
   be_launch_rawnorm(A, s);
-  P.rn_sorted_valid = true;
-  P.rn_hops += nw;
-  src = (const float*)P.x_rn.p;
+  S.sorted_valid = true;
+  S.hops += nw;
+  src = (const float*)S.x_rn.p;
   ch_stride = W; win_stride = (long long)C * W; starts = nullptr;
   return 0;
 }
@@ -176,12 +233,22 @@ int build_resample(Plan& P) {
   return 0;
 }
 
-static void kalman_reset(Plan& P) {
-  std::vector<double> st(P.kf_bytes / sizeof(double));
+// ---- the Kalman section of the state blob: x, P of every (channel, band) filter
+static size_t kalman_state_bytes(const Plan& P) { return P.kalman.bytes; }
+static void kalman_state_reset(Plan& P) {
+  if (!P.have_kalman) return;
+  std::vector<double> st(P.kalman.bytes / sizeof(double));
   for (size_t i = 0; i + 5 < st.size(); i += 6) {   // x = [0, 1], P = cov([[1, 0], [0, 1]])
     st[i] = 0.0; st[i + 1] = 1.0; st[i + 2] = 0.5; st[i + 3] = -0.5; st[i + 4] = -0.5; st[i + 5] = 0.5;
   }
-  be_h2d_sync(P.d_kf, st.data(), P.kf_bytes);
+  be_h2d_sync(P.kalman.d_state, st.data(), P.kalman.bytes);
+}
+static void kalman_state_export(const Plan& P, char* q) {
+  if (P.have_kalman) be_d2h_sync(q, P.kalman.d_state, P.kalman.bytes);
+}
+static int kalman_state_import(Plan& P, const char* q, size_t) {
+  if (P.have_kalman) be_h2d_sync(P.kalman.d_state, q, P.kalman.bytes);
+  return 0;
 }
 
 int build_kalman(Plan& P) {
@@ -189,18 +256,18 @@ int build_kalman(Plan& P) {
   if (!(d.features & NMX_F_BANDPOWER) || !(d.bp_features & 1u) || !d.bp_kalman_mask) return 0;
   NMX_REQUIRE(d.kalman_Tp > 0 && d.kalman_sigma_v > 0, "Kalman Tp and sigma_v must be positive");
   NMX_REQUIRE((d.bp_kalman_mask >> d.n_bands) == 0u, "Kalman band outside frequency_ranges_hz");
-  NmxKalmanArgs& K = P.kal;
+  NmxKalmanArgs& K = P.kalman.a;
   K.n_outputs = d.n_outputs + d.n_extra_cols; K.n_channels = d.n_channels; K.n_bands = d.n_bands;
   K.mask = d.bp_kalman_mask; K.cols = cv(d.bp_cols);
   const double T = d.kalman_Tp, sw2 = d.kalman_sigma_w * d.kalman_sigma_w;
   K.Tp = T; K.R = d.kalman_sigma_v;
   K.q00 = sw2 * T * T * T / 3.0; K.q01 = sw2 * T * T / 2.0; K.q11 = sw2 * T;
-  P.kf_bytes = (size_t)d.n_channels * d.n_bands * 6 * sizeof(double);
-  P.d_kf = (double*)be_alloc(P.kf_bytes);
-  if (!P.d_kf) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
-  K.state = P.d_kf;
-  kalman_reset(P);
+  const size_t bytes = (size_t)d.n_channels * d.n_bands * 6 * sizeof(double);
+  K.state = P.kalman.d_state = (double*)plan_alloc(P, bytes);
+  if (!K.state) return nmx_fail(NMX_E_NOMEM, "device allocation failed");
+  P.kalman.bytes = bytes;
   P.have_kalman = true;
+  kalman_state_reset(P);
   return 0;
 }
 

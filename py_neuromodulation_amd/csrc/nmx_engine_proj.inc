@@ -7,7 +7,7 @@ struct NmxProjHandle {
   NmxProjArgs a{};          // argument template: device tables, shape, tile (rows / ld / n_rows per call)
   long long min_ld = 0;     // the last column read or written + 1
   long long first_out = 0;  // the first column written (every gathered column lies in front of it)
-  void* d_tab = nullptr;    // w | gather | ptr | idx | out_col | out_stride | point_group (one allocation)
+  Buf tab;                  // w | gather | ptr | idx | out_col | out_stride | point_group (one allocation)
   Buf stage;                // host calls: rows [first gathered column, min_ld) of a batch
   long long first_in = 0;
   be_stream_t stream = nullptr;
@@ -57,9 +57,8 @@ int nmx_proj_create(int32_t device, const nmx_proj_desc* desc, nmx_proj** out) {
                        (n_gather + (size_t)D.n_points + 1 + (size_t)nnz + 3 * (size_t)D.n_points) * sizeof(int32_t);
   NmxProjHandle* H = new NmxProjHandle();
   H->device = device;
-  H->d_tab = be_alloc(bytes);
-  if (!H->d_tab) { delete H; return nmx_fail(NMX_E_NOMEM, "device allocation failed"); }
-  char* p = (char*)H->d_tab;
+  if (!H->tab.regrow(bytes)) { delete H; return nmx_fail(NMX_E_NOMEM, "device allocation failed"); }
+  char* p = (char*)H->tab.p;
   auto put = [&](const void* src, size_t n) -> void* {
     void* at = p;
     if (n) be_h2d_sync(at, src, n);
@@ -93,8 +92,6 @@ int nmx_proj_destroy(nmx_proj* proj) {
   if (!H) return 0;
   be_set_device(H->device);
   be_sync(H->stream);
-  if (H->d_tab) be_free(H->d_tab);
-  if (H->stage.p) be_free(H->stage.p);
   be_stream_destroy(H->stream);
   delete H;
   return 0;

@@ -186,7 +186,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     }
     launch_fir_stage(P, P.bank, A, nw * C, s, tev);
     if (P.have_kalman) {   // sequential over the hops of the chunk; chunks run in order on `s`
-      NmxKalmanArgs K = P.kal;
+      NmxKalmanArgs K = P.kalman.a;
       K.out = d_out; K.n_windows = nw;
       be_launch_kalman(K, s);
     }
@@ -497,10 +497,7 @@ int nmx_process_window(nmx_plan* plan, const double* x, int64_t ldx, float* out,
   if (P->win_pin.cap < need) {
     int rc = be_set_device(P->device);
     if (rc) return rc;
-    if (P->win_pin.p) be_host_free(P->win_pin.p);
-    P->win_pin.p = be_host_alloc(need);
-    P->win_pin.cap = P->win_pin.p ? need : 0;
-    if (!P->win_pin.p) return nmx_fail(NMX_E_NOMEM, "page-locked host allocation failed");
+    if (!P->win_pin.regrow(need)) return nmx_fail(NMX_E_NOMEM, "page-locked host allocation failed");
   }
   float* xf = (float*)P->win_pin.p;
   float* of = (float*)((char*)P->win_pin.p + xb);

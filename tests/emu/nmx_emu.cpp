@@ -7,6 +7,7 @@
 // package loader only ever opens libnmx.so (HIP); nothing under py_neuromodulation_amd/
 // references this file, and wave-level behaviour (races, barriers, shuffles) is only
 // exercised by the -m gpu tests on the MI355X.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -34,12 +35,15 @@ static int nmx_fail(int code, const std::string& msg);
 
 static int be_device_count() { return 1; }
 static int be_set_device(int) { return 0; }
-static void* be_alloc(size_t n) { return calloc(1, n ? n : 4); }
-static void be_free(void* p) { free(p); }
+// blocks handed out and not yet given back, "device" and page-locked together (nmx_emu_live_blocks below:
+// tests/test_plan_lifetime_cpu.py)
+static std::atomic<long long> g_live_blocks{0};
+static void* be_alloc(size_t n) { ++g_live_blocks; return calloc(1, n ? n : 4); }
+static void be_free(void* p) { if (p) --g_live_blocks; free(p); }
 static void be_dev_pool_age() {}
 static long long be_dev_pool_trim(long long) { return 0; }
-static void* be_host_alloc(size_t n) { return malloc(n ? n : 4); }
-static void be_host_free(void* p) { free(p); }
+static void* be_host_alloc(size_t n) { ++g_live_blocks; return malloc(n ? n : 4); }
+static void be_host_free(void* p) { if (p) --g_live_blocks; free(p); }
 static void be_h2d_sync(void* d, const void* s, size_t n) { memcpy(d, s, n); }
 static void be_d2h_sync(void* d, const void* s, size_t n) { memcpy(d, s, n); }
 static void be_memset_sync(void* d, int v, size_t n) { memset(d, v, n); }
@@ -210,3 +214,6 @@ static void be_launch_tap(const NmxTapArgs& A, int n_items, be_stream_t) {
 }
 
 #include "../../py_neuromodulation_amd/csrc/nmx_engine.inc"
+
+// the emulator library's own export (not part of include/nmx.h)
+extern "C" long long nmx_emu_live_blocks(void) { return g_live_blocks.load(); }
