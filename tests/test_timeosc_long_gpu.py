@@ -67,10 +67,11 @@ def _batch(e, W, hops=5, seed=5):
     return e.process_batch(x, np.arange(hops, dtype=np.int64) * (W // 10)).copy()
 
 
-@pytest.mark.parametrize("W,wide", [(30000, False), (20000, True)])
+@pytest.mark.parametrize("W,wide", [(30000, False), (20000, True), (20001, True)])
 def test_persistent_loop_reuses_lds_and_slab(W, wide):
     """NMX_TIMEOSC_LONG_BLOCKS=3 (read when the plan is built): ten items on three workgroups, each reusing its LDS --
-    and, with the wide band, its slab of device memory -- for three or four items; bit-identical to the uncapped run."""
+    and, with the wide band, its slab of device memory -- for three or four items; bit-identical to the uncapped run.
+    20 001: three subsequences of 6667 samples, an odd length (the full complex transform of each)."""
     feats = ["raw_hjorth", "return_raw", "linelength", "fft", "welch"]
     e = _engine(W, feats, wide)
     want = _batch(e, W)
