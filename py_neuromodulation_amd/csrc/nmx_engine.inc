@@ -36,7 +36,7 @@ static int nmx_fail(int code, const std::string& msg) {
 
 #ifdef NMX_HOST_EMU
 // The logic emulator (tests/emu) runs the item code of every stage, whatever kernel the plan chose: its launch interface
-// carries none of those choices (it runs the matrix-pipe spectrum's arithmetic when run_chunk hands it `todo`).
+// carries none of those choices (it runs the matrix-pipe spectrum's arithmetic when launch_timeosc_stage hands it `todo`).
 static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind, int n, int nt, size_t lds, int, be_stream_t s) { be_launch_timeosc(A, n, nt, lds, s); }
 static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind, long long n, size_t lds, be_stream_t s) { be_launch_hilbert(A, n, 128, lds, s); }
 static void be_launch_bank_w64(const NmxBankW64Args& A, int n, size_t lds, int, be_stream_t s) { be_launch_bank_w64(A, n, lds, s); }
@@ -75,6 +75,54 @@ struct Block {
 using Buf = Block<be_alloc, be_free>;                 // device memory (ensure)
 using HostBuf = Block<be_host_alloc, be_host_free>;   // page-locked host memory
 
+// Where the next stage reads its windows: window w of channel c begins at x + c * ch_stride + (starts ? starts[w] :
+// w * win_stride).  run_chunk and nmx_preprocess_window keep one and hand it from stage to stage; every stage that writes
+// windows sets it to its output.
+struct WinView {
+  const float* x;
+  long long ch_stride, win_stride;
+  const long long* starts;
+  int clean;           // NaN / infinity are still in the samples: the reader cleans on load
+};
+template <class Args>
+void view_into(Args& A, const WinView& v) {
+  A.x = v.x; A.ch_stride = v.ch_stride; A.win_stride = v.win_stride; A.starts = v.starts; A.clean_on_load = v.clean;
+}
+void view_into(NmxTapArgs& A, const WinView& v) {
+  A.x = v.x; A.ch_stride = v.ch_stride; A.win_stride = v.win_stride; A.starts = v.starts; A.clean = v.clean;
+}
+// the next stage reads y, laid out [nw][C][w] (and clean)
+WinView dense_view(const void* y, int C, int w) { return WinView{(const float*)y, w, (long long)C * w, nullptr, 0}; }
+
+// The front end of a chunk or of one window: the re-reference -- or, in a plan without one, the offset shift
+// (nmx_engine_plan_state.inc: build_front, launch_front).
+struct FrontStage {
+  float* d_R = nullptr;      // [C][C_in] re-reference matrix, fp32 (the plan's block: upload); null: the plan has none
+  bool car = false;          // R = (d - o) I + o 11^T: column-sum kernel instead of the dense product
+  float car_diag = 0.f, car_off = 0.f;
+  bool structured = false;   // taps + group-sum structure found in R (nmx_k_prep.h: NmxRerefStructArgs)
+  NmxRerefStructArgs rst{};
+  Buf x_ref;                 // the re-referenced / shifted sample range of a chunk
+};
+// The time / oscillatory kernel, chosen at plan time (nmx_engine_plan_spectral.inc: build_timeosc, launch_timeosc_stage).
+struct TimeOscStage {
+  NmxTimeOscArgs a{};        // argument template
+  NmxTimeOscKind kind = NMX_TO_GENERIC;
+  bool takes_dc = true;      // the kernel adds the carried offset on load (else: it reads a copy with it added back, dc_windows)
+  int nt = 64;               // threads per workgroup of the generic kernels
+  Buf todo;                  // flags of the matrix-pipe spectrum kernel (NmxTimeOscArgs::todo)
+};
+// Coherence between channel pairs (nmx_k_coh.h; nmx_engine_plan_spectral.inc: build_coh, launch_coh_stage): stateless.
+struct CohStage {
+  NmxCohArgs a{};            // argument template
+};
+// The resampler, behind the notch (nmx_engine_plan_state.inc: build_resample, launch_resample).
+struct ResampleStage {
+  NmxResampleArgs a{};       // argument template
+  int nt = 256;
+  Buf y;                     // resampled windows of a chunk
+};
+
 // A FIR stage -- a preprocessing_filter stage, the notch or the band-pass bank -- with its kernels decided at plan time
 // (nmx_engine_plan_fir.inc: build_fir_stage, launch_fir_stage).  One launch of its one-wave kernels: the filters of
 // `mask` on kernel `kernel`; the channel-pair kinds come with the tables of nmx_k_bank_w64c/d/e.h (build_pair_tables).
@@ -92,8 +140,8 @@ struct FirStage {
   bool w64 = false;    // one-wave kernels (M = 2048 / 4096) ...
   NmxBankW64Args w{};  // ... and their template
   std::vector<FirLaunch> launches;   // (the LDS kernels: one entry, for its stage)
-  bool takes_dc = true;   // its kernels add the carried offset on load (NmxBankArgs::dcf; else run_chunk hands them a copy of
-                          // the windows with the offset added back): set by fir_stage_finish
+  bool takes_dc = true;   // its kernels add the carried offset on load (NmxBankArgs::dcf; else they read a copy of the windows
+                          // with the offset added back, dc_windows): set by fir_stage_finish
 };
 
 // The bursts chain -- Hilbert envelope (where the bank leaves band series), threshold walk, run statistics -- with its kernels
@@ -180,11 +228,8 @@ struct Plan {
   ~Plan() { for (void* t : tables) be_free(t); }   // (and every Buf frees itself: nmx_plan_destroy has set the device)
   std::map<int, NmxFft> fft_cache;
   std::map<int, const float2*> twn_cache;   // exp(-2 pi i k / n), k < n, of the long-window kernel's combination step (NmxOsc::tw_n)
-  // kernel argument templates (per-call fields are patched in process_batch)
-  NmxTimeOscArgs to{};
-  bool have_to = false;
-  NmxTimeOscKind to_kind = NMX_TO_GENERIC;
-  bool to_takes_dc = true;            // the kernel adds the carried offset on load (else: it reads a copy with it added back)
+  // the stages of a chunk (run_chunk): argument templates and kinds decided when the plan is built, one launcher each
+  FrontStage front;                   // re-reference or offset shift
   FirStage bank;                      // band-pass bank: feeds bursts and sharp waves
   bool have_bank = false;
   FirStage notch;
@@ -193,37 +238,32 @@ struct Plan {
                                       // spectrum in LDS as well, one exchange tile fewer -- kept for measurement)
   std::vector<FirStage> pre;          // preprocessing_filter stages (one filter each)
   const float* w64e_tw = nullptr;     // twiddles of the M = 2048 channel-pair kernel (nmx_k_bank_w64e.h): notch and bank
-  const float* w500_tab = nullptr;
+  const float* w500_tab = nullptr;    // tables of the wave-level 500-point transform: time / oscillatory and Hilbert kernels
   BurstStage bursts;                  // bursts chain: behind the bank
   bool have_bursts = false;
   SharpStage sharp;                   // sharp-wave analysis: likewise
   bool have_sharp = false;
-  NmxCohArgs coh{};        // coherence between channel pairs (nmx_k_coh.h)
+  TimeOscStage timeosc;               // time / oscillatory kernel
+  bool have_timeosc = false;
+  CohStage coherence;                 // coherence between channel pairs
   bool have_coh = false;
-  float* d_R = nullptr;
-  bool car = false;      // R = (d - o) I + o 11^T: column-sum kernel instead of the dense product
-  float car_diag = 0.f, car_off = 0.f;
-  bool rs_ok = false;    // taps + group-sum structure found in R (nmx_k_prep.h: NmxRerefStructArgs)
-  NmxRerefStructArgs rst{};
-  int nt_timeosc = 64, nt_bank = 256;
+  int nt_bank = 256;
   int chunk_windows = 1024;
   bool tiny_inline = true;          // host batches of a few hops on ONE stream (nmx_engine_run.inc)
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
   // scratch
-  Buf to_todo;        // flags of the matrix-pipe spectrum kernel (NmxTimeOscArgs::todo)
   Buf tap;            // pre-processed windows of a chunk on their way to a host caller (nmx_process_batch_tap)
-  Buf x_in, x_in2[2], x_ref, x_rs, x_pf[2], y_notch, out, starts, mask;
+  Buf x_in, x_in2[2], x_pf[2], y_notch, out, starts, mask;
   HostBuf win_pin;    // page-locked HOST staging of the one-window call (nmx_process_window): cast input, feature row, mask
   // state
   KalmanStage kalman;
   bool have_kalman = false;
-  NmxResampleArgs rs{};
+  ResampleStage resample;             // raw_resampling, behind the notch
   bool have_resample = false;
   RawNormStage rawnorm;
   bool have_rawnorm = false;
   std::vector<std::vector<double>> pre_taps;
   int w_in = 0;           // samples per incoming window (raw_window when resampling, else window)
-  int nt_resample = 256;
   be_timer_t timers[9];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence,
                           // 8 grid projection
   std::string kernels[9];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
@@ -281,11 +321,11 @@ int env_int(const char* name, int dflt) {
   return (v && v[0] >= '0' && v[0] <= '9') ? atoi(v) : dflt;
 }
 
+#include "nmx_engine_dc.inc"
 #include "nmx_engine_plan_spectral.inc"
 #include "nmx_engine_plan_bursts.inc"
 #include "nmx_engine_plan_fir.inc"
 #include "nmx_engine_plan_state.inc"
-#include "nmx_engine_dc.inc"
 
 }  // namespace
 

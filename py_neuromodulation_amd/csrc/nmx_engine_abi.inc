@@ -141,31 +141,16 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
     const size_t n = (size_t)desc->n_channels * desc->n_channels_in;
     P->ref_matrix.assign(desc->ref_matrix, desc->ref_matrix + n);
     P->d.ref_matrix = P->ref_matrix.data();
-    std::vector<float> Rf(n);
-    for (size_t i = 0; i < n; ++i) Rf[i] = (float)P->ref_matrix[i];
-    P->d_R = (float*)upload(*P, Rf.data(), n * sizeof(float));
-    if (!P->d_R) return nmx_fail(NMX_E_NOMEM, "ref matrix");
-    const int C = desc->n_channels;
-    if (desc->n_channels_in == C && C >= 2 && env_int("NMX_CAR_FAST", 1)) {
-      const double dg = P->ref_matrix[0], of = P->ref_matrix[1];
-      bool ok = true;
-      for (int i = 0; i < C && ok; ++i)
-        for (int j = 0; j < C; ++j)
-          if (std::fabs(P->ref_matrix[(size_t)i * C + j] - (i == j ? dg : of)) > 1e-12) { ok = false; break; }
-      if (ok) { P->car = true; P->car_diag = (float)dg; P->car_off = (float)of; }
-    }
-    if (!P->car && env_int("NMX_REREF_STRUCT", 1) && (rc = find_reref_structure(*P))) return rc;
   } else {
     P->d.n_channels_in = desc->n_channels;
   }
-  P->nt_timeosc = desc->window <= 1024 ? 128 : 256;
   P->nt_bank = 256;
   P->tiny_inline = env_int("NMX_TINY_INLINE", 1) != 0;
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
-  if ((rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) || (rc = build_notch(*P)) ||
-      (rc = build_bursts(*P)) || (rc = build_sharp(*P)) || (rc = build_kalman(*P)) || (rc = build_resample(*P)) ||
-      (rc = build_prefilters(*P)) || (rc = build_rawnorm(*P)) || (rc = dc_build(*P)))
+  if ((rc = build_front(*P)) || (rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) ||
+      (rc = build_notch(*P)) || (rc = build_bursts(*P)) || (rc = build_sharp(*P)) || (rc = build_kalman(*P)) ||
+      (rc = build_resample(*P)) || (rc = build_prefilters(*P)) || (rc = build_rawnorm(*P)) || (rc = dc_build(*P)))
     return rc;
 #ifndef NMX_HOST_EMU
   choose_notch_bank_fuse(*P);   // (behind every stage's own choice: it reads the notch's, the bank's and what sits between them)

@@ -89,7 +89,7 @@ static int dc_build(Plan& P) {
 // re-reference or notch kernel, no host offsets), refresh the device tables when anything changed.
 static int dc_prepare(Plan& P, const float* x, long long ldx, long long t0, bool host, be_stream_t s) {
   if (!P.dc_ok) return 0;
-  if (P.dc_auto && (P.d_R || P.have_notch) && !P.dc_host_set && !P.dc_learned) {
+  if (P.dc_auto && (P.front.d_R || P.have_notch) && !P.dc_host_set && !P.dc_learned) {
     // the first window the plan sees: a row is split at its mean there when that level exceeds four times the
     // row's spread -- a recording without offsets keeps its samples as they are
     const int Cin = P.d.n_channels_in, Wi = P.w_in;
@@ -130,6 +130,40 @@ static int dc_prepare(Plan& P, const float* x, long long ldx, long long t0, bool
     P.dc_dirty = true;
   }
   if (P.dc_dirty) dc_recompute(P, s);
+  return 0;
+}
+
+// ---- consumers of the pre-processed windows `v` of a chunk (nw hops) ----------------------------------------------------
+// The windows with the offset added back, dense [nw][C][W], for a kernel that cannot take the offset on load.  `made`
+// (run_chunk's, false when the chunk starts): x_dc holds this chunk's windows already -- one copy serves every such reader.
+static int dc_windows(Plan& P, const WinView& v, int nw, be_stream_t s, bool& made, WinView* dense) {
+  const int C = P.d.n_channels, W = P.d.window;
+  if (!made) {
+    int rc = ensure(P.x_dc, (size_t)nw * C * W * sizeof(float));
+    if (rc) return rc;
+    NmxTapArgs T{};
+    view_into(T, v);
+    T.y = (float*)P.x_dc.p; T.C = C; T.W = W; T.add = P.d_dc_pref;
+    be_launch_tap(T, nw * C, s);
+    made = true;
+  }
+  *dense = dense_view(P.x_dc.p, C, W);
+  return 0;
+}
+// the offset table a consumer's kernel adds on load (null: no constant is carried)
+static const float* dc_table(const Plan& P) { return P.dc_active ? P.d_dc_pref : nullptr; }
+// What a consumer's arguments read (x .. clean_on_load, dcf): `v` and the offset table when its kernel takes the offset on
+// load (FirStage::takes_dc, TimeOscStage::takes_dc), else the copy of dc_windows and no table.
+template <class Args>
+static int dc_bind(Plan& P, Args& A, bool takes_dc, const WinView& v, int nw, be_stream_t s, bool& made) {
+  WinView use = v;
+  A.dcf = dc_table(P);
+  if (A.dcf && !takes_dc) {
+    int rc = dc_windows(P, v, nw, s, made, &use);
+    if (rc) return rc;
+    A.dcf = nullptr;
+  }
+  view_into(A, use);
   return 0;
 }
 

@@ -280,7 +280,7 @@ NmxTimeOscKind timeosc_kind(const Plan& P, const NmxTimeOscArgs& A) {
   if (A.w500_tab && nmx_timeosc_stft500_ok(A)) return NMX_TO_STFT500;
   // 510-sample FFT / STFT segments (17 ms at 30 kHz): one wave per item, in-place prime-factor transforms
   if (A.w510_tab && nmx_timeosc_w510_ok(A, A.w510_tab)) return NMX_TO_W510;
-  if (P.nt_timeosc == 128) return NMX_TO_FIXED128;
+  if (P.timeosc.nt == 128) return NMX_TO_FIXED128;
 #endif
   return NMX_TO_GENERIC;
 }
@@ -289,7 +289,9 @@ int build_timeosc(Plan& P) {
   const nmx_plan_desc& d = P.d;
   const unsigned mask = NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_STFT;
   if (!(d.features & mask)) return 0;
-  NmxTimeOscArgs& A = P.to;
+  TimeOscStage& S = P.timeosc;
+  S.nt = d.window <= 1024 ? 128 : 256;
+  NmxTimeOscArgs& A = S.a;
   A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
   A.n_channels = d.n_channels;
   A.W = d.window;
@@ -328,7 +330,7 @@ int build_timeosc(Plan& P) {
   if (d.features & NMX_F_WELCH) if ((rc = add(d.welch, 1, &A.welch))) return rc;
   if (d.features & NMX_F_STFT) if ((rc = add(d.stft, 2, &A.stft))) return rc;
   // per-wave STFT needs room for (threads / 64) transforms of 250 points in each buffer
-  A.stft_per_wave = (d.features & NMX_F_STFT) && maxc >= 250 * (P.nt_timeosc / 64);
+  A.stft_per_wave = (d.features & NMX_F_STFT) && maxc >= 250 * (S.nt / 64);
   A.long_mode = 0; A.long_nb = 0; A.long_spec_slab = 0; A.slab_floats = 0; A.slab_blocks = 0; A.slab = nullptr;
   if (lng) {
     NMX_REQUIRE(!(d.features & NMX_F_STFT), "internal: STFT in a long-window plan");
@@ -364,9 +366,8 @@ int build_timeosc(Plan& P) {
     A.slab_blocks = (int)std::max<size_t>(1, blocks);
 #endif
     if (A.slab_floats > 0) {
-      A.slab = (float*)be_alloc((size_t)A.slab_blocks * A.slab_floats * sizeof(float));
+      A.slab = (float*)plan_alloc(P, (size_t)A.slab_blocks * A.slab_floats * sizeof(float));
       if (!A.slab) return nmx_fail(NMX_E_NOMEM, "time/oscillatory slab allocation failed");
-      P.tables.push_back(A.slab);   // (freed with the plan's tables: nmx_plan_destroy)
     }
   } else {
     A.off_x = 0;
@@ -438,12 +439,36 @@ int build_timeosc(Plan& P) {
     if (!A.w510_tab) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
   }
 #endif
-  P.to_kind = timeosc_kind(P, A);
-  P.to_takes_dc = P.to_kind != NMX_TO_STFT500 && P.to_kind != NMX_TO_W510;
-  P.have_to = true;
+  S.kind = timeosc_kind(P, A);
+  S.takes_dc = S.kind != NMX_TO_STFT500 && S.kind != NMX_TO_W510;
+  P.have_timeosc = true;
   return 0;
 }
 
+// the time / oscillatory features of one chunk (nw hops) from the windows `v`.  (The matrix-pipe kernel's redo launch --
+// the windows it flagged: NaN / infinity on load -- stays outside the stage's timer and kernel list.)
+static int launch_timeosc_stage(Plan& P, const WinView& v, int nw, float* d_out, be_stream_t s, bool tev, bool& dc_made) {
+  if (!P.have_timeosc) return 0;
+  TimeOscStage& S = P.timeosc;
+  const int C = P.d.n_channels;
+  int rc;
+  NmxTimeOscArgs A = S.a;
+  A.out = d_out;
+  A.starts_mod4 = (!v.starts || P.starts_mod4) ? 1 : 0;
+  if ((rc = dc_bind(P, A, S.takes_dc, v, nw, s, dc_made))) return rc;
+  A.todo = nullptr;
+  const bool smm = S.kind == NMX_TO_SPECMM;
+  if (smm) {   // flags of the matrix-pipe kernel (nmx_k_specmm.h): a 16-bit mask per tile of 16 windows
+    if ((rc = ensure(S.todo, (size_t)((nw + 15) / 16) * C * sizeof(unsigned short)))) return rc;
+    A.todo = (unsigned short*)S.todo.p;
+  }
+  if (tev) be_timer_start(P.timers[2], s);
+  be_stage(2);
+  be_launch_timeosc(A, S.kind, nw * C, S.nt, (size_t)A.lds_floats * 4, P.n_cu, s);
+  if (tev) be_timer_stop(P.timers[2], s);
+  if (smm) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }
+  return 0;
+}
 
 // ---- coherence between channel pairs (nmx_k_coh.h) --------------------------------------------------------------------
 int build_coh(Plan& P) {
@@ -455,7 +480,7 @@ int build_coh(Plan& P) {
               "coherence: nperseg (clamped to the window) must lie in [2, 4096]");
   NMX_REQUIRE(d.coh_methods & 1u, "coherence: method coh must be enabled (the reference fails without it)");
   NMX_REQUIRE(d.coh_n_bands >= 0 && d.coh_n_bands <= NMX_MAX_BANDS_DEV, "coherence: too many bands");
-  NmxCohArgs& A = P.coh;
+  NmxCohArgs& A = P.coherence.a;
   A = NmxCohArgs{};
   A.n = n;
   A.step = n - n / 2;
@@ -504,4 +529,16 @@ int build_coh(Plan& P) {
   A.lds_floats = A.off_red + 64 + 2 * 128 + 16;
   P.have_coh = true;
   return 0;
+}
+
+// coherence of one chunk from the windows `v`: on the main stream, behind the time / oscillatory kernel
+static void launch_coh_stage(Plan& P, const WinView& v, int nw, float* d_out, be_stream_t s, bool tev) {
+  if (!P.have_coh) return;
+  NmxCohArgs A = P.coherence.a;
+  view_into(A, v);
+  A.out = d_out;
+  if (tev) be_timer_start(P.timers[7], s);
+  be_stage(7);
+  be_launch_coh(A, nw * A.n_pairs, s);
+  if (tev) be_timer_stop(P.timers[7], s);
 }

@@ -1,6 +1,7 @@
 // nmx_engine_plan_state.inc -- plan building, part 3: raw normaliser, preprocessing_filter stages, resampler, Kalman,
-// sharp waves, re-reference structure; the state-blob sections of the raw normaliser and the Kalman filters beside their
-// build functions (rawnorm_state_*, kalman_state_*: the table that walks them is in nmx_engine_abi.inc).  Included by nmx_engine.inc.
+// sharp waves, the front end (re-reference or offset shift); the state-blob sections of the raw normaliser and the Kalman
+// filters beside their build functions (rawnorm_state_*, kalman_state_*: the table that walks them is in nmx_engine_abi.inc).
+// Included by nmx_engine.inc.
 // ---- the raw normaliser's section of the state blob: hops seen | ring capacity of the exporting plan | rings | counts | lengths.
 // The capacity depends on the window length; a stream with ragged window lengths hands the blob of one plan to the plan
 // of the other length, which re-lays the histories into its own rings (rawnorm_state_import).
@@ -113,9 +114,9 @@ int build_rawnorm(Plan& P) {
   return 0;
 }
 
-// raw_normalization stage of one chunk / one window: statistics walk, then the elementwise map
-static int run_rawnorm(Plan& P, const float*& src, long long& ch_stride, long long& win_stride,
-                       const long long*& starts, int nw, int clean, be_stream_t s) {
+// raw_normalization stage of one chunk / one window: statistics walk, then the elementwise map; `v`: in, its windows; out, the
+// normalised ones
+static int run_rawnorm(Plan& P, WinView& v, int nw, be_stream_t s) {
   const int C = P.d.n_channels, W = P.d.window;
   RawNormStage& S = P.rawnorm;
   int rc;
@@ -123,9 +124,9 @@ static int run_rawnorm(Plan& P, const float*& src, long long& ch_stride, long lo
   if ((rc = ensure(S.mean, (size_t)nw * C * sizeof(float)))) return rc;
   if ((rc = ensure(S.scale, (size_t)nw * C * sizeof(float)))) return rc;
   NmxRawNormArgs A = S.a;
-  A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
+  view_into(A, v);
   A.y = (float*)S.x_rn.p; A.n_windows = nw; A.hop0 = S.hops;
-  A.mean = (float*)S.mean.p; A.scale = (float*)S.scale.p; A.clean_on_load = clean;
+  A.mean = (float*)S.mean.p; A.scale = (float*)S.scale.p;
   A.sorted_valid = S.sorted_valid ? 1 : 0;
   if (A.method == NMX_RAWNORM_QUANTILE) {
     if ((rc = ensure(S.qt, (size_t)nw * C * NMX_RAWNORM_NQ * sizeof(double)))) return rc;
@@ -138,8 +139,7 @@ static int run_rawnorm(Plan& P, const float*& src, long long& ch_stride, long lo
   be_launch_rawnorm(A, s);
   S.sorted_valid = true;
   S.hops += nw;
-  src = (const float*)S.x_rn.p;
-  ch_stride = W; win_stride = (long long)C * W; starts = nullptr;
+  v = dense_view(S.x_rn.p, C, W);
   return 0;
 }
 
@@ -186,7 +186,7 @@ int build_resample(Plan& P) {
   const int n_new = std::max((int)std::nearbyint(ratio * n_pad), 1);
   const int crop_l = (int)std::nearbyint(ratio * pad_l);
   NMX_REQUIRE(crop_l + final_len <= n_new, "internal: resample crop outside the output");
-  NmxResampleArgs& A = P.rs;
+  NmxResampleArgs& A = P.resample.a;
   A.n_channels = d.n_channels; A.W = W; A.W_new = final_len;
   A.n_pad = n_pad; A.pad_l = pad_l; A.n_new = n_new; A.crop_l = crop_l;
   A.inv_full = n_new & 1;
@@ -227,9 +227,23 @@ int build_resample(Plan& P) {
     if (!A.tab_n) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
   }
   if ((rc = build_fft(P, n_inv, &A.inv))) return rc;
-  P.nt_resample = 256;
   P.w_in = W;
   P.have_resample = true;
+  return 0;
+}
+
+// the resampler of one chunk / one window, behind the notch like the reference's (data_preprocessor.py:9-15,68-71);
+// `v`: in, the incoming windows; out, the resampled ones
+static int launch_resample(Plan& P, WinView& v, int nw, be_stream_t s) {
+  ResampleStage& S = P.resample;
+  const int C = P.d.n_channels, W = P.d.window;
+  int rc;
+  if ((rc = ensure(S.y, (size_t)nw * C * W * sizeof(float)))) return rc;
+  NmxResampleArgs A = S.a;
+  view_into(A, v);
+  A.y = (float*)S.y.p;
+  be_launch_resample(A, nw * C, S.nt, (size_t)A.lds_floats * 4, s);
+  v = dense_view(S.y.p, C, W);
   return 0;
 }
 
@@ -269,6 +283,14 @@ int build_kalman(Plan& P) {
   P.have_kalman = true;
   kalman_state_reset(P);
   return 0;
+}
+
+// behind the bank, on its stream: sequential over the hops of the chunk, and chunks run in order on `s`
+static void launch_kalman(Plan& P, int nw, float* d_out, be_stream_t s) {
+  if (!P.have_kalman) return;
+  NmxKalmanArgs K = P.kalman.a;
+  K.out = d_out; K.n_windows = nw;
+  be_launch_kalman(K, s);
 }
 
 int build_sharp(Plan& P) {
@@ -460,7 +482,7 @@ int find_reref_structure(Plan& P) {
       row_coef[(size_t)r * NMX_RS_TAPS + k] = (float)taps[k].second;
     }
   }
-  NmxRerefStructArgs& A = P.rst;
+  NmxRerefStructArgs& A = P.front.rst;
   A.C = C; A.C_in = Cin;
   A.n_groups = (int)group_list.size();
   A.group_off[0] = 0;
@@ -475,7 +497,29 @@ int find_reref_structure(Plan& P) {
   A.members = (const int*)upload(P, members.data(), members.size() * sizeof(int));
   if (!A.row_idx || !A.row_coef || !A.row_group || !A.row_b || !A.members)
     return nmx_fail(NMX_E_NOMEM, "table allocation failed");
-  P.rs_ok = true;
+  P.front.structured = true;
+  return 0;
+}
+
+// The front end's re-reference, from the plan's copy of the matrix: its fp32 upload, the exact common-average test, the
+// structure search.  (A plan without a matrix keeps d_R = null: its front end is the offset shift, or nothing.)
+int build_front(Plan& P) {
+  if (P.ref_matrix.empty()) return 0;
+  FrontStage& F = P.front;
+  const int C = P.d.n_channels, Cin = P.d.n_channels_in;
+  const std::vector<double>& R = P.ref_matrix;
+  std::vector<float> Rf(R.begin(), R.end());
+  F.d_R = (float*)upload(P, Rf.data(), Rf.size() * sizeof(float));
+  if (!F.d_R) return nmx_fail(NMX_E_NOMEM, "ref matrix");
+  if (Cin == C && C >= 2 && env_int("NMX_CAR_FAST", 1)) {
+    const double dg = R[0], of = R[1];
+    bool ok = true;
+    for (int i = 0; i < C && ok; ++i)
+      for (int j = 0; j < C; ++j)
+        if (std::fabs(R[(size_t)i * C + j] - (i == j ? dg : of)) > 1e-12) { ok = false; break; }
+    if (ok) { F.car = true; F.car_diag = (float)dg; F.car_off = (float)of; }
+  }
+  if (!F.car && env_int("NMX_REREF_STRUCT", 1)) return find_reref_structure(P);
   return 0;
 }
 
@@ -483,23 +527,50 @@ int find_reref_structure(Plan& P) {
 // matrices, taps + group sums when the structure was found, dense product otherwise
 void launch_reref(Plan& P, const float* x, long long ldx, float* y, long long ldy, long long T, be_stream_t s) {
   const int C = P.d.n_channels;
-  if (P.car) {
+  const FrontStage& F = P.front;
+  if (F.car) {
     NmxCarArgs R{};
     R.x = x; R.ldx = ldx; R.y = y; R.ldy = ldy; R.C = C; R.T = T;
-    R.diag = P.car_diag; R.off = P.car_off;
+    R.diag = F.car_diag; R.off = F.car_off;
     R.sub = P.dc_sub_active ? P.d_dc_sub : nullptr; R.nanv = P.dc_active ? P.d_dc_nanv : nullptr;
     be_launch_car(R, s);
-  } else if (P.rs_ok) {
-    NmxRerefStructArgs R = P.rst;
+  } else if (F.structured) {
+    NmxRerefStructArgs R = F.rst;
     R.x = x; R.ldx = ldx; R.y = y; R.ldy = ldy; R.T = T;
     R.sub = P.dc_sub_active ? P.d_dc_sub : nullptr; R.nanv = P.dc_active ? P.d_dc_nanv : nullptr;
     be_launch_reref_struct(R, s);
   } else {
     NmxRerefArgs R{};
-    R.x = x; R.ldx = ldx; R.y = y; R.ldy = ldy; R.R = P.d_R;
+    R.x = x; R.ldx = ldx; R.y = y; R.ldy = ldy; R.R = F.d_R;
     R.C = C; R.C_in = P.d.n_channels_in; R.T = T;
     R.sub = P.dc_sub_active ? P.d_dc_sub : nullptr; R.nanv = P.dc_active ? P.d_dc_nanv : nullptr;
     be_launch_reref(R, s);
   }
 }
 
+// The front end of a chunk, or of one window (lo = 0).  `x` / `ldx` address the recording with absolute sample indices; the
+// samples [lo, lo + n_range) of every row are re-referenced once (windows overlap: per sample, not per window) -- or, in a
+// plan without a matrix that carries constants, split: the learned constants are subtracted and a NaN becomes `nanv` -- into
+// x_ref, and `v` then addresses x_ref with the same absolute indices.  Neither: `v` stays on the caller's rows.
+// shift_if_host_offsets: whether the CALLER's constants alone (nothing learned, sub = 0: it handed over x - d) ask for the
+// shift.  A chunk: yes -- a NaN in the caller's split must still become the recording's value 0, i.e. -d in the split
+// domain (nanv); the consumers' own clean-on-load would make it 0 + d = d, and the burst history of that channel would part
+// from the reference's.  nmx_preprocess_window: no -- it has made a NaN the value 0 on the host before it subtracted d.
+static int launch_front(Plan& P, const float* x, long long ldx, long long lo, long long n_range, bool shift_if_host_offsets,
+                        be_stream_t s, WinView& v) {
+  FrontStage& F = P.front;
+  const int C = P.d.n_channels;
+  if (!F.d_R && !(shift_if_host_offsets ? P.dc_active : P.dc_sub_active)) return 0;
+  int rc = ensure(F.x_ref, (size_t)C * n_range * sizeof(float));
+  if (rc) return rc;
+  if (F.d_R) {
+    launch_reref(P, x + lo, ldx, (float*)F.x_ref.p, n_range, n_range, s);
+  } else {
+    NmxShiftArgs Sh{};
+    Sh.x = x + lo; Sh.ldx = ldx; Sh.y = (float*)F.x_ref.p; Sh.ldy = n_range; Sh.C = C; Sh.T = n_range;
+    Sh.sub = P.d_dc_sub; Sh.nanv = P.d_dc_nanv;
+    be_launch_shift(Sh, s);
+  }
+  v = WinView{(const float*)F.x_ref.p - lo, n_range, v.win_stride, v.starts, 0};
+  return 0;
+}

@@ -1,52 +1,37 @@
 // nmx_engine_run.inc -- C ABI, part 2: the launch sequence of one chunk (run_chunk), nmx_process_batch / _window,
 // nmx_preprocess_window, nmx_filter_window, timers and kernel names.  Included by nmx_engine.inc.
 // -----------------------------------------------------------------------------------------
-// The pre-processing behind a re-reference / offset shift, of a chunk (nw hops) or of one window (nw = 1, win_stride = 0):
+// The pre-processing behind the front end, of a chunk (nw hops) or of one window (nw = 1, win_stride = 0):
 // preprocessing_filter stages -> notch -> resampler (after the notch like the reference, data_preprocessor.py:9-15,68-71)
-// -> raw normaliser (the last pre-processor; its input already nan_to_num'ed).  src / strides / starts / clean follow the
-// output of each stage that runs.  `fuse_bank` (run_chunk, a plan with notch_bank_fuse): the bank's arguments of this chunk --
-// its second launch runs inside the notch kernel (choose_notch_bank_fuse).
-static int run_prep_stages(Plan& P, const float*& src, long long& ch_stride, long long& win_stride,
-                           const long long*& starts, int nw, int& clean, be_stream_t s, const NmxBankArgs* fuse_bank = nullptr) {
-  const int C = P.d.n_channels, W = P.d.window, Wi = P.w_in;
+// -> raw normaliser (the last pre-processor; its input already nan_to_num'ed).  `v` follows the output of each stage that
+// runs.  `fuse_bank` (run_chunk, a plan with notch_bank_fuse): the bank's arguments of this chunk -- its second launch runs
+// inside the notch kernel (choose_notch_bank_fuse).
+static int run_prep_stages(Plan& P, WinView& v, int nw, be_stream_t s, const NmxBankArgs* fuse_bank = nullptr) {
+  const int C = P.d.n_channels, Wi = P.w_in;
   int rc;
-  auto take = [&](const void* y, int w) {   // the next stage reads y, [nw][C][w]
-    src = (const float*)y;
-    ch_stride = w; win_stride = (long long)C * w; starts = nullptr; clean = 0;
-  };
   for (size_t i = 0; i < P.pre.size(); ++i) {   // preprocessing_filter: FIR stages one after the other
     Buf& dst = P.x_pf[i & 1];
     if ((rc = ensure(dst, (size_t)nw * C * Wi * sizeof(float)))) return rc;
     NmxBankArgs A = P.pre[i].a;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
+    view_into(A, v);
     A.out = nullptr; A.sw_out = (float*)dst.p;
     launch_fir_stage(P, P.pre[i], A, nw * C, s);
-    take(dst.p, Wi);
+    v = dense_view(dst.p, C, Wi);
   }
   if (P.have_notch) {
     if ((rc = ensure(P.y_notch, (size_t)nw * C * Wi * sizeof(float)))) return rc;
     NmxBankArgs A = P.notch.a;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
+    view_into(A, v);
     A.out = nullptr; A.y_out = (float*)P.y_notch.p;
 #ifndef NMX_HOST_EMU
     if (fuse_bank) launch_notch_bank_fused(P, A, *fuse_bank, nw * C, s);
     else
 #endif
     launch_fir_stage(P, P.notch, A, nw * C, s);
-    take(P.y_notch.p, Wi);
+    v = dense_view(P.y_notch.p, C, Wi);
   }
-  if (P.have_resample) {
-    if ((rc = ensure(P.x_rs, (size_t)nw * C * W * sizeof(float)))) return rc;
-    NmxResampleArgs A = P.rs;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts; A.clean_on_load = clean;
-    A.y = (float*)P.x_rs.p;
-    be_launch_resample(A, nw * C, P.nt_resample, (size_t)A.lds_floats * 4, s);
-    take(P.x_rs.p, W);
-  }
-  if (P.have_rawnorm) {
-    if ((rc = run_rawnorm(P, src, ch_stride, win_stride, starts, nw, clean, s))) return rc;
-    clean = 0;
-  }
+  if (P.have_resample && (rc = launch_resample(P, v, nw, s))) return rc;
+  if (P.have_rawnorm && (rc = run_rawnorm(P, v, nw, s))) return rc;
   return 0;
 }
 
@@ -57,7 +42,6 @@ static int run_prep_stages(Plan& P, const float*& src, long long& ch_stride, lon
 static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, long long hi,
                      const long long* d_starts, int nw, float* d_out, be_stream_t s, bool timed,
                      float* d_pre = nullptr, const int64_t* h_starts = nullptr) {
-  const long long n_range = hi - lo;
   const nmx_plan_desc& d = P.d;
   const int C = d.n_channels, W = d.window;
   int rc;
@@ -74,69 +58,42 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   Buf& B_env = P.bursts.env[par];
   Buf& B_swy = P.sharp.swy[par];
   // ---- pre-processing -------------------------------------------------------------------
-  const float* src = d_x;
-  long long ch_stride = ldx, win_stride = 0;
-  const long long* starts = d_starts;
-  int clean = 1;
-  bool raw_live = true;   // `src` still addresses the caller's samples
+  WinView v{d_x, ldx, 0, d_starts, 1};   // what the next stage reads: the caller's samples, until a stage has written its own
   // stage timers: two event records per stage -- 14 per call, ~5 us of host time each -- are what the one-window call of a
   // real-time loop would spend a fifth of its 0.45 ms on: batches of fewer than 8 hops keep the whole-call timer only
   const bool tev = timed && nw >= 8;
   if (timed) be_stage_reset();
   if (tev) be_timer_start(P.timers[1], s);
   be_stage(1);
-  if (P.d_R) {
-    // re-reference the sample range of this chunk once (windows overlap: per sample, not per window)
-    if ((rc = ensure(P.x_ref, (size_t)C * n_range * sizeof(float)))) return rc;
-    launch_reref(P, d_x + lo, ldx, (float*)P.x_ref.p, n_range, n_range, s);
-    src = (const float*)P.x_ref.p - lo;   // absolute starts index into the range buffer
-    ch_stride = n_range;
-    clean = 0;
-    raw_live = false;
-  } else if (P.dc_active) {
-    // constants without a re-reference in front (a notch / the features read the rows directly): split the chunk's sample
-    // range here -- learned constants are subtracted, and with the CALLER's constants (sub = 0: it handed over x - d) a NaN
-    // sample still has to become the recording's value 0, i.e. -d in the split domain (nanv): the consumers' own
-    // clean-on-load would make it 0 + d = d, and the burst history of that channel would part from the reference's
-    if ((rc = ensure(P.x_ref, (size_t)C * n_range * sizeof(float)))) return rc;
-    NmxShiftArgs Sh{};
-    Sh.x = d_x + lo; Sh.ldx = ldx; Sh.y = (float*)P.x_ref.p; Sh.ldy = n_range; Sh.C = C; Sh.T = n_range;
-    Sh.sub = P.d_dc_sub; Sh.nanv = P.d_dc_nanv;
-    be_launch_shift(Sh, s);
-    src = (const float*)P.x_ref.p - lo;
-    ch_stride = n_range;
-    clean = 0;
-    raw_live = false;
-  }
+  if ((rc = launch_front(P, d_x, ldx, lo, hi - lo, true, s, v))) return rc;
+  bool raw_live = v.x == d_x;   // `v` still addresses the caller's samples
   // Window starts in arithmetic progression (every stream with an integer hop; h_starts = the host's copy): the kernels
-  // address window w as src + w * hop -- no per-item load of starts[w] (in the DMA-fed kernel of nmx_k_specmm.h the wait
+  // address window w as x + w * hop -- no per-item load of starts[w] (in the DMA-fed kernel of nmx_k_specmm.h the wait
   // for that vector load drained the copies in flight once per tile)
   if (h_starts) {
     long long hop = nw > 1 ? (long long)(h_starts[1] - h_starts[0]) : 0;
     for (int i = 2; i < nw && hop >= 0; ++i)
       if ((long long)(h_starts[i] - h_starts[i - 1]) != hop) hop = -1;
-    if (hop >= 0) { src += h_starts[0]; win_stride = hop; starts = nullptr; }
+    if (hop >= 0) { v.x += h_starts[0]; v.win_stride = hop; v.starts = nullptr; }
   }
-  // ---- the carried offset (nmx_engine_dc.inc): consumers take it on load; one that cannot reads a copy with it added back
-  const float* dcf = P.dc_active ? P.d_dc_pref : nullptr;
   // the bank's second launch inside the notch kernel (choose_notch_bank_fuse): its outputs exist before the notch runs
   // (the wait on ev_join_d[par] above has freed this parity's sharp-wave series)
   NmxBankArgs fuse_a{};
   if (P.notch_bank_fuse) {
     fuse_a = P.bank.a;
     fuse_a.out = d_out;
-    fuse_a.dcf = dcf;
+    fuse_a.dcf = dc_table(P);
     if (P.have_sharp) {
       if ((rc = ensure(B_swy, (size_t)nw * C * d.n_sw_filters * W * sizeof(float)))) return rc;
       fuse_a.sw_out = (float*)B_swy.p;
     }
   }
-  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, nw, clean, s, P.notch_bank_fuse ? &fuse_a : nullptr))) return rc;
+  if ((rc = run_prep_stages(P, v, nw, s, P.notch_bank_fuse ? &fuse_a : nullptr))) return rc;
   if (!P.pre.empty() || P.have_notch || P.have_resample || P.have_rawnorm) raw_live = false;
   if (d_pre) {   // user-registered host features read what the device features read
     NmxTapArgs T{};
-    T.x = src; T.ch_stride = ch_stride; T.win_stride = win_stride; T.starts = starts;
-    T.y = d_pre; T.C = C; T.W = W; T.clean = clean;
+    view_into(T, v);
+    T.y = d_pre; T.C = C; T.W = W;
     be_launch_tap(T, nw * C, s);
   }
   if (tev) be_timer_stop(P.timers[1], s);
@@ -144,18 +101,9 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   // for the chunk's threshold walk and normaliser -- process_batch_impl)
   P.raw_consumed = !raw_live;
   if (P.raw_consumed && P.in_free_slot >= 0) be_event_record(P.ev_in_free[P.in_free_slot], s);
-  const float* src_dc = nullptr;
-  auto with_dc = [&]() -> int {   // [nw][C][W], the true windows
-    if (src_dc) return 0;
-    int rc2 = ensure(P.x_dc, (size_t)nw * C * W * sizeof(float));
-    if (rc2) return rc2;
-    NmxTapArgs T{};
-    T.x = src; T.ch_stride = ch_stride; T.win_stride = win_stride; T.starts = starts;
-    T.y = (float*)P.x_dc.p; T.C = C; T.W = W; T.clean = clean; T.add = dcf;
-    be_launch_tap(T, nw * C, s);
-    src_dc = (const float*)P.x_dc.p;
-    return 0;
-  };
+  // ---- the carried offset (nmx_engine_dc.inc): consumers take it on load; one that cannot reads a copy with it added back,
+  // made at most once per chunk (dc_bind)
+  bool dc_made = false;
   // ---- features --------------------------------------------------------------------------
   // Launch order on the main stream `s`: FIR bank (it feeds bursts and sharp waves) -> Hilbert -> time / oscillatory
   // -> sharp waves.  The sequential, latency-bound part of the bursts chain (threshold walk -> run statistics: a few
@@ -165,13 +113,8 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   be_stage(3);
   if (P.have_bank) {
     NmxBankArgs A = P.bank.a;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
-    A.out = d_out; A.clean_on_load = clean;
-    A.dcf = dcf;
-    if (dcf && !P.bank.takes_dc) {
-      if ((rc = with_dc())) return rc;
-      A.x = src_dc; A.ch_stride = W; A.win_stride = (long long)C * W; A.starts = nullptr; A.clean_on_load = 0; A.dcf = nullptr;
-    }
+    A.out = d_out;
+    if ((rc = dc_bind(P, A, P.bank.takes_dc, v, nw, s, dc_made))) return rc;
     if (P.have_bursts) {
       if ((rc = ensure(B_env, (size_t)nw * C * d.n_burst_bands * W * sizeof(float)))) return rc;
       A.env_out = (float*)B_env.p;
@@ -185,11 +128,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
       A.yb_out = (float*)P.bursts.yb.p;
     }
     launch_fir_stage(P, P.bank, A, nw * C, s, tev);
-    if (P.have_kalman) {   // sequential over the hops of the chunk; chunks run in order on `s`
-      NmxKalmanArgs K = P.kalman.a;
-      K.out = d_out; K.n_windows = nw;
-      be_launch_kalman(K, s);
-    }
+    launch_kalman(P, nw, d_out, s);
   }
   const bool sharp_side = P.overlap == 4 && P.have_sharp;
   if (sharp_side) {
@@ -200,37 +139,8 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   }
   be_stage(4);
   if (P.have_bursts && (rc = launch_burst_stage(P, par, nw, d_out, s, tev))) return rc;
-  if (P.have_to) {
-    NmxTimeOscArgs A = P.to;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
-    A.out = d_out; A.clean_on_load = clean;
-    A.starts_mod4 = (!starts || P.starts_mod4) ? 1 : 0;
-    A.dcf = dcf;
-    if (dcf && !P.to_takes_dc) {
-      if ((rc = with_dc())) return rc;
-      A.x = src_dc; A.ch_stride = W; A.win_stride = (long long)C * W; A.starts = nullptr; A.clean_on_load = 0; A.dcf = nullptr;
-    }
-    A.todo = nullptr;
-    const bool smm = P.to_kind == NMX_TO_SPECMM;
-    if (smm) {   // flags of the matrix-pipe kernel (nmx_k_specmm.h): a 16-bit mask per tile of 16 windows
-      if ((rc = ensure(P.to_todo, (size_t)((nw + 15) / 16) * C * sizeof(unsigned short)))) return rc;
-      A.todo = (unsigned short*)P.to_todo.p;
-    }
-    if (tev) be_timer_start(P.timers[2], s);
-    be_stage(2);
-    be_launch_timeosc(A, P.to_kind, nw * C, P.nt_timeosc, (size_t)A.lds_floats * 4, P.n_cu, s);
-    if (tev) be_timer_stop(P.timers[2], s);
-    if (smm) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }   // (windows the kernel flagged: NaN / infinity on load; outside the stage's timer and kernel list)
-  }
-  if (P.have_coh) {   // coherence between channel pairs: stateless, on the main stream behind the time / oscillatory kernel
-    NmxCohArgs A = P.coh;
-    A.x = src; A.ch_stride = ch_stride; A.win_stride = win_stride; A.starts = starts;
-    A.out = d_out; A.clean_on_load = clean;
-    if (tev) be_timer_start(P.timers[7], s);
-    be_stage(7);
-    be_launch_coh(A, nw * A.n_pairs, s);
-    if (tev) be_timer_stop(P.timers[7], s);
-  }
+  if ((rc = launch_timeosc_stage(P, v, nw, d_out, s, tev, dc_made))) return rc;
+  launch_coh_stage(P, v, nw, d_out, s, tev);
   if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
   // (no join on the main stream: the chunk is finished by chunk_finalize below, on its own stream)
   be_event_record(P.ev_main[par], s);
@@ -332,7 +242,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   // features of chunk k - 1 travel back.  Device buffers: one chunk = NMX_CHUNK_WINDOWS hops.
   // (a plan without a hand-off tensor -- time / oscillatory features straight from the recording -- has nothing a chunk
   // would bound: device-resident batches go out as ONE launch of up to 16 chunks' worth of hops)
-  const bool no_handoff = !P.have_bank && !P.have_notch && !P.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
+  const bool no_handoff = !P.have_bank && !P.have_notch && !P.front.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
   // (an attached normaliser needs a chunk's rows complete, and hop order: it runs on the finalize stream under the NEXT
   // chunk's kernels, so only the last chunk's pass is exposed -- against that, shorter chunks cost the main kernels 0.16 ms
   // per 1024 hops at 256.  Round 6, scans + cells at ~75 us per pass, headline step with / without the z-score:
@@ -537,34 +447,17 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   if ((rc = dc_prepare(P, xf.data(), W, 0, true, s))) return rc;
   if ((rc = ensure(P.x_in, xf.size() * sizeof(float)))) return rc;
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
-  const float* src = (const float*)P.x_in.p;
-  long long ch_stride = W, win_stride = 0;
-  const long long* starts = nullptr;
-  int clean = 1;
-  if (P.d_R) {
-    if ((rc = ensure(P.x_ref, (size_t)C * W * sizeof(float)))) return rc;
-    launch_reref(P, src, W, (float*)P.x_ref.p, W, W, s);
-    src = (const float*)P.x_ref.p;
-    clean = 0;
-  } else {
-    NMX_REQUIRE(Cin == C, "n_channels_in != n_channels without ref_matrix");
-    if (P.dc_sub_active) {
-      if ((rc = ensure(P.x_ref, (size_t)C * W * sizeof(float)))) return rc;
-      NmxShiftArgs Sh{};
-      Sh.x = src; Sh.ldx = W; Sh.y = (float*)P.x_ref.p; Sh.ldy = W; Sh.C = C; Sh.T = W; Sh.sub = P.d_dc_sub; Sh.nanv = P.d_dc_nanv;
-      be_launch_shift(Sh, s);
-      src = (const float*)P.x_ref.p;
-      clean = 0;
-    }
-  }
-  if ((rc = run_prep_stages(P, src, ch_stride, win_stride, starts, 1, clean, s))) return rc;
-  be_d2h_async(yf.data(), src, yf.size() * sizeof(float), s);
+  NMX_REQUIRE(P.front.d_R || Cin == C, "n_channels_in != n_channels without ref_matrix");
+  WinView v{(const float*)P.x_in.p, W, 0, nullptr, 1};
+  if ((rc = launch_front(P, v.x, W, 0, W, false, s, v))) return rc;
+  if ((rc = run_prep_stages(P, v, 1, s))) return rc;
+  be_d2h_async(yf.data(), v.x, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
     for (int i = 0; i < Wo; ++i) {
-      float v = yf[(size_t)c * Wo + i];
-      if (clean) v = (v != v) ? 0.f : v;
-      y[(size_t)c * ldy + i] = (double)v + (P.dc_active ? P.dc_pre_h[c] : 0.0);
+      float f = yf[(size_t)c * Wo + i];
+      if (v.clean) f = (f != f) ? 0.f : f;
+      y[(size_t)c * ldy + i] = (double)f + (P.dc_active ? P.dc_pre_h[c] : 0.0);
     }
   return be_check_launch();
 }
@@ -586,8 +479,8 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   if ((rc = ensure(P.sharp.swy[0], yf.size() * sizeof(float)))) return rc;
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
   NmxBankArgs A = P.bank.a;
-  A.x = (const float*)P.x_in.p; A.ch_stride = W; A.win_stride = 0; A.starts = nullptr;
-  A.clean_on_load = 0; A.out = nullptr;
+  view_into(A, WinView{(const float*)P.x_in.p, W, 0, nullptr, 0});
+  A.out = nullptr;
   A.n_sw_filters = NF; A.sw_out = (float*)P.sharp.swy[0].p;
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
