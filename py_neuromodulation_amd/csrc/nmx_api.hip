@@ -68,6 +68,12 @@ __global__ void __launch_bounds__(1024) nmx_kern_burst_thr_wide(const NmxBurstTh
   const int item = blockIdx.x;
   nmx_burst_thr_item<64>(A, item / A.n_bands, item % A.n_bands, nmx_smem);
 }
+// histories beyond 65 536 list entries (16 kHz x 30 s at the default 75th percentile: 120 001): the list stays in global
+// memory and every merge sweeps it in tiles of 1024 threads x 8 entries (nmx_merge_into_tiled)
+__global__ void __launch_bounds__(NMX_THR_TILE_NT) nmx_kern_burst_thr_tiled(const NmxBurstThrArgs A) {
+  const int item = blockIdx.x;
+  nmx_burst_thr_walk<1, true>(A, item / A.n_bands, item % A.n_bands, nmx_smem);
+}
 // kernels compiled with a compile-time workgroup size live in nmx_timeosc.hip / nmx_wave.hip
 extern "C" void nmx_timeosc_fixed_launch128(const NmxTimeOscArgs* A, int n_items, size_t lds, hipStream_t s);
 extern "C" void nmx_hilbert_fixed_launch128(const NmxHilbertArgs* A, long long n_items, size_t lds, hipStream_t s);
@@ -450,6 +456,7 @@ static void be_init_once() {
   be_allow_lds(nmx_kern_burst_thr<64>);
   be_allow_lds(nmx_kern_burst_thr<128>);
   be_allow_lds(nmx_kern_burst_thr_wide);
+  be_allow_lds(nmx_kern_burst_thr_tiled);
   be_allow_lds(nmx_kern_burst_fill);
   be_allow_lds(nmx_kern_burst_fill_sort);
   be_allow_lds(nmx_kern_rawnorm_order);   // 24 * (window + hop) + 8 KiB: above 64 KiB from ~2390 samples
@@ -551,7 +558,8 @@ static void be_launch_burst_thr(const NmxBurstThrArgs& A, const NmxBurstWalk& K,
   be_init_once();
   if (g.kind == NMX_WALK_WAVE) { nmx_wave_launch_burst_thr(&A, n_items, K.nr, g.list_lds, g.list_lds ? K.lds_list : K.lds, s); return; }
   const int chunk = (A.K + nt - 1) / nt;
-  if (nt > 256) { hipLaunchKernelGGL(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_wide"); }
+  if (nmx_burst_thr_tiled(A.K)) { hipLaunchKernelGGL(nmx_kern_burst_thr_tiled, dim3(n_items), dim3(NMX_THR_TILE_NT), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_tiled"); }
+  else if (nt > 256) { hipLaunchKernelGGL(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_wide"); }
   else if (chunk <= 32) { hipLaunchKernelGGL(nmx_kern_burst_thr<32>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<32>"); }
   else if (chunk <= 64) { hipLaunchKernelGGL(nmx_kern_burst_thr<64>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<64>"); }
   else { hipLaunchKernelGGL(nmx_kern_burst_thr<128>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<128>"); }

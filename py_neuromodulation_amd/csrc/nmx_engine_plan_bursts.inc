@@ -98,6 +98,7 @@ int build_bursts(Plan& P) {
   T.W = d.window;
   T.q = d.burst_threshold / 100.0;
   NMX_REQUIRE(T.q >= 0.0 && T.q <= 1.0, "burst threshold must be a percentile in [0, 100]");
+  NMX_REQUIRE(d.sfreq * d.burst_time_duration_s < 2147483647.0, "burst ring buffer (sfreq x time_duration_s) too long");
   T.n_ring = (int)(d.sfreq * d.burst_time_duration_s);
   NMX_REQUIRE(T.n_ring >= 2, "burst ring buffer too short");
   const double seg_s = d.segment_length_s > 0 ? d.segment_length_s : (double)d.window / d.sfreq;  // segment_length_features_ms / 1000
@@ -110,8 +111,16 @@ int build_bursts(Plan& P) {
   NMX_REQUIRE(T.overlap >= 1 && T.overlap <= d.window, "burst overlap (sfreq * seg_s / feat_hz) out of range");
   T.K = (int)std::floor((1.0 - T.q) * (double)(T.n_ring - 1)) + 2;
   T.K = std::min(T.K, T.n_ring);
+  // (before anything of the chain is allocated: the state alone is n_channels x n_burst_bands x K floats)
+  if (T.K > NMX_THR_K_MAX)
+    return nmx_fail(NMX_E_INVALID, "burst threshold history too long: floor((1 - threshold / 100) x (int(sfreq x time_duration_s) - 1)) + 2 = " +
+                    std::to_string(T.K) + " top-K list entries, the limit is 1 048 576 (bursts_settings.threshold, "
+                    "bursts_settings.time_duration_s and the sampling rate the bursts see)");
   int p2 = 1;
   while (p2 < std::max(std::max(d.window, T.overlap) + 4, 1024)) p2 <<= 1;   // >= NMX_THR_P (flush staging)
+  // (the three arrays are only indexed, never sorted as a network: a plan of the tiled kernel takes them as long as they have to be --
+  // 1 s windows up to 12.9 kHz instead of 8.1 kHz, where the default 30 s history at the 75th percentile keeps 90 001 entries)
+  if (nmx_burst_thr_tiled(T.K)) p2 = std::max(al4(std::max(d.window, T.overlap) + 4), 1024);
   T.P2 = p2;
   // NMX_THR_LIST_GLOBAL=1: the sorted top-K list is not copied to LDS (workgroups of ~20 KB instead of
   // ~50 KB leave room for the kernels that run next to the walk); every list access then goes to L2
@@ -126,9 +135,10 @@ int build_bursts(Plan& P) {
     if (T.lds_floats * 4 <= 160 * 1024 || T.list_in_global) break;
     T.list_in_global = 1;
   }
-  if ((T.K + B.nt_thr - 1) / B.nt_thr > 128) B.nt_thr = 1024;   // nmx_kern_burst_thr_wide: 64 entries per thread
-  NMX_REQUIRE((T.K + B.nt_thr - 1) / B.nt_thr <= (B.nt_thr > 256 ? 64 : 128), "burst top-K list too long for the merge kernel "
-              "(sfreq x time_duration_s x (1 - threshold / 100) > 65 536 samples)");
+  // the workgroup walk's kernel (be_launch_burst_thr): a thread's share of the list in registers -- 128 entries x 256 threads, 64 x
+  // 1024 in nmx_kern_burst_thr_wide --, beyond 65 536 entries the tiled merge of nmx_kern_burst_thr_tiled
+  if (nmx_burst_thr_tiled(T.K)) B.nt_thr = NMX_THR_TILE_NT;
+  else if ((T.K + B.nt_thr - 1) / B.nt_thr > 128) B.nt_thr = 1024;
   NMX_REQUIRE(T.lds_floats * 4 <= 160 * 1024,
               "burst threshold state does not fit in 160 KiB LDS (ring x (1 - q) too large)");
   NmxBurstStatArgs& S = B.bstat;

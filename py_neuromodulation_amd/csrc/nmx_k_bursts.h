@@ -36,7 +36,7 @@ struct NmxBurstThrArgs {
   int n_ring;           // int(sfreq * time_duration_s)
   int overlap;          // samples appended per window after the first (bursts.py:81-85)
   double q;             // threshold / 100
-  int P2;               // power of two >= max(W, overlap): bitonic sort size of the new piece
+  int P2;               // length of pc / ps / ins: >= max(W, overlap) + 4 and >= NMX_THR_P (a power of two where K <= NMX_THR_REG_MAX)
   int off_l0, off_l1, off_p, off_red, lds_floats;
   int list_in_global;   // the top-K list stays in its global (L2-resident) state array, LDS holds only the working sets
   // [C][Bb] or nullptr.  A walk that ends with the ring full leaves here the lower of the two order statistics its threshold
@@ -178,6 +178,71 @@ NMX_DEV int nmx_merge_into(float* L, int len, int K, const float* ps, int* ins, 
   return (len + n_new) < K ? (len + n_new) : K;
 }
 
+// ---- lists beyond the register merge: K > NMX_THR_REG_MAX ---------------------------------------------------------------
+// nmx_merge_into stages a thread's whole share of the list in registers: 128 entries x 256 threads, or 64 x 1024 in the
+// wide kernel.  A longer list (a 16 kHz recording's default history keeps 120 001 entries) is merged in TILES instead.
+#define NMX_THR_REG_MAX 65536    // longest list of nmx_merge_into
+#define NMX_THR_K_MAX 1048576    // longest list of a plan (build_bursts): 16 384 Hz x 60 s at any percentile
+#define NMX_THR_TILE_NT 1024     // threads of nmx_kern_burst_thr_tiled
+#define NMX_THR_TILE_E 8         // entries a thread holds: a tile is NMX_NT x 8 entries (8192 on the device, 8 in the emulator)
+static inline bool nmx_burst_thr_tiled(int K) { return K > NMX_THR_REG_MAX; }
+
+// nmx_merge_into without a per-thread capacity, for a list that stays in its global state array (L2): same arguments, same
+// result -- descending order, equal values: list entries first, truncated to K entries.
+//
+// Entry i of the list moves to i + cnt(i), cnt(i) = new samples with ins[j] <= i: a shift towards HIGHER indices that grows
+// with i.  So the list is swept in tiles of NMX_NT x NMX_THR_TILE_E entries from its last tile to its first.  A tile is
+// loaded to registers (entry base + k NMX_NT + tid: a wave's loads are consecutive), a barrier, and it is stored shifted:
+//   * the stores of a tile go to addresses at or above its own first entry, the tiles loaded after it lie below: nothing
+//     that is still to be loaded is overwritten, and no second copy of the list is needed;
+//   * ONE barrier per tile is enough: it separates a tile's loads from its own stores, and every store of a later (lower)
+//     tile comes behind that tile's own barrier, hence behind every load of the tiles above it;
+//   * the merge is a bijection onto [0, len + n_new): no two stores meet, whichever tiles they come from.
+// Only the tiles that move are touched.  cnt() grows with i, so the sweep ends at the first tile whose LAST entry has no new
+// sample in front of it (the entries below stay where they are): a hop whose samples all land near the tail reads a few
+// tiles, not the list.  A tile whose FIRST entry already lands at or beyond K is dropped without being read.  With the list
+// full, a hop none of whose samples exceeds L[K - 1] changes nothing and returns before its binary searches.
+// Every decision about a tile is taken from `ins` (LDS) and plan constants: uniform over the workgroup, as the barriers need.
+NMX_DEV int nmx_merge_into_tiled(float* L, int len, int K, const float* ps, int* ins, int n_new) {
+  if (n_new <= 0) return len;
+  if (len == K && ps[0] <= L[K - 1]) return len;   // (an equal sample sorts behind the list's entries: beyond K)
+  for (int j = NMX_TID; j < n_new; j += NMX_NT) ins[j] = nmx_count_ge(L, len, ps[j]);
+  NMX_SYNC();
+  const int tile = NMX_NT * NMX_THR_TILE_E;
+  for (int base = len > 0 ? ((len - 1) / tile) * tile : -1; base >= 0; base -= tile) {
+    const int end = (base + tile) < len ? (base + tile) : len;
+    const int c_hi = nmx_upper_bound_i(ins, n_new, end - 1);   // new samples in front of the tile's last entry
+    if (c_hi == 0) break;
+    const int c_lo = nmx_upper_bound_i(ins, n_new, base);      // ... of its first
+    if (base + c_lo >= K) continue;
+    float v[NMX_THR_TILE_E];
+#ifndef NMX_HOST_EMU
+#pragma unroll
+#endif
+    for (int k = 0; k < NMX_THR_TILE_E; ++k) {
+      const int i = base + k * NMX_NT + NMX_TID;
+      v[k] = i < end ? L[i] : 0.f;
+    }
+    NMX_SYNC();
+#ifndef NMX_HOST_EMU
+#pragma unroll
+#endif
+    for (int k = 0; k < NMX_THR_TILE_E; ++k) {
+      const int i = base + k * NMX_NT + NMX_TID;
+      if (i < end) {
+        const int cnt = c_lo + nmx_upper_bound_i(ins + c_lo, c_hi - c_lo, i);
+        if (cnt && i + cnt < K) L[i + cnt] = v[k];
+      }
+    }
+  }
+  for (int j = NMX_TID; j < n_new; j += NMX_NT) {
+    const int pos = ins[j] + j;
+    if (pos < K) L[pos] = ps[j];
+  }
+  NMX_SYNC();
+  return (len + n_new) < K ? (len + n_new) : K;
+}
+
 NMX_DEV float nmx_lerp_thr(double a, double b, double frac, bool have_b) {
   if (!have_b) return (float)a;
   const double d = b - a;
@@ -202,8 +267,12 @@ NMX_DEV float nmx_lerp_thr(double a, double b, double frac, bool have_b) {
 // F, drops the a smallest of F and reads the threshold from F -- a handful of tiny steps; only
 // when F runs low or P fills up (every ~10 hops) P is sorted and merged into L_main and F is
 // re-cut from the list's tail.  Bit-identical to the per-hop full merge.
-template <int CH>
-NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* smem) {
+//
+// TILED (K > NMX_THR_REG_MAX; nmx_kern_burst_thr_tiled, 1024 threads; nmx_burst_thr_item below is TILED = false): the same walk with every merge -- the fill regime's, the
+// steady regime's flush, and the per-hop merge of a full ring whose hops bring more than 256 samples -- done by
+// nmx_merge_into_tiled on the list in global memory; no thread holds a share of the list (CH is not used).
+template <int CH, bool TILED>
+NMX_DEV void nmx_burst_thr_walk(const NmxBurstThrArgs& A, int c, int bi, float* smem) {
   float* L = A.list_in_global ? A.top + ((long long)c * A.n_bands + bi) * A.K : smem + A.off_l0;
   float* pc = smem + A.off_p;            // [P2] raw new samples / flush staging
   float* ps = pc + A.P2;                 // [P2] sorted new samples
@@ -220,10 +289,10 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
   float* gtop = A.top + sidx * K;
   if (!A.list_in_global) for (int i = NMX_TID; i < len; i += NMX_NT) L[i] = gtop[i];
 #ifdef NMX_HOST_EMU
-  std::vector<float> vals_store(K > 0 ? K : 1);
+  std::vector<float> vals_store(TILED ? 1 : K > 0 ? K : 1);
   float* vals = vals_store.data();
 #else
-  float vals[CH];
+  float vals[TILED ? 1 : CH];
 #endif
   // steady-state bookkeeping
   const bool steady_ok = A.P2 >= NMX_THR_P && K > 2 * NMX_THR_F && A.overlap <= 256;
@@ -272,7 +341,7 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
     if (!steady) {
       nmx_rank_sort_desc(pc, n_new, ps);
       NMX_SYNC();
-      len = nmx_merge_into<CH>(L, len, K, ps, ins, n_new, vals);
+      len = TILED ? nmx_merge_into_tiled(L, len, K, ps, ins, n_new) : nmx_merge_into<CH>(L, len, K, ps, ins, n_new, vals);
       total += n_new;
       nwin += 1;
       if (NMX_TID == 0) {
@@ -339,7 +408,7 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
       NMX_SYNC();
       nmx_rank_sort_desc(pc, nP, ps);
       NMX_SYNC();
-      Lm = nmx_merge_into<CH>(L, Lm, K, ps, ins, nP, vals);
+      Lm = TILED ? nmx_merge_into_tiled(L, Lm, K, ps, ins, nP) : nmx_merge_into<CH>(L, Lm, K, ps, ins, nP, vals);
       for (int j = NMX_TID; j < nF; j += NMX_NT) L[Lm + j] = F[nF - 1 - j];
       NMX_SYNC();
       // (Lm + nF == K by construction)
@@ -359,6 +428,17 @@ NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* 
     if (A.floor && A.n_windows > 0)
       A.floor[sidx] = (total >= m_ring && ia_ring >= 0 && ia_ring < len) ? nmx_burst_floor_of(L[ia_ring]) : -INFINITY;
   }
+}
+
+// The workgroup walk with the register merge, as the kernels of lists up to NMX_THR_REG_MAX entries launch it.  The single-thread
+// emulator launches every plan's walk through this name: there a longer list takes the tiled walk, as the plan chose
+// (nmx_burst_thr_tiled) -- the same tile loop, tiles of NMX_THR_TILE_E entries, and no K-sized `vals`.
+template <int CH>
+NMX_DEV void nmx_burst_thr_item(const NmxBurstThrArgs& A, int c, int bi, float* smem) {
+#ifdef NMX_HOST_EMU
+  if (nmx_burst_thr_tiled(A.K)) { nmx_burst_thr_walk<CH, true>(A, c, bi, smem); return; }
+#endif
+  nmx_burst_thr_walk<CH, false>(A, c, bi, smem);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -85,6 +85,8 @@ extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items,
   if (nmx_first_on_device(seen)) {
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // (K / 64 block counters of the flush: beyond ~639 000 list entries the working set passes 64 KiB)
+    (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   if (nr == 2) {
     if (list_lds) hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, true>), dim3(n_items), dim3(64), lds, s, *A);
