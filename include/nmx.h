@@ -321,7 +321,8 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
  * Stages 1..8 are those of the first chunk of the batch.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
-/* Names of the kernels the first launch sequence of the last nmx_process_batch ran in stage `which`
+/* Names of the kernels the first launch sequence of the last nmx_process_batch -- or the last
+ * nmx_preprocess_window / nmx_filter_window, whichever came last -- ran in stage `which`
  * (1..8 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
  * (template arguments included).  Which variant runs depends on the shape, the batch size and the tuning
  * knobs, so measurement code names the kernel from here instead of hard-coding it.  NUL-terminated,

@@ -449,8 +449,12 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   be_h2d_async(P.x_in.p, xf.data(), xf.size() * sizeof(float), s);
   NMX_REQUIRE(P.front.d_R || Cin == C, "n_channels_in != n_channels without ref_matrix");
   WinView v{(const float*)P.x_in.p, W, 0, nullptr, 1};
+  be_stage_reset();
+  be_stage(1);
   if ((rc = launch_front(P, v.x, W, 0, W, false, s, v))) return rc;
   if ((rc = run_prep_stages(P, v, 1, s))) return rc;
+  be_stage(0);
+  for (int i = 0; i < 8; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), v.x, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
@@ -485,7 +489,11 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
   }
+  be_stage_reset();
+  be_stage(P.bank.launches[0].stage);
   launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
+  be_stage(0);
+  for (int i = 0; i < 8; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), P.sharp.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];

@@ -1132,7 +1132,7 @@ class HotPathEngine:
         return float(ms.value)
 
     def kernels(self, which: int) -> str:
-        """Kernels the last batch launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
+        """Kernels the last batch -- or the last ``preprocess_window`` / ``filter_window`` call -- launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
         5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
         7 coherence, 8 grid projection), named as rocprofv3 prints them."""
         buf = C.create_string_buffer(512)

@@ -1,7 +1,8 @@
 """The plans of tests/golden/fir_kernel_choice.json: the smallest shapes that reach every kernel of the one-wave FIR family
 (nmx_w64.hip) and every batch-size threshold of its launch geometry.  tests/golden/make_fir_kernel_choice.py records, and
 tests/test_fir_kernel_choice_gpu.py compares, the kernels a batch launched (stages 1, 3 and 6) and the SHA-256 of the
-table it returned.
+table it returned.  The hashes pin BYTES (a regression check); tests/fir_sample_probe_cases.py pins the VALUES of the same
+kernels, sample by sample against float64.
 
 Recordings: fixed-seed noise + a 20 Hz sine + per-channel offsets.  The 1 kHz cases run notch (50 Hz) + common average
 reference in front of the default features with bandpass_filter on; the other rates run the band-pass features alone.
