@@ -1,5 +1,6 @@
-// nmx_engine.inc -- host side of the engine: the Plan, scratch management and the parts below (plan building and the
-// stages' launchers: nmx_engine_plan_*.inc; C ABI: nmx_engine_abi.inc, nmx_engine_run.inc, nmx_engine_norm.inc).
+// nmx_engine.inc -- host side of the engine: the Plan, scratch management and the parts below (streams and events of a
+// chunk and a batch: nmx_engine_sched.inc; plan building and the stages' launchers: nmx_engine_plan_*.inc; C ABI:
+// nmx_engine_abi.inc, nmx_engine_run.inc, nmx_engine_norm.inc).
 // Included by nmx_api.hip (HIP backend: the product) and by
 // tests/emu/nmx_emu.cpp (single-thread logic emulator used by the CPU-only tests).  The
 // includer provides the be_* backend (allocation, copies, launches, events).
@@ -75,6 +76,23 @@ struct Block {
 using Buf = Block<be_alloc, be_free>;                 // device memory (ensure)
 using HostBuf = Block<be_host_alloc, be_host_free>;   // page-locked host memory
 
+#include "nmx_engine_sched.inc"
+
+// What a launch reports under: the index of its timer (nmx_last_timing_ms) and of its kernel list (nmx_last_kernels,
+// be_stage).  The numbers are ABI (include/nmx.h).
+enum Stage {
+  ST_BATCH = 0,      // the whole batch (timer only)
+  ST_PREP = 1,       // front end and pre-processing
+  ST_TIMEOSC = 2,
+  ST_BANK = 3,
+  ST_BURSTS = 4,
+  ST_SHARP = 5,
+  ST_BANK2 = 6,      // the bank's second launch, when its filters are split over two kernels
+  ST_COH = 7,
+  ST_PROJ = 8,       // grid projection: launched by chunk_finalize, behind the stages of run_chunk
+  ST_COUNT
+};
+
 // Where the next stage reads its windows: window w of channel c begins at x + c * ch_stride + (starts ? starts[w] :
 // w * win_stride).  run_chunk and nmx_preprocess_window keep one and hand it from stage to stage; every stage that writes
 // windows sets it to its output.
@@ -128,7 +146,7 @@ struct ResampleStage {
 // `mask` on kernel `kernel`; the channel-pair kinds come with the tables of nmx_k_bank_w64c/d/e.h (build_pair_tables).
 struct FirLaunch {
   unsigned mask = 0;
-  int stage = 3;       // timer / kernel-name stage it reports under (6: the bank's second launch)
+  Stage stage = ST_BANK;   // timer / kernel-name stage it reports under
   NmxFirKernel kernel = NMX_FIR_ONE;
   bool pipelined = false;   // NMX_FIR_ONE: large batches may run the pipelined persistent form (nmx_w64p_ok)
   const float* hc = nullptr;
@@ -204,26 +222,10 @@ struct Plan {
   std::vector<double> notch_taps_used;     // what the notch kernels convolve with: h, or delta - h (NmxBankArgs::residual)
   int device = 0;
   int n_cu = 256;                          // compute units of that device (the persistent kernels' grids)
-  be_stream_t stream = nullptr;            // the plan's own stream
-  be_stream_t last_stream = nullptr;       // stream of the last nmx_process_batch (may be the caller's): state calls wait for it
-  be_stream_t stream_b = nullptr;          // side stream: bursts chain overlaps time/osc + sharp waves
-  be_event_t ev_fork{}, ev_join[2]{};      // (join events per chunk parity: the next chunk starts under this one's side streams)
-  be_stream_t stream_d = nullptr;          // second side stream (NMX_OVERLAP=4): the sharp-wave analysis next to Hilbert + time / oscillatory
-  be_event_t ev_fork_d{}, ev_join_d[2]{};
-  be_stream_t stream_f = nullptr;          // finalize stream: feature normaliser + "rows ready" of a chunk, behind its main and side streams
-  be_event_t ev_main[2]{}, ev_final{};
-  long long chunk_seq = 0;                 // chunks launched so far: parity selects the double-buffered hand-off tensors
-  be_stream_t stream_c = nullptr;          // copy stream: host buffers move chunk by chunk next to the kernels
-  be_stream_t stream_o = nullptr;          // the features' way back: its waits for a chunk's completion do not hold the next input copy
-  be_event_t ev_in_free[2] = {};           // the raw samples of the chunk that used x_in2[i] have been consumed (re-referenced / filtered)
-  bool in_free[2] = {false, false};        // ... was recorded for that chunk (else: the chunk's completion)
-  bool raw_consumed = false;               // run_chunk: nothing behind the pre-processing reads the caller's samples
-  int in_free_slot = -1;                   // run_chunk records ev_in_free[slot] there (-1: not a recycled host buffer)
-  be_event_t ev_h2d{}, ev_done[2]{};
+  Schedule sched;                          // streams, events and overlap mode (nmx_engine_sched.inc)
   int host_chunk_windows = 512;            // hops per chunk when the caller hands over host memory ...
   int host_first_chunk = 128;              // ... after a short first one (nmx_engine_run.inc)
   int norm_chunk_windows = 384;           // device-resident batches with an attached normaliser (nmx_engine_run.inc; NMX_NORM_CHUNK_WINDOWS)
-  int overlap = 1;
   std::vector<void*> tables;               // device allocations of a fixed size (plan_alloc, upload): freed with the plan
   ~Plan() { for (void* t : tables) be_free(t); }   // (and every Buf frees itself: nmx_plan_destroy has set the device)
   std::map<int, NmxFft> fft_cache;
@@ -264,9 +266,8 @@ struct Plan {
   bool have_rawnorm = false;
   std::vector<std::vector<double>> pre_taps;
   int w_in = 0;           // samples per incoming window (raw_window when resampling, else window)
-  be_timer_t timers[9];   // 0 batch, 1 prep, 2 timeosc, 3 bank, 4 bursts, 5 sharp, 6 bank (second launch when split), 7 coherence,
-                          // 8 grid projection
-  std::string kernels[9];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
+  be_timer_t timers[ST_COUNT];
+  std::string kernels[ST_COUNT];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
   nmx_norm* norm = nullptr; // attached feature normaliser (not owned): applied to every chunk's rows on the device
   nmx_proj* proj = nullptr; // attached grid projection (not owned): behind the normaliser, on the same stream
   // offset split (nmx_engine_dc.inc): x = u + d per input row, the constants carried in float64 on the host

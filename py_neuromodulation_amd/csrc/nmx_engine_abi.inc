@@ -3,27 +3,6 @@
 // =========================================================================================
 namespace {
 
-// The plan's streams (f(stream, high priority)) and events, listed once: nmx_plan_create and nmx_plan_destroy walk them.
-template <class F>
-void plan_each_stream(Plan& P, F f) {
-  f(P.stream, false); f(P.stream_b, true); f(P.stream_f, false); f(P.stream_d, false); f(P.stream_c, false); f(P.stream_o, false);
-}
-template <class F>
-void plan_each_event(Plan& P, F f) {
-  f(P.ev_fork); f(P.ev_fork_d); f(P.ev_final); f(P.ev_h2d);
-  for (int i = 0; i < 2; ++i) { f(P.ev_join[i]); f(P.ev_join_d[i]); f(P.ev_main[i]); f(P.ev_in_free[i]); f(P.ev_done[i]); }
-}
-
-// Nothing of the plan's is in flight any more: what destroy, state reset, export and import wait for.  (stream_d runs the
-// sharp-wave analysis, which has no state: for the state calls an idle stream unless a batch is still running.)
-void plan_quiesce(Plan& P) {
-  be_sync(P.stream);
-  if (P.last_stream && P.last_stream != P.stream) be_sync(P.last_stream);   // batch launched on a caller's stream
-  be_sync(P.stream_b);
-  be_sync(P.stream_d);
-  be_sync(P.stream_f);
-}
-
 // The sections of the state blob, in the blob's order.  bytes: the section's size in this plan (0: the plan has none);
 // export_to / import_from get the section's start in the blob, import_from also its size there.  bytes_in (optional): the
 // size of the section in a blob another plan wrote, where that may differ (the raw normaliser of a ragged stream).
@@ -58,10 +37,10 @@ int nmx_plan_destroy(nmx_plan* plan) {
   Plan* P = (Plan*)plan;
   if (!P) return 0;
   be_set_device(P->device);
-  plan_quiesce(*P);
+  P->sched.quiesce();
   for (auto& t : P->timers) be_timer_destroy(t);
-  plan_each_event(*P, [](be_event_t& e) { be_event_destroy(e); });
-  plan_each_stream(*P, [](be_stream_t& s, bool) { be_stream_destroy(s); });
+  P->sched.each_event([](be_event_t& e) { be_event_destroy(e); });
+  P->sched.each_stream([](be_stream_t& s, bool) { be_stream_destroy(s); });
   delete P;   // every device block and the page-locked one: P.tables, the Bufs
   be_dev_pool_age();
   return 0;
@@ -113,11 +92,11 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   if (rc) return rc;
   P->n_cu = be_cu_count(P->device);
   P->w_in = P->d.raw_window > 0 ? P->d.raw_window : P->d.window;   // samples per incoming window
-  plan_each_stream(*P, [](be_stream_t& s, bool high) { s = high ? be_stream_create_high() : be_stream_create(); });
-  plan_each_event(*P, [](be_event_t& e) { be_event_create(e); });
+  P->sched.each_stream([](be_stream_t& s, bool high) { s = high ? be_stream_create_high() : be_stream_create(); });
+  P->sched.each_event([](be_event_t& e) { be_event_create(e); });
   P->host_chunk_windows = std::max(1, env_int("NMX_HOST_CHUNK_WINDOWS", 512));
   P->host_first_chunk = std::max(1, env_int("NMX_HOST_FIRST_CHUNK", 128));
-  P->overlap = env_int("NMX_OVERLAP", 4);
+  P->sched.mode = overlap_mode(env_int("NMX_OVERLAP", 4));
   for (auto& t : P->timers) be_timer_create(t);
   P->taps.resize(desc->n_filters);
   for (int i = 0; i < desc->n_filters; ++i) {
@@ -155,6 +134,8 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
 #ifndef NMX_HOST_EMU
   choose_notch_bank_fuse(*P);   // (behind every stage's own choice: it reads the notch's, the bank's and what sits between them)
 #endif
+  P->sched.bursts = P->have_bursts;
+  P->sched.sharp = P->have_sharp;
   P->bank.takes_dc = fir_stage_takes_dc(P->bank);   // (behind the fuse choice: a launch inside the notch kernel takes it)
   NMX_REQUIRE(!(P->d.features & NMX_F_BANDPOWER) || P->have_bank, "bandpass_filter enabled without filters");
   *out = (nmx_plan*)P;
@@ -191,7 +172,7 @@ int nmx_plan_get_offsets(nmx_plan* plan, double* d_in, double* d_pre, int* state
   if (!P) return nmx_fail(NMX_E_INVALID, "null plan");
   if (P->dc_ok && P->dc_dirty) {
     be_set_device(P->device);
-    dc_recompute(*P, P->stream);
+    dc_recompute(*P, P->sched.main);
   }
   if (d_in)
     for (int j = 0; j < P->d.n_channels_in; ++j)
@@ -222,7 +203,7 @@ int nmx_state_reset(nmx_plan* plan) {
   Plan* P = (Plan*)plan;
   if (!P) return nmx_fail(NMX_E_INVALID, "null plan");
   be_set_device(P->device);
-  plan_quiesce(*P);
+  P->sched.quiesce();
   for (const StateSection& S : kStateSections) S.reset(*P);
   return 0;
 }
@@ -240,7 +221,7 @@ int nmx_state_export(nmx_plan* plan, void* dst, int64_t n_bytes) {
   NMX_REQUIRE((size_t)n_bytes == state_bytes(*P), "state size mismatch");
   if (!n_bytes) return 0;
   be_set_device(P->device);
-  plan_quiesce(*P);
+  P->sched.quiesce();
   size_t at = 0;
   for (const StateSection& S : kStateSections) {
     S.export_to(*P, (char*)dst + at);
@@ -266,7 +247,7 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes) {
   NMX_REQUIRE((size_t)n_bytes == total, "state size mismatch");
   if (!n_bytes) return 0;
   be_set_device(P->device);
-  plan_quiesce(*P);
+  P->sched.quiesce();
   size_t at = 0;
   for (int i = 0; i < n_sections; ++i) {
     if ((rc = kStateSections[i].import_from(*P, (const char*)src + at, size[i]))) return rc;

@@ -180,25 +180,21 @@ int build_bursts(Plan& P) {
   return 0;
 }
 
-// The bursts chain of one chunk (nw hops, parity `par`) behind the bank on the main stream `s`: Hilbert envelope, threshold walk,
+// The bursts chain of one chunk (nw hops) of batch `b` behind the bank on its main stream: Hilbert envelope, threshold walk,
 // run statistics.  Its sequential, latency-bound part (walk -> run statistics: a few waves) runs on the high-priority side
-// stream stream_b next to the throughput kernels that follow on `s` (NMX_OVERLAP >= 2; 1: Hilbert too; 0: one stream), and
-// ev_join[par] marks its end.
-static int launch_burst_stage(Plan& P, int par, int nw, float* d_out, be_stream_t s, bool tev) {
+// stream next to the throughput kernels that follow on the main stream -- from the walk on, or from the Hilbert kernel on,
+// or not at all: the batch's schedule says (nmx_engine_sched.inc).
+static int launch_burst_stage(Plan& P, const BatchSched& b, int nw, float* d_out, bool tev) {
   BurstStage& B = P.bursts;
+  const int par = P.sched.parity();
   const int n_seq = P.d.n_channels * P.d.n_burst_bands, W = P.d.window;
   Buf& B_env = B.env[par];
   Buf& B_thr = B.thr[par];
   int rc;
   if ((rc = ensure(B_thr, (size_t)nw * n_seq * sizeof(float)))) return rc;
-  be_stream_t sb = s;
-  auto fork = [&]() {
-    sb = P.stream_b;
-    be_event_record(P.ev_fork, s);
-    be_stream_wait(sb, P.ev_fork);
-  };
-  if (P.overlap == 1) fork();
-  if (tev) be_timer_start(P.timers[4], sb);
+  be_stream_t sb = b.s;
+  if (P.sched.hilbert_on_side(b)) sb = P.sched.fork_bursts(b);
+  if (tev) be_timer_start(P.timers[ST_BURSTS], sb);
   const unsigned char* env_full = nullptr;
   if (B.own_hilbert) {
     NmxHilbertArgs H = B.hil;
@@ -224,7 +220,7 @@ static int launch_burst_stage(Plan& P, int par, int nw, float* d_out, be_stream_
       B.env_rows += (long long)f.size();
     }
   }
-  if (P.overlap >= 2) fork();
+  if (P.sched.walk_on_side(b)) sb = P.sched.fork_bursts(b);
   NmxBurstThrArgs T = B.bthr;
   T.top = B.d_top; T.counts = B.d_counts; T.floor = B.d_floor;
   NmxBurstWalkSeg seg[3];
@@ -248,7 +244,7 @@ static int launch_burst_stage(Plan& P, int par, int nw, float* d_out, be_stream_
   S.env = (const float*)B_env.p; S.thr = (const float*)B_thr.p; S.out = d_out; S.n_windows = nw;
   S.full = env_full;
   be_launch_burst_stat(S, B.stat_kind, nw * n_seq, (size_t)S.lds_floats * 4, sb);
-  if (tev) be_timer_stop(P.timers[4], sb);
-  if (P.overlap) be_event_record(P.ev_join[par], sb);
+  if (tev) be_timer_stop(P.timers[ST_BURSTS], sb);
+  P.sched.join_bursts(b, sb);
   return 0;
 }

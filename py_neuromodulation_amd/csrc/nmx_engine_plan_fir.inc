@@ -199,8 +199,8 @@ static bool fir_stage_takes_dc(const FirStage& S) {
 // the plan moved into the notch kernel (FirLaunch::fused) is skipped unless `with_fused` (nmx_filter_window: no notch).
 static void launch_fir_stage(Plan& P, const FirStage& S, const NmxBankArgs& A, int n_items, be_stream_t s, bool timed = false,
                              bool with_fused = false) {
-  const int first = S.launches[0].stage;
-  int cur = first;
+  const Stage first = S.launches[0].stage;
+  Stage cur = first;
   if (timed) be_timer_start(P.timers[cur], s);
   if (!S.w64) {
     be_launch_bank(A, n_items, P.nt_bank, (size_t)A.lds_floats * 4, s);
@@ -239,7 +239,7 @@ void choose_notch_bank_fuse(Plan& P) {
   if (!want || !P.have_notch || !P.have_bank || P.have_resample || P.have_rawnorm) return;
   if (!P.notch.w64 || !P.bank.w64 || P.notch.launches.size() != 1 || P.bank.launches.size() != 2) return;
   FirLaunch& L = P.bank.launches[1];
-  if (L.stage != 6 || L.kernel != NMX_FIR_PAIR_E) return;
+  if (L.stage != ST_BANK2 || L.kernel != NMX_FIR_PAIR_E) return;
   if (P.notch.launches[0].kernel != NMX_FIR_PAIR_E || !nmx_w64e_notch_w1000(P.notch.a)) return;
   if (P.bank.a.W != P.notch.a.W || P.bank.a.n_channels != P.notch.a.n_channels) return;
   if (!nmx_w64e_fits(__builtin_popcount(L.mask) + (want == 2 ? 1 : 0))) return;
@@ -357,11 +357,11 @@ struct FirRules {
   int w64_lo;     // the one-wave M = 2048 kernels for W + reach in (w64_lo, 2048]
   bool w64x2;     // the M = 4096 one-wave kernel for W + reach in (2048, 4096] (device only)
   bool hilbert;   // the LDS bank kernel also holds the Hilbert transform's buffers
-  int stage;      // timer / kernel-name stage of its launches
+  Stage stage;    // timer / kernel-name stage of its launches
 };
 
 // a launch of the filters of `mask` on the one-channel M = 2048 kernels (NMX_FIR_ONE); S.w is built
-static FirLaunch fir_one_launch(const FirStage& S, unsigned mask, int stage) {
+static FirLaunch fir_one_launch(const FirStage& S, unsigned mask, Stage stage) {
   FirLaunch L{mask, stage};
   L.pipelined = nmx_w64p_ok(S.a, __builtin_popcount(mask), S.w.lds_floats);
   return L;
@@ -450,7 +450,7 @@ int build_bank(Plan& P) {
   // Stockham of half the length, measured on BASELINE config 5)
   const bool fits_x2 = (d.window & 3) == 0 && !(d.bp_features & 6u);
   std::vector<std::vector<float>> H;
-  int rc = build_fir_stage(P, live, FirRules{reach, 512, fits_x2, hil, 3}, &S, &H);
+  int rc = build_fir_stage(P, live, FirRules{reach, 512, fits_x2, hil, ST_BANK}, &S, &H);
   if (rc) return rc;
   if (hil && !A.partitioned) {
     A.hil_full = d.window & 1;
@@ -488,7 +488,7 @@ int build_bank(Plan& P) {
       }
     }
     if (all & ~mask) {
-      FirLaunch rest = fir_one_launch(S, all & ~mask, mask ? 6 : 3);
+      FirLaunch rest = fir_one_launch(S, all & ~mask, mask ? ST_BANK2 : ST_BANK);
       // (one spectrum's room is left free: the notch's, when the launch moves into the notch kernel with it in LDS --
       // choose_notch_bank_fuse, NMX_NOTCH_SW_FUSE=2)
       if (env_int("NMX_BANK_W64E", 1) == 1 && nmx_w64e_fits(__builtin_popcount(rest.mask) + 1) &&
@@ -530,7 +530,7 @@ int build_notch(Plan& P) {
   F.sw_index = -1;
   F.store_raw = 1;
   std::vector<std::vector<float>> H;
-  int rc = build_fir_stage(P, {P.notch_taps_used.data()}, FirRules{2 * half, 1024, false, false, 1}, &S, &H);
+  int rc = build_fir_stage(P, {P.notch_taps_used.data()}, FirRules{2 * half, 1024, false, false, ST_PREP}, &S, &H);
   if (rc) return rc;
 #ifndef NMX_HOST_EMU
   // two channels per 2048-point complex transform (nmx_k_bank_w64e.h, PAD = 1)

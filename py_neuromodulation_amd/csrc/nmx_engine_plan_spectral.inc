@@ -462,11 +462,11 @@ static int launch_timeosc_stage(Plan& P, const WinView& v, int nw, float* d_out,
     if ((rc = ensure(S.todo, (size_t)((nw + 15) / 16) * C * sizeof(unsigned short)))) return rc;
     A.todo = (unsigned short*)S.todo.p;
   }
-  if (tev) be_timer_start(P.timers[2], s);
-  be_stage(2);
+  if (tev) be_timer_start(P.timers[ST_TIMEOSC], s);
+  be_stage(ST_TIMEOSC);
   be_launch_timeosc(A, S.kind, nw * C, S.nt, (size_t)A.lds_floats * 4, P.n_cu, s);
-  if (tev) be_timer_stop(P.timers[2], s);
-  if (smm) { be_stage(0); be_launch_timeosc_redo(A, nw * C, s); }
+  if (tev) be_timer_stop(P.timers[ST_TIMEOSC], s);
+  if (smm) { be_stage(ST_BATCH); be_launch_timeosc_redo(A, nw * C, s); }
   return 0;
 }
 
@@ -537,8 +537,8 @@ static void launch_coh_stage(Plan& P, const WinView& v, int nw, float* d_out, be
   NmxCohArgs A = P.coherence.a;
   view_into(A, v);
   A.out = d_out;
-  if (tev) be_timer_start(P.timers[7], s);
-  be_stage(7);
+  if (tev) be_timer_start(P.timers[ST_COH], s);
+  be_stage(ST_COH);
   be_launch_coh(A, nw * A.n_pairs, s);
-  if (tev) be_timer_stop(P.timers[7], s);
+  if (tev) be_timer_stop(P.timers[ST_COH], s);
 }

@@ -163,7 +163,7 @@ int build_prefilters(Plan& P) {
     F.burst_index = -1;
     F.sw_index = 0;
     F.store_raw = 0;
-    int rc = build_fir_stage(P, {P.pre_taps[i].data() + (half - uh)}, FirRules{uh, 1024, false, false, 1}, &P.pre[i]);
+    int rc = build_fir_stage(P, {P.pre_taps[i].data() + (half - uh)}, FirRules{uh, 1024, false, false, ST_PREP}, &P.pre[i]);
     if (rc) return rc;
   }
   return 0;
@@ -431,10 +431,10 @@ static int launch_sharp_stage(Plan& P, int par, int nw, float* d_out, be_stream_
     if ((rc = ensure(S.todo[par], (size_t)n_items))) return rc;
     A.todo = (unsigned char*)S.todo[par].p;
   }
-  be_stage(5);
-  if (tev) be_timer_start(P.timers[5], ss);
+  be_stage(ST_SHARP);
+  if (tev) be_timer_start(P.timers[ST_SHARP], ss);
   be_launch_sharp(A, S.kind, n_items, (size_t)A.lds_floats * 4, ss);
-  if (tev) be_timer_stop(P.timers[5], ss);
+  if (tev) be_timer_stop(P.timers[ST_SHARP], ss);
   return 0;
 }
 

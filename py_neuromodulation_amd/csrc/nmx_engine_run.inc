@@ -35,26 +35,22 @@ static int run_prep_stages(Plan& P, WinView& v, int nw, be_stream_t s, const Nmx
   return 0;
 }
 
+// One chunk of batch `b`: the stage order of DESIGN section 3 (which stream, which event: nmx_engine_sched.inc).
 // d_x / ldx address the recording with ABSOLUTE sample indices (the windows' starts); only the samples
 // [lo, hi) that the windows of this chunk touch are read (d_x may point lo samples before a buffer that
 // holds just that range).
 // d_pre (may be null): where the pre-processed windows of this chunk go, [nw][C][W] on the device.
-static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, long long hi,
-                     const long long* d_starts, int nw, float* d_out, be_stream_t s, bool timed,
-                     float* d_pre = nullptr, const int64_t* h_starts = nullptr) {
+// samples_free (may be null): recorded once nothing more of this chunk reads the caller's samples -- if that point exists
+// (*samples_freed says; a plan whose features read the samples themselves has none before the chunk is complete).
+static int run_chunk(Plan& P, const BatchSched& b, const float* d_x, long long ldx, long long lo, long long hi,
+                     const long long* d_starts, int nw, float* d_out, bool timed, float* d_pre = nullptr,
+                     const int64_t* h_starts = nullptr, be_event_t* samples_free = nullptr, bool* samples_freed = nullptr) {
   const nmx_plan_desc& d = P.d;
   const int C = d.n_channels, W = d.window;
+  const be_stream_t s = b.s;
   int rc;
-  // The tensors the SIDE streams read (envelopes, thresholds, sharp-wave series and flags) exist twice: this chunk's main
-  // stream does not wait for the previous chunk's threshold walk / run statistics / sharp waves -- its re-reference,
-  // notch and FIR bank run under them -- only for the chunk before that, whose set it is about to overwrite.
-  const int par = (int)(P.chunk_seq & 1);
-  if (P.chunk_seq >= 2) {
-    be_stream_wait(s, P.ev_join[par]);
-    be_stream_wait(s, P.ev_join_d[par]);
-  }
-  if (P.overlap == 1 && P.chunk_seq >= 1)   // (this schedule runs the Hilbert kernel on the side stream too: it reads the
-    be_stream_wait(s, P.ev_join[par ^ 1]);  // band series `yb`, which exists once)
+  const int par = P.sched.parity();   // selects the hand-off tensors the side streams read (they exist twice)
+  P.sched.begin_chunk(b);
   Buf& B_env = P.bursts.env[par];
   Buf& B_swy = P.sharp.swy[par];
   // ---- pre-processing -------------------------------------------------------------------
@@ -63,8 +59,8 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
   // real-time loop would spend a fifth of its 0.45 ms on: batches of fewer than 8 hops keep the whole-call timer only
   const bool tev = timed && nw >= 8;
   if (timed) be_stage_reset();
-  if (tev) be_timer_start(P.timers[1], s);
-  be_stage(1);
+  if (tev) be_timer_start(P.timers[ST_PREP], s);
+  be_stage(ST_PREP);
   if ((rc = launch_front(P, d_x, ldx, lo, hi - lo, true, s, v))) return rc;
   bool raw_live = v.x == d_x;   // `v` still addresses the caller's samples
   // Window starts in arithmetic progression (every stream with an integer hop; h_starts = the host's copy): the kernels
@@ -77,7 +73,7 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     if (hop >= 0) { v.x += h_starts[0]; v.win_stride = hop; v.starts = nullptr; }
   }
   // the bank's second launch inside the notch kernel (choose_notch_bank_fuse): its outputs exist before the notch runs
-  // (the wait on ev_join_d[par] above has freed this parity's sharp-wave series)
+  // (begin_chunk has freed this parity's sharp-wave series)
   NmxBankArgs fuse_a{};
   if (P.notch_bank_fuse) {
     fuse_a = P.bank.a;
@@ -96,21 +92,20 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     T.y = d_pre; T.C = C; T.W = W;
     be_launch_tap(T, nw * C, s);
   }
-  if (tev) be_timer_stop(P.timers[1], s);
+  if (tev) be_timer_stop(P.timers[ST_PREP], s);
   // (a host batch recycles its two input buffers: the copy of the chunk after next waits for THIS point of the stream, not
-  // for the chunk's threshold walk and normaliser -- process_batch_impl)
-  P.raw_consumed = !raw_live;
-  if (P.raw_consumed && P.in_free_slot >= 0) be_event_record(P.ev_in_free[P.in_free_slot], s);
+  // for the chunk's threshold walk and normaliser -- stage_host_chunk)
+  const bool freed = !raw_live && samples_free;
+  if (freed) be_event_record(*samples_free, s);
+  if (samples_freed) *samples_freed = freed;
   // ---- the carried offset (nmx_engine_dc.inc): consumers take it on load; one that cannot reads a copy with it added back,
   // made at most once per chunk (dc_bind)
   bool dc_made = false;
   // ---- features --------------------------------------------------------------------------
-  // Launch order on the main stream `s`: FIR bank (it feeds bursts and sharp waves) -> Hilbert -> time / oscillatory
-  // -> sharp waves.  The sequential, latency-bound part of the bursts chain (threshold walk -> run statistics: a few
-  // waves) runs on the high-priority side stream stream_b next to the throughput kernels that follow (NMX_OVERLAP >= 2;
-  // 1: Hilbert too; 0: one stream).  NMX_OVERLAP=4 also moves the sharp-wave analysis -- scalar / latency bound list
-  // code -- to a second side stream, next to Hilbert and the time / oscillatory kernel (VALU bound).
-  be_stage(3);
+  // Launch order: FIR bank (it feeds bursts and sharp waves) -> Hilbert -> threshold walk -> run statistics -> time /
+  // oscillatory -> coherence -> sharp waves.  The walk and the statistics are sequential and latency bound (a few waves), the
+  // sharp-wave analysis scalar list code: the schedule may run them beside the throughput kernels (NMX_OVERLAP).
+  be_stage(ST_BANK);
   if (P.have_bank) {
     NmxBankArgs A = P.bank.a;
     A.out = d_out;
@@ -130,116 +125,79 @@ static int run_chunk(Plan& P, const float* d_x, long long ldx, long long lo, lon
     launch_fir_stage(P, P.bank, A, nw * C, s, tev);
     launch_kalman(P, nw, d_out, s);
   }
-  const bool sharp_side = P.overlap == 4 && P.have_sharp;
+  const bool sharp_side = P.sched.sharp_on_side(b);
   if (sharp_side) {
-    be_event_record(P.ev_fork_d, s);
-    be_stream_wait(P.stream_d, P.ev_fork_d);
-    if ((rc = launch_sharp_stage(P, par, nw, d_out, P.stream_d, tev))) return rc;
-    be_event_record(P.ev_join_d[par], P.stream_d);
+    if ((rc = launch_sharp_stage(P, par, nw, d_out, P.sched.fork_sharp(b), tev))) return rc;
+    P.sched.join_sharp();
   }
-  be_stage(4);
-  if (P.have_bursts && (rc = launch_burst_stage(P, par, nw, d_out, s, tev))) return rc;
+  be_stage(ST_BURSTS);
+  if (P.have_bursts && (rc = launch_burst_stage(P, b, nw, d_out, tev))) return rc;
   if ((rc = launch_timeosc_stage(P, v, nw, d_out, s, tev, dc_made))) return rc;
   launch_coh_stage(P, v, nw, d_out, s, tev);
   if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
-  // (no join on the main stream: the chunk is finished by chunk_finalize below, on its own stream)
-  be_event_record(P.ev_main[par], s);
-  be_stage(0);
-  if (timed) for (int i = 0; i < 8; ++i) P.kernels[i] = be_stage_kernels(i);
+  P.sched.end_main(b);
+  be_stage(ST_BATCH);
+  if (timed) for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (the projection's: chunk_finalize)
   return be_check_launch();
 }
 
 // What follows a chunk's kernels.  With a feature normaliser attached (sequential over hops: chunks in order) it runs on the
-// finalize stream, behind the chunk's main stream and both side streams, and ev_done[par] marks the rows complete.
-// Without one nothing is launched: "the rows are there" is the chunk's own events (chunk_wait_done) -- a detour over a
+// finalize stream, behind the chunk's main stream and both side streams, and the schedule marks the rows complete there.
+// Without one nothing is launched: "the rows are there" is the chunk's own events (Schedule::wait_done) -- a detour over a
 // third stream costs two cross-stream hand-offs per call, as much as the whole batch of a light plan (BASELINE
 // config[1]: 0.27 ms of kernel, 0.70 ms per call with the detour, 0.30 without).
-// (`inline_on`: a batch of a few hops on ONE stream -- process_batch_impl -- normalises there too)
+// (a batch of a few hops on ONE stream normalises there too)
 // An attached grid projection (nmx_engine_proj.inc) follows the normaliser on the same stream: it reads normalised rows.
-// `ld`: the row stride (features + the plan's extra columns); `timed`: the batch's first chunk (stage 8 timer / kernel name).
+// `ld`: the row stride (features + the plan's extra columns); `timed`: the batch's first chunk (projection timer / kernel name).
 static int proj_launch(nmx_proj* proj, float* rows, long long ld, int n_rows, be_stream_t s);
-static int chunk_finalize(Plan& P, float* d_outk, int ld, int nw, be_stream_t inline_on = nullptr, bool timed = false) {
-  const int par = (int)(P.chunk_seq & 1);
+static bool plan_finalizes(const Plan& P) { return P.norm || P.proj; }
+static int chunk_finalize(Plan& P, const BatchSched& b, float* d_outk, int ld, int nw, bool timed) {
   int rc = 0;
-  if (timed) P.kernels[8].clear();
-  if (P.norm || P.proj) {
-    be_stream_t sf = inline_on ? inline_on : P.stream_f;
-    if (!inline_on) {
-      be_stream_wait(sf, P.ev_main[par]);
-      if (P.have_bursts && P.overlap) be_stream_wait(sf, P.ev_join[par]);
-      if (P.overlap == 4 && P.have_sharp) be_stream_wait(sf, P.ev_join_d[par]);
-    }
+  if (timed) P.kernels[ST_PROJ].clear();
+  if (plan_finalizes(P)) {
+    be_stream_t sf = P.sched.begin_finalize(b);
     if (P.norm) rc = nmx_norm_process(P.norm, d_outk, ld, nw, 1, (void*)sf);
     if (P.proj && !rc) {
       const bool tev = timed && nw >= 8;
-      if (tev) be_timer_start(P.timers[8], sf);
-      if (timed) { be_stage_reset(); be_stage(8); }
+      if (tev) be_timer_start(P.timers[ST_PROJ], sf);
+      if (timed) { be_stage_reset(); be_stage(ST_PROJ); }
       rc = proj_launch(P.proj, d_outk, ld, nw, sf);
-      if (tev) be_timer_stop(P.timers[8], sf);
-      if (timed) { P.kernels[8] = be_stage_kernels(8); be_stage(0); }
+      if (tev) be_timer_stop(P.timers[ST_PROJ], sf);
+      if (timed) { P.kernels[ST_PROJ] = be_stage_kernels(ST_PROJ); be_stage(ST_BATCH); }
     }
-    be_event_record(P.ev_done[par], sf);
+    P.sched.end_finalize(sf);
   }
-  ++P.chunk_seq;
+  P.sched.next_chunk();
   return rc;
 }
-// stream `st` waits until the chunk of parity `par` is complete (its rows final); `own_main`: st IS the chunk's main stream
-static void chunk_wait_done(Plan& P, be_stream_t st, int par, bool own_main) {
-  if (P.norm || P.proj) { be_stream_wait(st, P.ev_done[par]); return; }
-  if (!own_main) be_stream_wait(st, P.ev_main[par]);
-  if (P.have_bursts && P.overlap) be_stream_wait(st, P.ev_join[par]);
-  if (P.overlap == 4 && P.have_sharp) be_stream_wait(st, P.ev_join_d[par]);
-}
 
-static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples,
-                              const int64_t* starts, int64_t n_windows, float* out, uint8_t* nan_mask,
-                              int memspace, void* hip_stream, float* pre) {
-  Plan* Pp = (Plan*)plan;
-  if (!Pp || !x || !starts || !out) return nmx_fail(NMX_E_INVALID, "null argument");
-  Plan& P = *Pp;
-  const nmx_plan_desc& d = P.d;
+// ---- a batch, in parts ----------------------------------------------------------------------------------------------------
+static int check_batch_args(Plan* P, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                            float* out, int memspace) {
+  if (!P || !x || !starts || !out) return nmx_fail(NMX_E_INVALID, "null argument");
   NMX_REQUIRE(n_windows >= 1, "n_windows must be >= 1");
   NMX_REQUIRE(memspace == 0 || memspace == 1, "memspace must be 0 (host) or 1 (device)");
-  NMX_REQUIRE(ldx >= n_samples && n_samples >= P.w_in, "ldx / n_samples too small");
+  NMX_REQUIRE(ldx >= n_samples && n_samples >= P->w_in, "ldx / n_samples too small");
   bool mod4 = true;
   for (int64_t i = 0; i < n_windows; ++i) {
-    NMX_REQUIRE(starts[i] >= 0 && starts[i] + P.w_in <= n_samples, "window outside the data");
+    NMX_REQUIRE(starts[i] >= 0 && starts[i] + P->w_in <= n_samples, "window outside the data");
     mod4 = mod4 && (starts[i] & 3) == 0;
   }
-  Pp->starts_mod4 = mod4;
-  int rc = be_set_device(P.device);
-  if (rc) return rc;
-  be_stream_t s = hip_stream ? (be_stream_t)hip_stream : P.stream;
-  P.last_stream = s;
-  const int Cin = d.n_channels_in, F = d.n_outputs + d.n_extra_cols;   // (F: the row stride)
-  const float* d_x = x;
-  long long d_ldx = ldx;
-  float* d_out = out;
-  unsigned char* d_mask = nan_mask;
-  if ((rc = dc_prepare(P, x, ldx, starts[0], memspace == 0, s))) return rc;
-  if ((rc = ensure(P.starts, (size_t)n_windows * sizeof(long long)))) return rc;
-  be_h2d_async(P.starts.p, starts, (size_t)n_windows * sizeof(long long), s);
-  const bool host = memspace == 0;
-  // The one-window call of a real-time loop (and any host batch of a few hops): ONE stream for copies, kernels and the
-  // normaliser.  Side streams buy such a batch nothing -- its kernels are microseconds -- and every cross-stream hand-off
-  // (fork / join of the bursts and sharp-wave chains, finalize stream, copy stream) is an event round trip of 10 - 25 us
-  // on a 0.4 ms call.  (NMX_TINY_INLINE=0: the schedule of large batches.)
-  const bool tiny = P.tiny_inline && host && n_windows < 8 && !P.pipe_in_ready && !P.pipe_out_done;
-  struct OverlapGuard { Plan& P; int keep; ~OverlapGuard() { P.overlap = keep; } } overlap_guard{P, P.overlap};
-  if (tiny) P.overlap = 0;
-  be_stream_t sc = tiny ? s : P.stream_c;   // the copy stream of this batch (input)
-  be_stream_t so = tiny ? s : P.stream_o;   // ... and the one the features come back on
-  if (host) {
-    if ((rc = ensure(P.out, (size_t)n_windows * F * sizeof(float)))) return rc;
-    d_out = (float*)P.out.p;
-    if (nan_mask) {
-      if ((rc = ensure(P.mask, (size_t)n_windows * Cin))) return rc;
-      d_mask = (unsigned char*)P.mask.p;
-    }
-  }
-  // Host buffers move chunk by chunk on a copy stream: while chunk k computes, the host thread is already
-  // copying the samples of chunk k + 1 (pageable memory: the copy blocks the host, not the GPU) and the
-  // features of chunk k - 1 travel back.  Device buffers: one chunk = NMX_CHUNK_WINDOWS hops.
+  P->starts_mod4 = mod4;
+  return 0;
+}
+
+// Hops per chunk of one batch.
+// Host buffers move chunk by chunk on a copy stream: while chunk k computes, the host thread is already
+// copying the samples of chunk k + 1 (pageable memory: the copy blocks the host, not the GPU) and the
+// features of chunk k - 1 travel back.  Device buffers: one chunk = NMX_CHUNK_WINDOWS hops.
+struct ChunkSizes {
+  bool host;
+  int64_t dev_chunk, host_first, host_big;
+  int64_t at(int64_t w0) const { return host ? (w0 == 0 ? host_first : host_big) : dev_chunk; }
+};
+static ChunkSizes batch_chunk_sizes(const Plan& P, bool host) {
+  ChunkSizes z{host, 0, 0, 0};
   // (a plan without a hand-off tensor -- time / oscillatory features straight from the recording -- has nothing a chunk
   // would bound: device-resident batches go out as ONE launch of up to 16 chunks' worth of hops)
   const bool no_handoff = !P.have_bank && !P.have_notch && !P.front.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
@@ -247,49 +205,127 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   // chunk's kernels, so only the last chunk's pass is exposed -- against that, shorter chunks cost the main kernels 0.16 ms
   // per 1024 hops at 256.  Round 6, scans + cells at ~75 us per pass, headline step with / without the z-score:
   // 128 hops 7.30 / 6.60 ms, 256: 6.90 / 6.57, 384: 6.77 / 6.56, 512: 6.85 / 6.53, 1024: 7.02 / 6.60)
-  const int64_t dev_chunk = no_handoff ? (int64_t)P.chunk_windows * 16
-                            : (P.norm ? std::min<int64_t>(P.chunk_windows, P.norm_chunk_windows) : (int64_t)P.chunk_windows);
+  z.dev_chunk = no_handoff ? (int64_t)P.chunk_windows * 16
+                           : (P.norm ? std::min<int64_t>(P.chunk_windows, P.norm_chunk_windows) : (int64_t)P.chunk_windows);
   // host buffers: a SHORT first chunk (its copy is the only one nothing hides; the kernels start a quarter of a
   // millisecond after the call), then chunks as long as the device's own -- the sequential, latency-bound members of the
   // path (threshold walk, feature normaliser: ~1 ms per launch whatever the hop count) are paid per chunk, and a chunk's
   // copy runs under the chunk before it
-  const int64_t host_big = std::min<int64_t>(P.chunk_windows, P.host_chunk_windows);
-  int64_t host_first = std::min<int64_t>(host_big, P.host_first_chunk);
+  z.host_big = std::min<int64_t>(P.chunk_windows, P.host_chunk_windows);
+  z.host_first = std::min<int64_t>(z.host_big, P.host_first_chunk);
   if (host && P.have_bursts)   // a fresh stream: the whole fill phase of the burst history in ONE sort (nmx_k_burst_fill.h)
-    host_first = std::max<int64_t>(host_first, P.bursts.fill_hops((int)host_big));
-  auto chunk_at = [&](int64_t w0_) { return host ? (w0_ == 0 ? host_first : host_big) : dev_chunk; };
-  be_timer_start(P.timers[0], s);
+    z.host_first = std::max<int64_t>(z.host_first, P.bursts.fill_hops((int)z.host_big));
+  return z;
+}
+
+// The samples [lo, hi) of every row of a host recording -> input buffer k & 1 of the plan, for chunk k of batch `b`;
+// *d_xk / *ldxk address them with absolute sample indices.
+static int stage_host_chunk(Plan& P, const BatchSched& b, int k, const float* x, int64_t ldx, long long lo, long long hi,
+                            const float** d_xk, long long* ldxk) {
+  const int Cin = P.d.n_channels_in;
+  const be_stream_t sc = P.sched.in_stream(b);
+  Buf& xb = P.x_in2[k & 1];
+  const long long n_range = hi - lo;
+  int rc;
+  if ((rc = ensure(xb, (size_t)Cin * n_range * sizeof(float)))) return rc;
+  P.sched.wait_input_free(b, k, plan_finalizes(P));
+  if (P.pipe_in_ready) {
+    // the caller converts the recording slice by slice on its own threads: the chunk's samples are copied piece by
+    // piece as they are published (a caller that publishes finer than a chunk gets its copies under its conversion)
+    long long pos = lo, spins = 0;
+    while (pos < hi) {
+      const long long want = std::min<long long>(hi, pos + 4096);
+      long long ready = __atomic_load_n(P.pipe_in_ready, __ATOMIC_ACQUIRE);
+      if (ready < want) {
+        if (++spins > 2000000) return nmx_fail(NMX_E_INVALID, "nmx_plan_set_pipeline: the input never became ready");
+        std::this_thread::sleep_for(std::chrono::microseconds(5));
+        continue;
+      }
+      const long long upto = std::min<long long>(hi, ready);
+      be_h2d_2d_async((float*)xb.p + (pos - lo), (size_t)n_range * sizeof(float), x + pos, (size_t)ldx * sizeof(float),
+                      (size_t)(upto - pos) * sizeof(float), (size_t)Cin, sc);
+      pos = upto;
+    }
+  } else {
+    be_h2d_2d_async(xb.p, (size_t)n_range * sizeof(float), x + lo, (size_t)ldx * sizeof(float),
+                    (size_t)n_range * sizeof(float), (size_t)Cin, sc);
+  }
+  P.sched.input_copied(b);
+  *d_xk = (const float*)xb.p - lo;
+  *ldxk = n_range;
+  return 0;
+}
+
+// Where a batch's rows and NaN mask are computed (d_*: the caller's buffers, or the plan's for a host batch) and where the
+// caller wants them.
+struct BatchOut {
+  float *out, *d_out;
+  uint8_t* nan_mask;
+  unsigned char* d_mask;
+  int F, Cin;   // row stride; mask bytes per row
+};
+// features of the finished chunk of parity `par` (rows [w0, w0 + nw)) -> host
+// (on its own stream: behind the copy stream's input copies these waits held the copy of chunk k + 1 until chunk
+// k - 1 was complete -- on a young stream, whose threshold walks are the long pole, 6 ms after its samples were ready)
+static void fetch_back(Plan& P, const BatchSched& b, const BatchOut& o, int64_t w0, int64_t nw, int par) {
+  const be_stream_t so = P.sched.out_stream(b);
+  if (!b.inline_all) P.sched.wait_done(b, so, par, plan_finalizes(P), false);
+  be_d2h_async(o.out + (size_t)w0 * o.F, o.d_out + (size_t)w0 * o.F, (size_t)nw * o.F * sizeof(float), so);
+  if (o.nan_mask) be_d2h_async(o.nan_mask + (size_t)w0 * o.Cin, o.d_mask + (size_t)w0 * o.Cin, (size_t)nw * o.Cin, so);
+  if (P.pipe_out_done && P.pipe_marks.size() < P.pipe_marks.capacity()) {   // tell the caller's threads: rows [0, w0 + nw) are there
+    P.pipe_marks.push_back(Plan::Progress{P.pipe_out_done, w0 + nw});
+    be_host_fn(so, [](void* a) { auto* m = (Plan::Progress*)a; __atomic_store_n(m->dst, m->value, __ATOMIC_RELEASE); },
+               &P.pipe_marks.back());
+  }
+}
+
+static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples,
+                              const int64_t* starts, int64_t n_windows, float* out, uint8_t* nan_mask,
+                              int memspace, void* hip_stream, float* pre) {
+  int rc = check_batch_args((Plan*)plan, x, ldx, n_samples, starts, n_windows, out, memspace);
+  if (rc) return rc;
+  Plan& P = *(Plan*)plan;
+  const nmx_plan_desc& d = P.d;
+  if ((rc = be_set_device(P.device))) return rc;
+  const bool host = memspace == 0;
+  // The one-window call of a real-time loop (and any host batch of a few hops): ONE stream for copies, kernels and the
+  // normaliser.  Side streams buy such a batch nothing -- its kernels are microseconds -- and every cross-stream hand-off
+  // (fork / join of the bursts and sharp-wave chains, finalize stream, copy stream) is an event round trip of 10 - 25 us
+  // on a 0.4 ms call.  (NMX_TINY_INLINE=0: the schedule of large batches.)
+  const bool tiny = P.tiny_inline && host && n_windows < 8 && !P.pipe_in_ready && !P.pipe_out_done;
+  const BatchSched b{hip_stream ? (be_stream_t)hip_stream : P.sched.main, tiny};
+  const be_stream_t s = b.s;
+  P.sched.last_stream = s;
+  BatchOut o{out, out, nan_mask, nan_mask, d.n_outputs + d.n_extra_cols, d.n_channels_in};
+  if ((rc = dc_prepare(P, x, ldx, starts[0], host, s))) return rc;
+  if ((rc = ensure(P.starts, (size_t)n_windows * sizeof(long long)))) return rc;
+  be_h2d_async(P.starts.p, starts, (size_t)n_windows * sizeof(long long), s);
+  if (host) {
+    if ((rc = ensure(P.out, (size_t)n_windows * o.F * sizeof(float)))) return rc;
+    o.d_out = (float*)P.out.p;
+    if (nan_mask) {
+      if ((rc = ensure(P.mask, (size_t)n_windows * o.Cin))) return rc;
+      o.d_mask = (unsigned char*)P.mask.p;
+    }
+  }
+  const ChunkSizes sizes = batch_chunk_sizes(P, host);
+  be_timer_start(P.timers[ST_BATCH], s);
   int64_t prev_w0 = -1, prev_nw = 0;
   int k = 0, last_par = -1;
   P.pipe_marks.clear();
   P.pipe_marks.reserve((size_t)(n_windows / std::max<int64_t>(1, std::min<int64_t>(P.host_first_chunk, P.chunk_windows)) + 8));
-  auto fetch_back = [&](int64_t w0b, int64_t nwb, int par_b) {   // features of a finished chunk -> host
-    // (on its own stream: behind the copy stream's input copies these waits held the copy of chunk k + 1 until chunk
-    // k - 1 was complete -- on a young stream, whose threshold walks are the long pole, 6 ms after its samples were ready)
-    if (!tiny) chunk_wait_done(P, so, par_b, false);
-    be_d2h_async(out + (size_t)w0b * F, d_out + (size_t)w0b * F, (size_t)nwb * F * sizeof(float), so);
-    if (nan_mask) be_d2h_async(nan_mask + (size_t)w0b * Cin, d_mask + (size_t)w0b * Cin, (size_t)nwb * Cin, so);
-    if (P.pipe_out_done && P.pipe_marks.size() < P.pipe_marks.capacity()) {   // tell the caller's threads: rows [0, w0b + nwb) are there
-      P.pipe_marks.push_back(Plan::Progress{P.pipe_out_done, w0b + nwb});
-      be_host_fn(so, [](void* a) { auto* m = (Plan::Progress*)a; __atomic_store_n(m->dst, m->value, __ATOMIC_RELEASE); },
-                 &P.pipe_marks.back());
-    }
-  };
   // an error in mid-batch leaves work in flight: host callbacks holding pointers into P.pipe_marks, copies into the caller's
   // out / mask.  Nothing returns to the caller -- who may free those buffers, or start the next batch, whose
-  // pipe_marks.clear() + reserve() may move the marks -- before both streams have drained.
+  // pipe_marks.clear() + reserve() may move the marks -- before the batch's streams have drained.
   auto bail = [&](int r) {
-    be_sync_quiet(sc);
-    be_sync_quiet(so);
-    be_sync_quiet(s);
+    P.sched.drain(b);
     return r;
   };
   struct ScaleGuard { ~ScaleGuard() { g_ensure_scale = 1.0; } } scale_guard;
   for (int64_t w0 = 0; w0 < n_windows; ++k) {
-    const int64_t chunk = chunk_at(w0);
-    const int nw = (int)std::min<int64_t>(chunk, n_windows - w0);
+    const int nw = (int)std::min<int64_t>(sizes.at(w0), n_windows - w0);
     // (buffers that grow during the short first chunk: sized for the longest chunk behind it -- see ensure())
-    g_ensure_scale = (host && w0 == 0 && n_windows > nw) ? (double)std::min<int64_t>(host_big, n_windows - nw) / (double)nw : 1.0;
+    g_ensure_scale = (host && w0 == 0 && n_windows > nw) ? (double)std::min<int64_t>(sizes.host_big, n_windows - nw) / (double)nw : 1.0;
     long long lo = starts[w0], hi = starts[w0] + P.w_in;
     for (int64_t i = w0; i < w0 + nw; ++i) {
       lo = std::min<long long>(lo, starts[i]);
@@ -297,50 +333,14 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
     }
     const float* d_xk = x;
     long long ldxk = ldx;
-    if (host) {
-      Buf& xb = P.x_in2[k & 1];   // (the chunk that used this buffer two steps ago has been fetched back: done)
-      const long long n_range = hi - lo;
-      if ((rc = ensure(xb, (size_t)Cin * n_range * sizeof(float)))) return bail(rc);
-      if (k >= 2) {   // the chunk two back read this buffer: its samples consumed (its pre-processing done), or -- a plan whose
-        // features read the samples themselves -- the chunk complete (same parity; events not yet re-recorded)
-        if (P.in_free[k & 1]) be_stream_wait(sc, P.ev_in_free[k & 1]);
-        else chunk_wait_done(P, sc, (int)(P.chunk_seq & 1), false);
-      }
-      if (P.pipe_in_ready) {
-        // the caller converts the recording slice by slice on its own threads: the chunk's samples are copied piece by
-        // piece as they are published (a caller that publishes finer than a chunk gets its copies under its conversion)
-        long long pos = lo, spins = 0;
-        while (pos < hi) {
-          const long long want = std::min<long long>(hi, pos + 4096);
-          long long ready = __atomic_load_n(P.pipe_in_ready, __ATOMIC_ACQUIRE);
-          if (ready < want) {
-            if (++spins > 2000000) return bail(nmx_fail(NMX_E_INVALID, "nmx_plan_set_pipeline: the input never became ready"));
-            std::this_thread::sleep_for(std::chrono::microseconds(5));
-            continue;
-          }
-          const long long upto = std::min<long long>(hi, ready);
-          be_h2d_2d_async((float*)xb.p + (pos - lo), (size_t)n_range * sizeof(float), x + pos, (size_t)ldx * sizeof(float),
-                          (size_t)(upto - pos) * sizeof(float), (size_t)Cin, sc);
-          pos = upto;
-        }
-      } else {
-        be_h2d_2d_async(xb.p, (size_t)n_range * sizeof(float), x + lo, (size_t)ldx * sizeof(float),
-                        (size_t)n_range * sizeof(float), (size_t)Cin, sc);
-      }
-      if (!tiny) {
-        be_event_record(P.ev_h2d, sc);
-        be_stream_wait(s, P.ev_h2d);
-      }
-      d_xk = (const float*)xb.p - lo;
-      ldxk = n_range;
-    }
-    float* d_outk = d_out + (size_t)w0 * F;
-    be_memset_async(d_outk, 0xFF, (size_t)nw * F * sizeof(float), s);  // unwritten -> NaN
-    if (d_mask) {
+    if (host && (rc = stage_host_chunk(P, b, k, x, ldx, lo, hi, &d_xk, &ldxk))) return bail(rc);
+    float* d_outk = o.d_out + (size_t)w0 * o.F;
+    be_memset_async(d_outk, 0xFF, (size_t)nw * o.F * sizeof(float), s);  // unwritten -> NaN
+    if (o.d_mask) {
       NmxNanMaskArgs M{};
-      M.x = d_xk; M.ldx = ldxk; M.starts = (const long long*)P.starts.p + w0; M.mask = d_mask + (size_t)w0 * Cin;
-      M.C_in = Cin; M.W = P.w_in;
-      be_launch_nanmask(M, nw * Cin, s);
+      M.x = d_xk; M.ldx = ldxk; M.starts = (const long long*)P.starts.p + w0; M.mask = o.d_mask + (size_t)w0 * o.Cin;
+      M.C_in = o.Cin; M.W = P.w_in;
+      be_launch_nanmask(M, nw * o.Cin, s);
     }
     float* d_prek = nullptr;
     const size_t pre_n = (size_t)nw * d.n_channels * d.window;
@@ -352,31 +352,30 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
         d_prek = pre + (size_t)w0 * d.n_channels * d.window;
       }
     }
-    P.in_free_slot = (host && !tiny) ? (k & 1) : -1;
-    rc = run_chunk(P, d_xk, ldxk, lo, hi, (const long long*)P.starts.p + w0, nw, d_outk, s, w0 == 0, d_prek, starts + w0);
-    P.in_free_slot = -1;
+    bool freed = false;
+    rc = run_chunk(P, b, d_xk, ldxk, lo, hi, (const long long*)P.starts.p + w0, nw, d_outk, w0 == 0, d_prek, starts + w0,
+                   host ? P.sched.input_consumed_event(b, k) : nullptr, &freed);
     if (rc) return bail(rc);
-    if (host) P.in_free[k & 1] = !tiny && P.raw_consumed;
+    if (host) P.sched.input_consumed(k, freed);
     if (pre && host)   // same stream as the kernels: the next chunk's gather waits for this copy
       be_d2h_async(pre + (size_t)w0 * d.n_channels * d.window, d_prek, pre_n * sizeof(float), s);
-    const int par_k = (int)(P.chunk_seq & 1);
-    if ((rc = chunk_finalize(P, d_outk, F, nw, tiny ? s : nullptr, w0 == 0))) return bail(rc);   // (normaliser: hop order = chunk order)
+    const int par_k = P.sched.parity();
+    if ((rc = chunk_finalize(P, b, d_outk, o.F, nw, w0 == 0))) return bail(rc);   // (normaliser: hop order = chunk order)
     last_par = par_k;
     if (host) {
-      if (prev_w0 >= 0) fetch_back(prev_w0, prev_nw, par_k ^ 1);
+      if (prev_w0 >= 0) fetch_back(P, b, o, prev_w0, prev_nw, par_k ^ 1);
       prev_w0 = w0;
       prev_nw = nw;
     }
     w0 += nw;
   }
   // the caller's stream completes when the last chunk's rows do
-  if (last_par >= 0 && !tiny) chunk_wait_done(P, s, last_par, true);
-  be_timer_stop(P.timers[0], s);
+  if (last_par >= 0 && !tiny) P.sched.wait_done(b, s, last_par, plan_finalizes(P), true);
+  be_timer_stop(P.timers[ST_BATCH], s);
   if (host) {
-    fetch_back(prev_w0, prev_nw, last_par);
-    if ((rc = be_sync_watch(so, P.kernels, 9))) return rc;   // (a watchdog verdict: nothing more is waited for)
-    if ((rc = be_sync_watch(sc, P.kernels, 9))) return rc;
-    if ((rc = be_sync_watch(s, P.kernels, 9))) return rc;
+    fetch_back(P, b, o, prev_w0, prev_nw, last_par);
+    for (be_stream_t st : {P.sched.out_stream(b), P.sched.in_stream(b), s})   // (a watchdog verdict: nothing more is waited for)
+      if ((rc = be_sync_watch(st, P.kernels, ST_COUNT))) return rc;
     if (P.pipe_out_done) __atomic_store_n(P.pipe_out_done, (int64_t)n_windows, __ATOMIC_RELEASE);
   }
   return be_check_launch();
@@ -435,7 +434,7 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   const int W = P.w_in;   // incoming samples per window
   int rc = be_set_device(P.device);
   if (rc) return rc;
-  be_stream_t s = P.stream;
+  be_stream_t s = P.sched.main;
   std::vector<float> xf((size_t)Cin * W), yf((size_t)C * Wo);
   for (int c = 0; c < Cin; ++c) {
     const double dh = P.dc_host_set ? P.dc_host[c] : 0.0;
@@ -450,11 +449,11 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   NMX_REQUIRE(P.front.d_R || Cin == C, "n_channels_in != n_channels without ref_matrix");
   WinView v{(const float*)P.x_in.p, W, 0, nullptr, 1};
   be_stage_reset();
-  be_stage(1);
+  be_stage(ST_PREP);
   if ((rc = launch_front(P, v.x, W, 0, W, false, s, v))) return rc;
   if ((rc = run_prep_stages(P, v, 1, s))) return rc;
-  be_stage(0);
-  for (int i = 0; i < 8; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
+  be_stage(ST_BATCH);
+  for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), v.x, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
@@ -475,7 +474,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   const int C = d.n_channels, W = d.window, NF = d.n_filters;
   int rc = be_set_device(P.device);
   if (rc) return rc;
-  be_stream_t s = P.stream;
+  be_stream_t s = P.sched.main;
   std::vector<float> xf((size_t)C * W), yf((size_t)C * NF * W);
   for (int c = 0; c < C; ++c)
     for (int i = 0; i < W; ++i) xf[(size_t)c * W + i] = (float)x[(size_t)c * ldx + i];
@@ -492,8 +491,8 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   be_stage_reset();
   be_stage(P.bank.launches[0].stage);
   launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
-  be_stage(0);
-  for (int i = 0; i < 8; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
+  be_stage(ST_BATCH);
+  for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), P.sharp.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];
@@ -502,7 +501,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
 
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms) {
   Plan* P = (Plan*)plan;
-  if (!P || !ms || which < 0 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !ms || which < ST_BATCH || which >= ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
   be_set_device(P->device);
   *ms = be_timer_elapsed(P->timers[which]);
   return 0;
@@ -628,9 +627,9 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
-  if (!P || !buf || n < 1 || which < 1 || which > 8) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !buf || n < 1 || which < ST_PREP || which >= ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
   std::string k = P->kernels[which];
-  if (which == 4 && P->bursts.sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
+  if (which == ST_BURSTS && P->bursts.sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
     k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->bursts.env_tail_rows) + "/" + std::to_string(P->bursts.env_rows);
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
   memcpy(buf, k.data(), m);

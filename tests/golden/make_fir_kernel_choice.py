@@ -5,6 +5,7 @@ the batches launched in the module's stages and the SHA-256 of the tables they r
     tests/burst_kernel_choice_cases.py              -> tests/golden/burst_kernel_choice.json  (bursts chain, sharp waves)
     tests/state_blob_cases.py                       -> tests/golden/state_blob.json           (state blobs; --emu: state_blob_emu.json)
     tests/prep_stage_cases.py                       -> tests/golden/prep_stage.json           (a chunk's launch sequence; --emu: prep_stage_emu.json)
+    tests/chunk_schedule_cases.py                   -> tests/golden/chunk_schedule.json       (streams and events of a chunk and a batch; --emu: chunk_schedule_emu.json)
 
 Runs on the GPU, at the commit whose kernel choice is to be kept (the parent of a change to how those kernels are chosen);
 tests/test_fir_kernel_choice_gpu.py / tests/test_burst_kernel_choice_gpu.py compare a later build against the file.  Every
