@@ -555,7 +555,8 @@ def case_reference_property_tests(lib):
 
 
 def case_feature_normalizer_batches(lib):
-    """nmx_norm_* (batch scan) == the reference's hop-by-hop Normalizer for "zscore", "mean", "median",
+    """nmx_norm_* (the column walk: with N = 50 the scan kernels, which need N - 1 >= 64, are not reached -- they and the
+    walk's edges are probed in tests/norm_probe_cases.py) == the reference's hop-by-hop Normalizer for "zscore", "mean", "median",
     "zscore-median" and the scikit-learn based "robust", "minmax", "quantile" (fitted on nan_to_num(history)):
     history carried across batches and through export/import, N - 1 trimming, NaN-aware statistics,
     constant columns (std 0 -> 1), the untouched first row, clip, and the "psd" column mask.
