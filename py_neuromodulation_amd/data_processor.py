@@ -21,19 +21,18 @@ registration order and go through the same normaliser / NaN policy.
 
 from __future__ import annotations
 
+import weakref
 from time import time
 
 import numpy as np
 
 from . import channels as chmod
-from . import fir_design
+from . import file_writer as fw
 from .engine import HotPathEngine, parallel_cast, table_empty
+from .prep import LocalInput, PrepPlan
 from .processing import DeviceFeatureNormalizer, FeatureNormalizer
 from .projection import DeviceProjection, GridProjection
 from .settings import NMSettings
-
-PREPROCESSOR_ORDER = ["preprocessing_filter", "notch_filter", "raw_resampling", "re_referencing",
-                      "raw_normalization"]
 
 
 class _LazyNanCols:
@@ -77,7 +76,6 @@ class UserColumns:
         self.user_keys: list[str] | None = None
         self.cols: np.ndarray | None = None
         self.norm = None
-        self.n_builtin = len(keys)
         self._instantiate()
 
     def _instantiate(self) -> None:
@@ -134,102 +132,224 @@ class UserColumns:
         return table
 
 
-class DataProcessor:
+class PostChain:
+    """Everything behind the engine's rows, ONE object per processor family (the twins of other window lengths share it):
+    the feature normaliser, the grid projection (host plan ``proj``, device object ``proj_dev`` for the engine's key
+    layout), the ``user`` columns, the key list and the NaN-column scanner.  ``where`` records where each step runs:
+
+        step         where      when
+        normalizer   "engine"   feature_normalization on (inside the plan's launch sequence: no second round trip)
+                     "host"     after `detach`: a ragged run normalises the merged table, sequentially over ALL hops
+        projection   "engine"   behind an in-engine normaliser, or with no normaliser (it reads normalised rows)
+                     "host"     after `detach`, on the engine's rows behind the host normaliser
+                     "merged"   user features exist: their keys come first, the grid follows on the merged table
+        (None: the step does not exist.  A channel shard has no user features: its coordinator's chain holds them.)"""
+
+    def __init__(self, settings, ch_names, proj=None, plugins: bool = False, device: int = 0, lib=None) -> None:
+        self.settings, self.ch_names, self.proj, self.plugins = settings, ch_names, proj, plugins
+        self.device, self.lib = device, lib
+        self.keys = self.user = self.normalizer = self.proj_dev = self._user_grid = self._nan_cols = None
+        self.n_feat, self._engines = 0, weakref.WeakSet()   # (`start` fills the first; the engines `attach` was handed)
+        self.where = {"normalizer": None, "projection": "merged" if proj is not None and plugins else None}
+
+    def extra_cols(self, keys) -> int:
+        """The grid columns behind the built-in ones in the engine's rows (known when the plan is built)."""
+        return self.proj.layout(keys).n_grid if self.proj is not None and not self.plugins else 0
+
+    def start(self, feat_keys, names, sfreq, dry_run: bool = False, normalize: bool = True) -> None:
+        """The key list and the objects of the chain, from the engine's keys."""
+        st = self.settings
+        self.n_feat, self.keys = len(feat_keys), list(feat_keys)
+        # with user features their keys come first, and the grid follows on the merged table (`finish_table`)
+        layout = self.proj.layout(feat_keys) if self.proj is not None and not self.plugins else None
+        if layout is not None:
+            self.keys += layout.grid_keys
+        # user features: instantiated after the built-ins with the same arguments (feature_processor.py:45-53)
+        if self.plugins:
+            self.user = UserColumns(st, names, sfreq, self.keys, device=self.device, lib=self.lib)
+        if normalize and st.postprocessing.feature_normalization and not dry_run:
+            FeatureNormalizer(st)   # an unknown method name raises NotImplementedError here, naming it
+            # every method of normalization.py:57-70: one HIP scan per batch of hops; the column mask carries the
+            # "psd" exclusion (stream/data_processor.py:263-290); the feature columns, not the grid columns behind them
+            mask = None
+            if not st.feature_normalization_settings.normalize_psd:
+                mask = np.array(["psd" not in k for k in feat_keys], dtype=np.uint8)
+            self.normalizer = DeviceFeatureNormalizer(st, len(feat_keys), colmask=mask, device=self.device, lib=self.lib)
+            self.where["normalizer"] = "engine"
+        if layout is not None and layout.n_grid and not dry_run:
+            self.proj_dev = DeviceProjection(layout, self.device, self.lib)   # (stateless: one for every twin)
+            self.where["projection"] = "engine"
+        self._nan_cols = _LazyNanCols(self.keys, self.ch_names)
+
+    def attach(self, engine) -> None:
+        """The steps placed in the engine into ``engine``'s launch sequence."""
+        self.lib = engine.lib
+        self._engines.add(engine)
+        if self.where["normalizer"] == "engine":
+            engine.attach_normalizer(self.normalizer)
+        if self.where["projection"] == "engine":
+            engine.attach_projection(self.proj_dev)
+
+    def detach(self) -> None:
+        """Out of EVERY engine of the family (they share ``where``): both steps run in `finish` from now on (a ragged run)."""
+        for engine in self._engines:
+            if engine._norm is not None:
+                engine.attach_normalizer(None)
+            if engine._proj is not None:
+                engine.attach_projection(None)
+        self.where.update({k: "host" for k, v in self.where.items() if v == "engine"})
+
+    def reset(self) -> None:
+        if self.normalizer is not None:
+            self.normalizer.reset()
+        if self.user is not None:
+            self.user.reset()
+
+    def table(self, out: np.ndarray) -> np.ndarray:
+        """Engine rows ``float32[n, row_width]`` in hop order -> the float64 table: the normaliser and the grid projection
+        (unless they ran inside the engine), the cast."""
+        F = self.n_feat
+        if self.where["normalizer"] == "host":
+            if out.shape[1] == F:
+                out = self.normalizer.process_batch(out)
+            else:   # (the grid columns behind the features)
+                out = np.array(out, dtype=np.float32, order="C")
+                out[:, :F] = self.normalizer.process_batch(out[:, :F])
+        if self.where["projection"] == "host" and out.shape[1] > F:
+            out = np.require(out, np.float32, "C")
+            self.proj_dev.process(out)
+        if len(out) == 1:   # (one hop, `process`: the pooled table and the threaded cast cost more than they save)
+            return out.astype(np.float64)
+        table = table_empty(out.shape)
+        parallel_cast(table, out, None, self.lib)
+        return table
+
+    def finish_table(self, table: np.ndarray, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
+        """The user columns and their projection into the float64 ``table``, then the NaN policy (last: the plugin and grid
+        keys follow it too)."""
+        if user is not None:
+            table = self.user.merge(table, user)
+            if self.proj is not None:
+                # the grid behind the user columns (dict.update after the plugin keys): laid out at the first hop, when the
+                # plugin keys are known (Projection.init_projection_run), its keys appended to the list the NaN policy scans
+                if self._user_grid is None:
+                    lay = self.proj.layout(self.keys)
+                    self._user_grid = (lay, DeviceProjection(lay, self.device, self.lib) if lay.n_grid else None)
+                    self.keys.extend(lay.grid_keys)
+                if self._user_grid[1] is not None:
+                    table = self._user_grid[1].process_table(table)
+        return self._nan_cols.apply(table, mask)
+
+    def finish(self, out: np.ndarray, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
+        return self.finish_table(self.table(out), mask, user)
+
+
+class LengthTable:
+    """One processor per window length (a sampling rate that is not a whole number of samples per segment: the reference's
+    generator cuts two lengths, stream/generator.py:41-53, and its DataProcessor takes whatever arrives), who ran last,
+    and the hand-over: what carries over from hop to hop (burst history, Kalman filters, raw-normaliser history; the
+    layout depends on sfreq and the settings, not on the length: nmx_state_export / _import) goes from whoever ran last
+    into the next where the length changes.  Two drivers: ``DataProcessor.process`` hop by hop over twins that share one
+    PostChain, and `run_ragged` for ``Stream.run`` / ``ShardedStream``.  ``make(n_samples)`` builds a new length's."""
+
+    def __init__(self, make, first=None) -> None:
+        self.make, self.by_len, self.last = make, {}, first
+        if first is not None:
+            self.by_len[first.engine.W_in] = first
+
+    def of(self, n_samples: int):
+        if n_samples not in self.by_len:
+            self.by_len[n_samples] = self.make(n_samples)
+        return self.by_len[n_samples]
+
+    @staticmethod
+    def plans(p) -> list:
+        """The processors that hold a plan: ``p`` itself, or the parts of a MultiDeviceProcessor (one state blob each)."""
+        return getattr(p, "parts", [p])
+
+    def switch(self, n_samples: int):
+        """The processor for windows of ``n_samples``, holding the state of whoever ran last."""
+        p, cur = self.of(n_samples), self.last
+        if cur is not None and cur is not p:
+            for src, dst in zip(self.plans(cur), self.plans(p)):
+                state = src.engine.export_state()
+                if state:
+                    dst.engine.import_state(state)
+            p.cnt_samples = cur.cnt_samples
+        self.last = p
+        return p
+
+    def run_ragged(self, lens: np.ndarray, run) -> list:
+        """The hops in order as consecutive runs of one length, ``run(processor, a, b)`` computing hops [a, b); the
+        post-processing is detached from every engine first (PostChain).  -> the results of ``run`` in hop order."""
+        for w in sorted(set(int(v) for v in lens)):
+            for q in self.plans(self.of(w)):
+                q.chain.detach()
+        cuts = [0] + [i for i in range(1, len(lens)) if lens[i] != lens[i - 1]] + [len(lens)]
+        return [run(self.switch(int(lens[a])), a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def no_sharded_projection(settings) -> None:
+    """A grid point mixes the features of channels of every shard: the projection needs them all in one plan."""
+    pp = settings.postprocessing
+    if pp.project_cortex or pp.project_subcortex:
+        raise NotImplementedError("grid projection (project_cortex / project_subcortex) needs every channel in one plan: "
+                                  "it is not supported with channels sharded over several devices (use one device)")
+
+
+class UserViews:
+    """``user_features`` / ``user_keys`` (features/feature_processor.py:52-53,80-82) of a processor whose ``chain`` holds them."""
+
+    @property
+    def user_features(self) -> dict:
+        return self.chain.user.features if self.chain.user is not None else {}
+
+    @property
+    def user_keys(self):
+        return self.chain.user.user_keys if self.chain.user is not None else None
+
+
+class DataProcessor(UserViews):
     def __init__(self, sfreq: float, settings, channels, coord_names=None, coord_list=None,
                  line_noise: float | None = None, path_grids=None, verbose: bool = True,
                  device: int = 0, window: int | None = None, lib=None,
                  channel_subset=None, dry_run: bool = False,
                  resample_features_at_new_rate: bool = False, local_inputs: bool = False,
-                 staging_slot: int = 0, _share: "DataProcessor | None" = None) -> None:
-        """``_share``: the processor this one is the twin of for another window length (`_for_length`): the twin takes
-        its feature normaliser, user features, grid projection and table of twins instead of building its own.
+                 staging_slot: int = 0, _family: tuple | None = None) -> None:
+        """``_family``: (PrepPlan, PostChain, LengthTable) of the processor this one is the twin of for another window
+        length (`_twin`): the twin takes them instead of building its own.
 
         ``coord_names`` / ``coord_list`` / ``path_grids``: the contacts' coordinates and the directory of grid_cortex.tsv /
         grid_subcortex.tsv for the grid projection (postprocessing.project_cortex / project_subcortex,
         processing/projection.py); ``path_grids=None`` takes the grids of an installed reference package."""
-        self.settings = NMSettings.load(settings)
+        from . import user_features as _registered
+
+        self.settings = st = NMSettings.load(settings)
         self.channels = chmod.load_channels(channels)
         # (what a twin for another window length is built from: `process` under the reference's own loop, below)
         self._ctor = dict(sfreq=sfreq, line_noise=line_noise, verbose=verbose, device=device, lib=lib,
                           resample_features_at_new_rate=resample_features_at_new_rate, staging_slot=staging_slot)
         self._twin_ok = channel_subset is None and not dry_run and not local_inputs
-        self._by_len, self._active = (None, None) if _share is None else (_share._by_len, _share._active)
-        self.sfreq_features = self.settings.sampling_rate_features_hz
-        self._sfreq_raw_orig = sfreq
-        self.sfreq_raw = sfreq // 1
-        self.line_noise = line_noise
-        self.verbose = verbose
-        st = self.settings
-        self._proj = None            # grid projection: the host plan (projection.GridProjection) ...
-        self._proj_dev = None        # ... and its device object for the rows of the engine
-        self._proj_in_engine = False
-        if st.postprocessing.project_cortex or st.postprocessing.project_subcortex:
-            if channel_subset is not None:   # a grid point mixes channels of every shard
-                raise NotImplementedError("grid projection (project_cortex / project_subcortex) needs every channel in one "
-                                          "plan: it is not supported with channels sharded over several devices (use one device)")
-            self._proj = _share._proj if _share is not None else GridProjection(st, self.channels, coord_names, coord_list,
-                                                                               path_grids)
-        self.ch_names_used, self.feature_idx, self.target_idx = chmod.channel_info(self.channels)
-        n_all = len(self.channels)
-
-        notch_taps = None
-        R = None
-        resample_to = None
-        pre_taps = None
-        raw_norm = None
-        for name in st.preprocessing:
-            if name not in PREPROCESSOR_ORDER:
-                raise ValueError(f"Invalid preprocessing method '{name}'. Must be one of {PREPROCESSOR_ORDER}")
-        for name in PREPROCESSOR_ORDER:
-            if name not in st.preprocessing:
-                continue
-            if name == "notch_filter":
-                if line_noise is None:
-                    raise ValueError("Either line_noise or freqs must be defined if notch_filter is activated.")
-                notch_taps = fir_design.notch_bank(self.sfreq_raw, line_noise)
-            elif name == "preprocessing_filter":
-                pre_taps = fir_design.preprocessing_filter_bank(st.preprocessing_filter, self.sfreq_raw)
-            elif name == "raw_resampling":
-                new_rate = float(st.raw_resampling_settings.resample_freq_hz)
-                if float(new_rate / self.sfreq_raw) != 1.0:
-                    # The reference resamples every window but keeps building notch AND features with the
-                    # RAW rate (stream/data_processor.py:55,68,80): every frequency axis of the features is
-                    # off by the ratio.  Reproduced as is (default); resample_features_at_new_rate=True
-                    # selects the consistent pipeline (features designed for the rate they see).
-                    resample_to = new_rate
-                    if not resample_features_at_new_rate:
-                        from . import logger
-
-                        logger.info("raw_resampling %g -> %g Hz: features are designed with the raw rate like "
-                                    "the reference (pass resample_features_at_new_rate=True for the new rate)",
-                                    self.sfreq_raw, new_rate)
-            elif name == "re_referencing":
-                R = chmod.reref_matrix(self.channels)
-            elif name == "raw_normalization":
-                rs = st.raw_normalization_settings
-                rate = resample_to if (resample_to is not None and resample_features_at_new_rate) else self.sfreq_raw
-                # normalization.py:52-58: add_samples = int(sfreq / feat_hz), N = int(time_s * sfreq)
-                raw_norm = (rs.normalization_method, rs.clip, int(rs.normalization_time_s * rate),
-                            int(rate / st.sampling_rate_features_hz))
-            else:
-                raise NotImplementedError(f"{name} is outside the accelerated hot path (SURVEY 8f)")
-        C = len(self.feature_idx)
-        if R is not None and R.shape[0] != C:
-            raise ValueError(f"re-reference matrix is {R.shape} but {C} channels are picked for features")
-        # fold data[feature_idx] (and R) into one [C, C_all] matrix applied on the device
-        need_matrix = R is not None or self.feature_idx != list(range(n_all))
-        full = None
-        if need_matrix:
-            S = np.zeros((C, n_all))
-            S[np.arange(C), self.feature_idx] = 1.0
-            full = (R @ S) if R is not None else S
-        self.ref_matrix = R
+        self.sfreq_features, self._sfreq_raw_orig = st.sampling_rate_features_hz, sfreq
+        self.line_noise, self.verbose = line_noise, verbose
+        projecting = st.postprocessing.project_cortex or st.postprocessing.project_subcortex
+        if channel_subset is not None:
+            no_sharded_projection(st)
+        if _family is None:
+            proj = GridProjection(st, self.channels, coord_names, coord_list, path_grids) if projecting else None
+            prep = PrepPlan(st, self.channels, sfreq, line_noise, resample_features_at_new_rate)
+            # (a channel shard leaves the user features to its coordinator, sharding.MultiDeviceProcessor: they see ALL channels)
+            plugins = bool(_registered and not dry_run and channel_subset is None)
+            _family = (prep, PostChain(st, prep.ch_names_used, proj, plugins, device, lib), None)
+        self.prep, self.chain, self._lengths = _family
+        prep, chain = _family[:2]
+        self.ch_names_used, self.feature_idx, self.target_idx = prep.ch_names_used, prep.feature_idx, prep.target_idx
+        self.ref_matrix, self.sfreq_raw = prep.ref_matrix, prep.sfreq_design
         # channel sharding over GPUs: this processor computes the features of a subset of the
         # picked channels but its re-reference rows still read ALL input rows (SURVEY 8e)
-        self.all_ch_names_used = list(self.ch_names_used)
-        names = self.ch_names_used
-        self.local_rows = None      # local_inputs: the input rows this processor expects, then hi / lo rows of the group sums
-        self.local_groups = []      # local_inputs: member rows (global) of every group sum it expects
+        names, kw = self.ch_names_used, prep.engine_kwargs(window)
+        self.local = None           # local_inputs: the LocalInput layout of this shard; its `rows` and `groups`:
+        self.local_rows, self.local_groups = None, []
         if channel_subset is not None:
             subset = list(channel_subset)
             if ("coherence" in st.features.get_enabled() and st.coherence_settings.channels
@@ -237,229 +357,79 @@ class DataProcessor:
                 # a pair may join channels of two shards; the plan of one shard sees its own channels only
                 raise NotImplementedError("coherence needs both channels of every pair in one plan: it is not supported "
                                           "with channels sharded over several devices (use one device)")
-            if full is None:
-                full = np.eye(n_all)
-            full = full[subset]
+            full = (prep.matrix if prep.matrix is not None else np.eye(len(self.channels)))[subset]
             names = [self.ch_names_used[i] for i in subset]
             if local_inputs:
-                # Channel shard WITHOUT replicating the recording: this rank is handed only the input rows its
-                # own output rows tap, plus one row per type group holding sum_{j in group} x_j (partial sums
-                # of the owners, all-reduced by the caller -- sharding.ShardedStream).  Its matrix then has a
-                # handful of non-zeros per row: taps on local rows + the coefficient of the group-sum row.
-                st_ = chmod.reref_structure(full)
-                if st_ is None:
-                    raise NotImplementedError("local_inputs needs re-reference rows made of a few named channels "
-                                              "and / or one group average (processing/rereference.py:52-86)")
-                taps, gi, gb, groups = st_
-                rows = sorted({j for t in taps for j, _ in t})
-                pos = {j: i for i, j in enumerate(rows)}
-                used_groups = sorted({int(k) for k in gi if k >= 0})
-                # a group sum arrives as TWO float32 rows, hi + lo of the float64 sum (channels.split_hi_lo): the
-                # device accumulates coefficient x row in float64, so the re-referenced sample is rounded to float32
-                # once, as in the single-device kernel that forms the sum itself
-                gpos = {k: len(rows) + 2 * i for i, k in enumerate(used_groups)}
-                loc = np.zeros((len(subset), len(rows) + 2 * len(used_groups)))
-                for r, t in enumerate(taps):
-                    for j, c in t:
-                        loc[r, pos[j]] += c
-                    if gi[r] >= 0:
-                        loc[r, gpos[int(gi[r])]] = gb[r]
-                        loc[r, gpos[int(gi[r])] + 1] = gb[r]
-                full = loc if not (loc.shape[0] == loc.shape[1] and np.array_equal(loc, np.eye(len(loc)))) else None
-                self.local_rows = rows
-                self.local_groups = [groups[k] for k in used_groups]
-        from . import user_features as _registered
-
-        has_user = (_share._user is not None) if _share is not None else bool(_registered and not dry_run
-                                                                             and channel_subset is None)
-        # the grid columns follow the built-in ones in the engine's rows (the key list is known when the plan is built);
-        # with user features their keys come first, and the projection runs on the merged table (_project_user)
-        grid = self._proj is not None and not has_user
-        extra = (lambda keys: self._proj.layout(keys).n_grid) if grid else 0
-        if resample_to is None:
-            self.engine = HotPathEngine(st, names, self.sfreq_raw, ref_matrix=full, notch_taps=notch_taps,
-                                        device=device, window=window, lib=lib, dry_run=dry_run,
-                                        pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot, extra_cols=extra)
-        elif resample_features_at_new_rate:   # `window` counts RAW samples (the generator cuts raw data)
-            self.engine = HotPathEngine(st, names, resample_to, ref_matrix=full, notch_taps=notch_taps,
-                                        device=device, lib=lib, dry_run=dry_run,
-                                        resample_from=self.sfreq_raw, raw_window=window, pre_taps=pre_taps,
-                                        raw_norm=raw_norm, staging_slot=staging_slot, extra_cols=extra)
-            self.sfreq_raw = resample_to
-        else:   # the reference: windows resampled, everything designed with the raw rate
-            self.engine = HotPathEngine(st, names, self.sfreq_raw, ref_matrix=full, notch_taps=notch_taps,
-                                        device=device, lib=lib, dry_run=dry_run,
-                                        resample_from=self.sfreq_raw, resample_to=resample_to,
-                                        raw_window=window, pre_taps=pre_taps, raw_norm=raw_norm, staging_slot=staging_slot,
-                                        extra_cols=extra)
-        self.keys = list(self.engine.keys)
-        layout = None
-        if grid:
-            layout = self._proj.layout(self.engine.keys)
-            self.keys += layout.grid_keys
-        # user features: instantiated after the built-ins with the same arguments (feature_processor.py:45-53); a
-        # channel shard leaves them to its coordinator (they see ALL channels: sharding.MultiDeviceProcessor)
-        self._user = None
-        if _share is not None:
-            self._user = _share._user
-            if self._user is not None:   # (one key list: the plugin and grid keys are appended to it at the first hop)
-                self.keys = _share.keys
-        elif _registered and not dry_run and channel_subset is None:
-            self._user = UserColumns(st, names, self.sfreq_raw, self.keys, device=device, lib=lib)
+                self.local = LocalInput(full)
+                full, self.local_rows, self.local_groups = self.local.matrix, self.local.rows, self.local.groups
+            kw["ref_matrix"] = full
+        self.engine = HotPathEngine(st, names, device=device, lib=lib, dry_run=dry_run, staging_slot=staging_slot,
+                                    extra_cols=chain.extra_cols, **kw)
+        if chain.keys is None:
+            chain.start(self.engine.keys, names, self.sfreq_raw, dry_run)
+        if not dry_run:
+            chain.attach(self.engine)
+        # (the chain's own key list: plugin and grid keys are appended at the first hop; `projection`: the host plan or None)
+        self.keys, self.device_normalizer, self.projection = chain.keys, chain.normalizer, chain.proj
         self._user_chunk = 64                          # hops per tapped batch (bounds the [n, C, W] hand-back)
-        self.device_normalizer = None
-        self._norm_in_engine = False
-        if st.postprocessing.feature_normalization and not dry_run:
-            if _share is not None:
-                self.device_normalizer = _share.device_normalizer
-            else:
-                FeatureNormalizer(st)   # an unknown method name raises NotImplementedError here, naming it
-                # every method of normalization.py:57-70: one HIP scan per batch of hops; the column mask carries the
-                # "psd" exclusion (stream/data_processor.py:263-290)
-                mask = None
-                feat = self.engine.keys   # (the feature columns: not the grid columns behind them)
-                if not st.feature_normalization_settings.normalize_psd:
-                    mask = np.array(["psd" not in k for k in feat], dtype=np.uint8)
-                self.device_normalizer = DeviceFeatureNormalizer(st, len(feat), colmask=mask,
-                                                                 device=device, lib=lib)
-            if _share is None or _share._norm_in_engine:
-                # inside the engine's launch sequence: rows come back normalised (no second round trip)
-                self.engine.attach_normalizer(self.device_normalizer)
-                self._norm_in_engine = True
-        if layout is not None and layout.n_grid and not dry_run:
-            # stateless: the twins of other window lengths with the same key list share the device object
-            share = _share._proj_dev if _share is not None else None
-            self._proj_dev = share if share is not None and share.layout is layout else DeviceProjection(layout, device, lib)
-            if self.device_normalizer is None or self._norm_in_engine:   # (it reads normalised rows)
-                self.engine.attach_projection(self._proj_dev)
-                self._proj_in_engine = True
-        self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
+        self._row_template = self.settings_token = None
         self.cnt_samples = 0
-        self.settings_token = None
 
     # -- stream/data_processor.py:313-351: what the reference's Stream calls after its loop ---------------------------------
     def save_sidecar(self, out_dir, prefix: str = "", additional_args: dict | None = None) -> None:
-        from . import file_writer as fw
-
         sidecar = {"original_fs": self._sfreq_raw_orig, "final_fs": self.sfreq_raw, "sfreq": self.sfreq_features}
-        sidecar.update(self.projection_sidecar())
-        if additional_args is not None:
-            sidecar = sidecar | additional_args
-        fw.save_sidecar(sidecar, out_dir, prefix)
+        fw.save_sidecar(sidecar | self.projection_sidecar() | (additional_args or {}), out_dir, prefix)
 
     def projection_sidecar(self) -> dict:
         """What the grid projection adds to the sidecar (stream/data_processor.py:326-333): coords, grid_cortex,
         proj_matrix_cortex, grid_subcortex, proj_matrix_subcortex; {} without a projection."""
-        return self._proj.sidecar() if self._proj is not None else {}
-
-    @property
-    def projection(self):
-        """The grid projection's host plan (projection.GridProjection: matrices, active points, channels) or None."""
-        return self._proj
+        return self.chain.proj.sidecar() if self.chain.proj is not None else {}
 
     def save_settings(self, out_dir, prefix: str = "") -> None:
         self.settings.save(out_dir, prefix)
 
     def save_channels(self, out_dir, prefix: str) -> None:
-        from . import file_writer as fw
-
         fw.save_channels(self.channels, out_dir, prefix)
 
     def save_features(self, feature_arr, out_dir="", prefix: str = "") -> None:
-        from . import file_writer as fw
-
         fw.save_features(feature_arr, out_dir, prefix)
 
     def reset(self) -> None:
         """Forget everything carried across hops (burst history, Kalman filters, raw and feature normaliser
         histories): the state of a freshly constructed processor."""
         self.engine.reset_state()
-        if self._by_len is not None:   # (the twins of other window lengths take their state from whoever ran last)
-            for p in self._by_len.values():
-                if p is not self:
-                    p.engine.reset_state()
-            self._active[0] = self
-        if self.device_normalizer is not None:
-            self.device_normalizer.reset()
-        if self._user is not None:
-            self._user.reset()
+        if self._lengths is not None:   # (the twins of other window lengths take their state from whoever ran last)
+            for p in self._lengths.by_len.values():
+                p.engine.reset_state()
+            self._lengths.last = self
+        self.chain.reset()
         self.cnt_samples = 0
 
-    # ------------------------------------------------------------------------------------
-    def _finish(self, out: np.ndarray, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
-        """Engine rows ``float32[n, row_width]`` in hop order -> the float64 table: the normaliser (unless it ran inside the
-        engine), the grid projection (likewise), the cast, the user columns and their projection, the NaN policy (last:
-        the plugin and grid keys follow it too)."""
-        F = self.engine.n_outputs
-        if self.device_normalizer is not None and not self._norm_in_engine:
-            if out.shape[1] == F:
-                out = self.device_normalizer.process_batch(out)
-            else:   # (the grid columns behind the features)
-                out = np.array(out, dtype=np.float32, order="C")
-                out[:, :F] = self.device_normalizer.process_batch(out[:, :F])
-        if self._proj_dev is not None and not self._proj_in_engine and out.shape[1] > F:
-            out = np.require(out, np.float32, "C")
-            self._proj_dev.process(out)
-        if len(out) == 1:   # (one hop, `process`: the pooled table and the threaded cast cost more than they save)
-            table = out.astype(np.float64)
-        else:
-            table = table_empty(out.shape)
-            parallel_cast(table, out, None, self.engine.lib)
-        if user is not None:
-            table = self._user.merge(table, user)
-            if self._proj is not None:
-                table = self._project_user(table)
-        return self._nan_cols.apply(table, mask)
-
-    def _project_user(self, table: np.ndarray) -> np.ndarray:
-        """The grid projection behind the user columns (dict.update after the plugin keys): laid out at the first hop, when
-        the plugin keys are known (Projection.init_projection_run); the grid keys are appended to the key list the plugins
-        extended -- the one the NaN policy scans."""
-        u = self._user
-        g = getattr(u, "grid", None)
-        if g is None:
-            lay = self._proj.layout(u.keys)
-            dev = DeviceProjection(lay, self._ctor["device"], self.engine.lib) if lay.n_grid else None
-            u.keys.extend(lay.grid_keys)
-            g = u.grid = (lay, dev)
-        return g[1].process_table(table) if g[1] is not None else table
-
     # -- user-registered features (features/feature_processor.py:52-53,80-82) ----------------------
-    @property
-    def user_features(self) -> dict:
-        return self._user.features if self._user is not None else {}
-
-    @property
-    def user_keys(self):
-        return self._user.user_keys if self._user is not None else None
-
-    def _host_windows(self, data: np.ndarray, starts) -> "list[np.ndarray]":
-        W = self.engine.W_in
-        return [np.nan_to_num(np.asarray(data[:, int(s):int(s) + W], dtype=np.float64)) for s in starts]
-
     def process_batch_tapped(self, data: np.ndarray, starts: np.ndarray):
         """One batch through the engine AND the windows its features read: (float32 rows -- normalised when the
         normaliser is attached --, NaN mask, float64 [n, C, W])."""
         eng = self.engine
         if eng.preprocessing_is_identity:
             o, m = eng.process_batch(data, starts, want_nan_mask=True)
-            return o, m, np.stack(self._host_windows(data, starts))
+            return o, m, np.stack([np.nan_to_num(np.asarray(data[:, int(s):int(s) + eng.W_in], dtype=np.float64)) for s in starts])
         o, m, pre = eng.process_batch(data, starts, want_nan_mask=True, tap=True)
         return o, m, pre.astype(np.float64)
 
     def _process_batch_user(self, data: np.ndarray, starts: np.ndarray):
         """Engine rows, NaN mask and the user-feature rows of the same hops; the hops go through the engine in chunks
         of ``_user_chunk`` so that the tapped windows stay small."""
+        user = self.chain.user
         starts = np.asarray(starts, dtype=np.int64)
         if len(starts) == 0:   # (an empty batch is an empty table, as without plugins)
             return (np.empty((0, self.engine.n_outputs), np.float32), np.zeros((0, self.engine.C_in), bool),
-                    np.empty((0, len(self._user.user_keys or [])), np.float64))
+                    np.empty((0, len(user.user_keys or [])), np.float64))
         outs, masks, users = [], [], []
         for i in range(0, len(starts), self._user_chunk):
             o, m, wins = self.process_batch_tapped(data, starts[i:i + self._user_chunk])
             outs.append(o)
             masks.append(m)
-            users.append(self._user.rows(wins))
+            users.append(user.rows(wins))
         return np.concatenate(outs), np.concatenate(masks), np.concatenate(users)
 
     def _row_dict(self, row: np.ndarray) -> dict:
@@ -468,7 +438,7 @@ class DataProcessor:
         ``dict(zip(keys, values))`` -- which grows its table eleven times on the way -- costs 0.72 (the engine's part of a
         256-channel call is 0.36 ms)."""
         keys = self.keys
-        tmpl = getattr(self, "_row_template", None)
+        tmpl = self._row_template
         if tmpl is None or tmpl[0] is not keys or len(tmpl[1]) != len(keys):
             tmpl = self._row_template = (keys, dict.fromkeys(keys, 0.0), tuple(keys))
         if len(tmpl[1]) != len(tmpl[2]):   # (duplicate keys: nothing a template can hold)
@@ -477,42 +447,29 @@ class DataProcessor:
         d.update(zip(tmpl[2], row.tolist()))
         return d
 
-    def _for_length(self, n_samples: int) -> "DataProcessor":
-        """The processor for windows of ``n_samples`` (a sampling rate that is not a whole number of samples per segment:
-        the reference's generator cuts two lengths, stream/generator.py:41-53, and its DataProcessor takes whatever
-        arrives).  One plan per length; what carries over from hop to hop (burst history, Kalman filters, raw-normaliser
-        history) is handed from plan to plan when the length changes, and ONE feature normaliser and one set of user
-        features serve them all -- the hop-by-hop form of what `Stream.run` does for its ragged runs."""
-        if self._by_len is None:
-            self._by_len, self._active = {self.engine.W_in: self}, [self]
-        p = self._by_len.get(n_samples)
-        if p is None:
-            if not self._twin_ok:
-                raise ValueError(f"expected windows of {self.engine.W_in} samples, got {n_samples}")
-            p = self._by_len[n_samples] = DataProcessor(settings=self.settings, channels=self.channels, window=n_samples,
-                                                        _share=self, **self._ctor)
-        cur = self._active[0]
-        if cur is not p:
-            state = cur.engine.export_state()
-            if state:
-                p.engine.import_state(state)
-            p.cnt_samples = cur.cnt_samples
-            self._active[0] = p
-        return p
+    def _twin(self, n_samples: int) -> "DataProcessor":
+        """The twin for windows of ``n_samples``: one plan per length, ONE PostChain (feature normaliser, user features)
+        and one table of lengths serve them all."""
+        if not self._twin_ok:
+            raise ValueError(f"expected windows of {self.engine.W_in} samples, got {n_samples}")
+        return DataProcessor(settings=self.settings, channels=self.channels, window=n_samples,
+                             _family=(self.prep, self.chain, self._lengths), **self._ctor)
 
     def process(self, data: np.ndarray) -> dict:
         n_samples = np.shape(data)[-1]
-        if n_samples != self.engine.W_in or (self._active is not None and self._active[0] is not self):
-            p = self._for_length(n_samples)
+        if n_samples != self.engine.W_in or (self._lengths is not None and self._lengths.last is not self):
+            if self._lengths is None:
+                self._lengths = LengthTable(self._twin, self)
+            p = self._lengths.switch(n_samples)
             if p is not self:
                 return p.process(data)
         start_time = time()
-        if self._user is not None:
+        if self.chain.user is not None:
             out, mask, user = self._process_batch_user(np.asarray(data), np.zeros(1, np.int64))
         else:
             out, mask = self.engine.process_window(data, want_nan_mask=True)
             out, mask, user = out[None], mask[None], None
-        row = self._finish(out, mask, user)[0]   # (a table of one hop)
+        row = self.chain.finish(out, mask, user)[0]   # (a table of one hop)
         if self.verbose:
             from . import logger
 
@@ -523,60 +480,25 @@ class DataProcessor:
         """data[C_all, T], window start samples -> float64[n, n_features] (same post-processing,
         applied hop by hop because the normaliser is sequential).  ``spare_cols``: the table MAY come back with that
         many extra columns behind the features (HotPathEngine.process_batch_f64) -- the caller checks the shape."""
-        if self._user is not None:
-            return self._finish(*self._process_batch_user(data, starts))
-        if self.device_normalizer is None or self._norm_in_engine:
+        if self.chain.user is not None:
+            return self.chain.finish(*self._process_batch_user(data, starts))
+        if self.chain.where["normalizer"] != "host":
             # nothing left to do on the host but the NaN policy: conversions pipelined against the device
             rows, mask = self.engine.process_batch_f64(data, starts, want_nan_mask=True, spare_cols=spare_cols)
-            return self._nan_cols.apply(rows, mask)
-        return self._finish(*self.engine.process_batch(data, starts, want_nan_mask=True, staged_output=True))
+            return self.chain.finish_table(rows, mask)
+        return self.chain.finish(*self.engine.process_batch(data, starts, want_nan_mask=True, staged_output=True))
 
-    # -- ragged window lengths (a non-integer number of samples per segment): `Stream.run` cuts the hops into
-    # consecutive runs of one length, one processor per length; what carries over from hop to hop travels between them
-    def ragged_prepare(self) -> None:
-        """The feature normaliser is sequential over ALL hops: it runs on the merged table (`ragged_finish`), and the grid
-        projection, which reads normalised rows, behind it."""
-        if self._norm_in_engine:
-            self.engine.attach_normalizer(None)
-            self._norm_in_engine = False
-        if self._proj_in_engine:
-            self.engine.attach_projection(None)
-            self._proj_in_engine = False
-
-    def ragged_state(self):
-        """Burst history, Kalman filters ... of the engine (its layout depends on sfreq and the settings, not on the
-        window length: nmx_state_export / _import); None when the plan carries nothing."""
-        return self.engine.export_state() or None
-
-    def ragged_set_state(self, state) -> None:
-        self.engine.import_state(state)
-
+    # -- the ragged runs of `Stream.run`: the hops cut into consecutive runs of one length, one processor per length
+    # (LengthTable.run_ragged)
     def ragged_run(self, data: np.ndarray, starts: np.ndarray):
         """One run of equal-length hops -> (float32 engine rows, NaN mask, pre-processed windows or None)."""
-        if self._user is not None:
+        if self.chain.user is not None:
             return self.process_batch_tapped(data, starts)
         return (*self.engine.process_batch(data, starts, want_nan_mask=True), None)
 
     def ragged_finish(self, runs) -> np.ndarray:
         """The runs of `ragged_run` in hop order -> the float64 table (normaliser, user columns, NaN policy)."""
         # one set of user-feature instances sees every hop in order, like the reference
-        user = self._user.rows([w for r in runs for w in r[2]]) if self._user is not None else None
-        return self._finish(np.concatenate([r[0] for r in runs]), np.concatenate([r[1] for r in runs]), user)
+        user = self.chain.user.rows([w for r in runs for w in r[2]]) if self.chain.user is not None else None
+        return self.chain.finish(np.concatenate([r[0] for r in runs]), np.concatenate([r[1] for r in runs]), user)
 
-
-def _ragged_runs(procs: dict, lens: np.ndarray, run) -> list:
-    """Ragged window lengths (a non-integer number of samples per segment): the hops in order as consecutive runs of one
-    length, ``run(processor, a, b)`` computing hops [a, b) on ``procs[length]``.  What carries over from hop to hop (burst
-    history, Kalman filters, raw-normaliser history) travels from processor to processor where the length changes
-    (``ragged_*`` of DataProcessor / MultiDeviceProcessor).  -> the results of ``run`` in hop order."""
-    for p in procs.values():
-        p.ragged_prepare()
-    cuts = [0] + [i for i in range(1, len(lens)) if lens[i] != lens[i - 1]] + [len(lens)]
-    state, runs = None, []
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        p = procs[int(lens[a])]
-        if state is not None:
-            p.ragged_set_state(state)
-        runs.append(run(p, a, b))
-        state = p.ragged_state()
-    return runs

@@ -23,18 +23,17 @@ import os
 
 import numpy as np
 
+from . import _lib
 from . import channels as chmod
-from .data_processor import DataProcessor, UserColumns, _LazyNanCols, _ragged_runs
-from .engine import table_empty
+from .data_processor import DataProcessor, LengthTable, PostChain, UserViews, no_sharded_projection
 from .generator import window_schedule
+from .host_mem import _pool, _rows_ok, parallel_cast, staging_thread, table_empty
 from .settings import NMSettings
 
 
 def _force_collectives() -> bool:
     """NMX_FORCE_COLLECTIVES=1: run the exchange step through the process group even when it has ONE rank (a 1-GPU
     box can then exercise the RCCL code path -- device tensors, object collectives -- that a multi-GPU node takes)."""
-    import os
-
     return os.environ.get("NMX_FORCE_COLLECTIVES", "0") == "1"
 
 
@@ -43,14 +42,6 @@ def channel_shard(n_channels: int, world_size: int, rank: int) -> range:
     base, rem = divmod(n_channels, world_size)
     lo = rank * base + min(rank, rem)
     return range(lo, lo + base + (1 if rank < rem else 0))
-
-
-def _no_projection(settings) -> None:
-    """A grid point mixes the features of channels of every shard: the projection needs them all in one plan."""
-    pp = settings.postprocessing
-    if pp.project_cortex or pp.project_subcortex:
-        raise NotImplementedError("grid projection (project_cortex / project_subcortex) needs every channel in one plan: "
-                                  "it is not supported with channels sharded over several devices (use one device)")
 
 
 def global_keys(sfreq, settings, channels) -> list[str]:
@@ -66,7 +57,7 @@ class ShardedStream:
                  world_size: int = 1, device: int | None = None, lib=None, local_input: bool = False) -> None:
         self.sfreq = sfreq
         self.settings = NMSettings.load(settings)
-        _no_projection(self.settings)
+        no_sharded_projection(self.settings)
         self.channels = chmod.load_channels(channels)
         self.line_noise = line_noise
         self.rank, self.world_size = rank, world_size
@@ -78,7 +69,8 @@ class ShardedStream:
         self._dp = None
         if local_input:   # plan the local rows up front (no GPU needed): callers slice the recording with them
             self._dp = self._processor(None, dry_run=True)
-            self.local_rows = list(self._dp.local_rows)
+            self._local = self._dp.local
+            self.local_rows = list(self._local.rows)
             # an input row is OWNED by the rank whose channel block holds its channel
             self.owned_rows = [self.feature_idx[i] for i in self.shard]
 
@@ -110,18 +102,13 @@ class ShardedStream:
         import torch
         import torch.distributed as dist
 
-        dp = self._dp
-        pos = {j: i for i, j in enumerate(self.local_rows)}
         own = set(self.owned_rows)
-        part = np.zeros((len(dp.local_groups), local_data.shape[1]))
+        part = np.zeros((len(self._local.groups), local_data.shape[1]))
         local_data = np.asarray(local_data)
-        from . import _lib as _libmod
-
-        lib = self._lib if self._lib is not None else _libmod.get_library()   # (host passes only: no device needed)
-        native = (local_data.ndim == 2 and local_data.dtype in (np.float32, np.float64) and local_data.strides[1] == local_data.itemsize
-                  and local_data.strides[0] > 0 and local_data.strides[0] % local_data.itemsize == 0)
-        for g, members in enumerate(dp.local_groups):
-            idx = [pos[int(j)] for j in members if int(j) in own]
+        lib = self._lib if self._lib is not None else _lib.get_library()   # (host passes only: no device needed)
+        native = _rows_ok(local_data, np.float32, np.float64)
+        for g, members in enumerate(self._local.groups):
+            idx = self._local.columns(j for j in members if int(j) in own)
             if not idx:
                 continue
             if native:   # one pass of libnmx's staging helper: nan_to_num of the float32-rounded samples, float64 sum in row order
@@ -138,20 +125,19 @@ class ShardedStream:
             part = t.cpu().numpy()
         return part
 
-    def _gather_mask(self, mask_local: np.ndarray, n_all: int, group=None) -> np.ndarray:
-        """NaN mask over ALL input rows [n_windows, n_all] from every rank's owned rows."""
+    def _gather_mask(self, mask_local: np.ndarray, group=None) -> np.ndarray:
+        """NaN mask over ALL input rows [n_windows, C_all] from every rank's owned rows."""
         import torch
         import torch.distributed as dist
 
-        pos = {j: i for i, j in enumerate(self.local_rows)}
-        mine = (np.asarray(self.owned_rows, np.int64), mask_local[:, [pos[j] for j in self.owned_rows]].astype(np.uint8))
+        mine = (np.asarray(self.owned_rows, np.int64), mask_local[:, self._local.columns(self.owned_rows)].astype(np.uint8))
         if dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or _force_collectives()):
             parts = [None] * dist.get_world_size(group)
             self._comm_device(group)
             dist.all_gather_object(parts, mine, group=group)
         else:
             parts = [mine]
-        full = np.zeros((mask_local.shape[0], n_all), dtype=bool)
+        full = np.zeros((mask_local.shape[0], len(self.channels)), dtype=bool)
         for rows, m in parts:
             full[:, rows] = m.astype(bool)
         return full
@@ -165,22 +151,18 @@ class ShardedStream:
         sums = self.group_sums(data, group)
         return np.concatenate([np.asarray(data, np.float32)] + [chmod.split_hi_lo(v) for v in sums], axis=0)
 
-    def _local_table(self, dp, out: np.ndarray, mask: np.ndarray, group=None) -> np.ndarray:
-        """With ``local_input``: the engine rows -> the float64 table, the NaN policy seeing the mask of every rank."""
-        return dp._finish(out, self._gather_mask(mask, len(self.channels), group))
-
     def _run_ragged(self, data, starts, lens, times, group):
         """Ragged window lengths (a non-integer number of samples per segment): one processor per length, this rank's
-        state handed from processor to processor where the length changes (data_processor._ragged_runs, as Stream.run)."""
-        procs = {int(w): self._processor(int(w)) for w in sorted(set(lens.tolist()))}
-        dp0 = procs[min(procs)]
+        state handed from processor to processor where the length changes (data_processor.LengthTable, as Stream.run)."""
+        table = LengthTable(self._processor)
+        x = self._local_x(data, group) if self.local_input else None
+        runs = table.run_ragged(lens, (lambda p, a, b: p.engine.process_batch(x, starts[a:b], want_nan_mask=True))
+                                if self.local_input else (lambda p, a, b: p.ragged_run(data, starts[a:b])))
+        dp0 = table.by_len[int(lens.min())]
         if not self.local_input:
-            runs = _ragged_runs(procs, lens, lambda p, a, b: p.ragged_run(data, starts[a:b]))
             return list(dp0.keys), dp0.ragged_finish(runs), times
-        x = self._local_x(data, group)
-        runs = _ragged_runs(procs, lens, lambda p, a, b: p.engine.process_batch(x, starts[a:b], want_nan_mask=True))
         out, mask = np.concatenate([o for o, _ in runs]), np.concatenate([m for _, m in runs])
-        return list(dp0.keys), self._local_table(dp0, out, mask, group), times
+        return list(dp0.keys), dp0.chain.finish(out, self._gather_mask(mask, group)), times
 
     def run(self, data: np.ndarray, group=None):
         """-> (local_keys, float64[n_windows, n_local], time_ms) for this rank's channels.
@@ -199,10 +181,11 @@ class ShardedStream:
         if not len(starts):
             return list(dp.keys), np.empty((0, len(dp.keys))), times
         out, mask = dp.engine.process_batch(x, starts, want_nan_mask=True)
-        return list(dp.keys), self._local_table(dp, out, mask, group), times
+        # (the NaN policy sees the mask of every rank)
+        return list(dp.keys), dp.chain.finish(out, self._gather_mask(mask, group)), times
 
 
-class MultiDeviceProcessor:
+class MultiDeviceProcessor(UserViews):
     """Single-process form of the channel shard: one plan per device, one host thread per plan
     (ctypes drops the GIL for the duration of every libnmx call, so the launch sequences, the host <-> device
     copies and the waits of all devices overlap).  Same surface as ``DataProcessor`` for what ``Stream``
@@ -222,7 +205,7 @@ class MultiDeviceProcessor:
         from concurrent.futures import ThreadPoolExecutor
 
         self.settings = NMSettings.load(settings)
-        _no_projection(self.settings)
+        no_sharded_projection(self.settings)
         self.channels = chmod.load_channels(channels)
         devices = [int(d) for d in devices]
         if not devices:
@@ -231,10 +214,9 @@ class MultiDeviceProcessor:
         kw = dict(line_noise=line_noise, verbose=False, window=window, lib=lib,
                   resample_features_at_new_rate=resample_features_at_new_rate)
         layout = DataProcessor(sfreq, self.settings, self.channels, dry_run=True, **kw)
-        self.keys = list(layout.keys)
         self.sfreq_raw = layout.sfreq_raw
         self.ch_names_used = layout.ch_names_used
-        col = {k: i for i, k in enumerate(self.keys)}
+        col = {k: i for i, k in enumerate(layout.keys)}
         self.parts, self._cols = [], []
         self.local_input = bool(local_input)
         while True:
@@ -254,35 +236,30 @@ class MultiDeviceProcessor:
                 for p in self.parts:   # rows without the taps + group-sum structure: replicated input
                     p.engine.close()
                 self.parts, self._cols, self.local_input = [], [], False
-        self.h2d_rows = [len(p.local_rows) + 2 * len(p.local_groups) if self.local_input else len(self.channels)
+        self.h2d_rows = [p.local.n_rows if self.local_input else len(self.channels)
                          for p in self.parts]   # input rows every device receives (profiles/r04_host_boundary.json)
         if self.local_input:
-            # every group sum once, whoever needs it
-            self._groups, gid = [], {}
-            self._part_groups = []
+            # every group sum once, whoever needs it: the groups in order of first use, and which of them each part takes
+            gid: dict = {}
             for p in self.parts:
-                ids = []
                 for members in p.local_groups:
-                    key = tuple(int(j) for j in members)
-                    if key not in gid:
-                        gid[key] = len(self._groups)
-                        self._groups.append(np.asarray(key, dtype=np.int64))
-                    ids.append(gid[key])
-                self._part_groups.append(ids)
+                    gid.setdefault(tuple(int(j) for j in members), len(gid))
+            self._part_groups = [[gid[tuple(int(j) for j in m)] for m in p.local_groups] for p in self.parts]
+            self._groups = [np.asarray(key, dtype=np.int64) for key in gid]
         self.devices = devices[:len(self.parts)]
         self.verbose = verbose
-        self.settings_token = None
-        self._norm_in_engine = all(p._norm_in_engine for p in self.parts)
+        self.settings_token, self.cnt_samples = None, 0
         self._pool = ThreadPoolExecutor(max_workers=len(self.parts))
         # user-registered features see ALL channels (features/feature_processor.py:52-53): the parts hand back the
-        # pre-processed windows of their channel blocks, the coordinator runs the plugins on the joined window
+        # pre-processed windows of their channel blocks, the coordinator's chain runs the plugins on the joined window
+        # (and the NaN policy; every part's own chain normalises its columns)
         from . import user_features as _registered
 
-        self._user = None
-        if _registered:
-            self._user = UserColumns(self.settings, self.ch_names_used, self.sfreq_raw, self.keys,
-                                     device=self.devices[0], lib=lib)
+        self.chain = PostChain(self.settings, self.ch_names_used, None, bool(_registered), self.devices[0], lib)
+        self.chain.start(layout.keys, self.ch_names_used, self.sfreq_raw, normalize=False)
+        self.keys = self.chain.keys
         self._user_chunk = 64
+        self._gather = self._gather_dst = self._runs = self._groups_i32 = None   # (built on first use)
         # threads of libnmx's staging passes.  The library's default (an eighth of the machine, 4 - 16) assumes eight ranks
         # share a node; here ONE process feeds every device, and the pass that reads the float64 recording for all parts sets
         # the rate beyond two of them (profiles/r06_staging_bandwidth.json: 16 threads 50 - 70 GB/s of source, 64: 65 - 90;
@@ -292,54 +269,38 @@ class MultiDeviceProcessor:
         if len(self.devices) > 2 and not os.environ.get("NMX_HOST_THREADS"):
             self.stage_threads = int(max(16, min(64, 8 * len(self.devices), (os.cpu_count() or 32) // 2)))
         self.pipeline_min = (64, 1 << 20)   # hops, samples: below, staging and widening are not worth their threads
-        self._nan_cols = _LazyNanCols(self.keys, self.ch_names_used)
 
     @property
     def engine(self):
         return self.parts[0].engine   # window length / input shape are the same on every device
 
-    @property
-    def user_features(self) -> dict:
-        return self._user.features if self._user is not None else {}
-
-    @property
-    def user_keys(self):
-        return self._user.user_keys if self._user is not None else None
-
     def projection_sidecar(self) -> dict:
-        """No grid projection across devices (``_no_projection``): nothing to add to the sidecar."""
+        """No grid projection across devices (``no_sharded_projection``): nothing to add to the sidecar."""
         return {}
 
     def reset(self) -> None:
         for p in self.parts:
             p.reset()
-        if self._user is not None:
-            self._user.reset()
+        self.chain.reset()
 
     def _finish(self, outs, mask: np.ndarray, user: np.ndarray | None = None) -> np.ndarray:
-        """The parts' float32 rows (hop order) -> the float64 table: every part normalises and widens its own columns
-        (the normaliser is per column), then the joined table takes the user columns and the NaN policy."""
-        zero = np.zeros_like(mask)
-        table = self._merge([p._finish(o, zero) for p, o in zip(self.parts, outs)])
-        if user is not None:
-            table = self._user.merge(table, user)
-        return self._nan_cols.apply(table, mask)
+        """The parts' float32 rows (hop order) -> the float64 table: every part's chain normalises and widens its own columns
+        (the normaliser is per column), then the coordinator's chain gives the joined table the user columns and the NaN
+        policy."""
+        return self.chain.finish_table(self._merge([p.chain.table(o) for p, o in zip(self.parts, outs)]), mask, user)
 
     def _merge(self, rows) -> np.ndarray:
         """The parts' tables side by side -> the global column order (a gather with one precomputed permutation, row
         blocks on the conversion threads: a per-part fancy-index scatter of 8 000 columns cost 30 ms per 1024 hops)."""
-        from .engine import _pool
-
         n, F = rows[0].shape[0], len(self.keys)
-        n_builtin = int(sum(len(c) for c in self._cols))
-        if getattr(self, "_gather", None) is None or len(self._gather) != n_builtin:
+        if self._gather is None:
             order = np.concatenate(self._cols)                 # global column of every concatenated column
             self._gather = np.argsort(order, kind="stable")     # concatenated column of every global built-in column
             self._gather_dst = np.sort(order)
-        out = np.full((n, F), np.nan) if F != n_builtin else np.empty((n, F))
+        out = np.full((n, F), np.nan) if F != self.chain.n_feat else np.empty((n, F))
         cat = rows[0] if len(rows) == 1 else None
         edges = [(i * n) // 8 for i in range(9)] if n >= 64 else [0, n]
-        contiguous = F == n_builtin or np.array_equal(self._gather_dst, np.arange(n_builtin))
+        contiguous = F == self.chain.n_feat or np.array_equal(self._gather_dst, np.arange(self.chain.n_feat))
 
         def job(i):
             a, b = edges[i], edges[i + 1]
@@ -347,7 +308,7 @@ class MultiDeviceProcessor:
                 return
             blk = cat[a:b] if cat is not None else np.concatenate([r[a:b] for r in rows], axis=1)
             if contiguous:
-                np.take(blk, self._gather, axis=1, out=out[a:b, :n_builtin])
+                np.take(blk, self._gather, axis=1, out=out[a:b, :self.chain.n_feat])
             else:
                 out[a:b][:, self._gather_dst] = blk[:, self._gather]
 
@@ -356,7 +317,7 @@ class MultiDeviceProcessor:
 
     def _column_runs(self):
         """Per part: (first column in the table, first column of the part's row, length) of every contiguous run."""
-        if getattr(self, "_runs", None) is None:
+        if self._runs is None:
             self._runs = []
             for cols in self._cols:
                 cut = np.flatnonzero(np.diff(cols) != 1) + 1
@@ -374,11 +335,9 @@ class MultiDeviceProcessor:
         lib = self.parts[0].engine.lib
         n, F = outs[0].shape[0], len(self.keys)
         self._column_runs()
-        n_builtin = int(sum(len(c) for c in self._cols))
-        table = table_empty((n, F), np.nan if F != n_builtin else None)
+        table = table_empty((n, F), np.nan if F != self.chain.n_feat else None)
         for o, runs in zip(outs, self._runs):
-            o = o if (o.dtype == np.float32 and o.ndim == 2 and o.strides[1] == 4 and o.strides[0] % 4 == 0
-                      and o.strides[0] > 0) else np.ascontiguousarray(o, dtype=np.float32)
+            o = o if _rows_ok(o, np.float32) else np.ascontiguousarray(o, dtype=np.float32)
             if n and len(runs):
                 lib.check(lib.lib.nmx_host_widen_rows(table.ctypes.data, F, o.ctypes.data, o.strides[0] // 4, 0, n,
                                                       runs.ctypes.data, len(runs), 0))
@@ -391,8 +350,7 @@ class MultiDeviceProcessor:
         stream/data_processor.py:255) by libnmx's staging helpers: one pass over the recording for the sums, one for the
         rows (the NumPy reduction along the channel axis ran at ~3 GB/s and set the rate of the whole stream)."""
         data = np.asarray(data)
-        if not (data.dtype in (np.float32, np.float64) and data.strides[1] == data.itemsize and data.strides[0] > 0
-                and data.strides[0] % data.itemsize == 0):
+        if not _rows_ok(data, np.float32, np.float64):   # (libnmx reads float rows in place: a C-ordered copy otherwise)
             data = np.ascontiguousarray(data, dtype=np.float32 if data.dtype == np.float32 else np.float64)
         lib = self.parts[0].engine.lib
         T, f64, ld = data.shape[1], int(data.dtype == np.float64), data.strides[0] // data.itemsize
@@ -402,70 +360,46 @@ class MultiDeviceProcessor:
             v, rows = np.empty(T), np.ascontiguousarray(g, dtype=np.int32)
             lib.check(lib.lib.nmx_host_group_sums(v.ctypes.data, data.ctypes.data, f64, ld, rows.ctypes.data, len(rows), 0, T, 0))
             hilo.append(chmod.split_hi_lo(v))
-        xs = []
-        for p, ids in zip(self.parts, self._part_groups):
-            nl = len(p.local_rows)
-            x = p.engine._pinned.array("x_local", (nl + 2 * len(ids), T), np.float32)
-            rows = np.ascontiguousarray(p.local_rows, dtype=np.int32)
-            lib.check(lib.lib.nmx_host_stage_rows(x.ctypes.data, x.strides[0] // 4, data.ctypes.data, f64, ld,
-                                                  rows.ctypes.data, nl, 0, T, None, 0))
-            for q, gi in enumerate(ids):
-                x[nl + 2 * q:nl + 2 * q + 2] = hilo[gi]
-            xs.append(x)
-        return xs
-
-    def _stage_local_slice(self, data, f64, ld, a, b, xs, plan):
-        """Samples [a, b) of every part's staging array: its rows, and the hi / lo rows of its group sums -- the
-        recording is read once (nmx_host_stage_parts: rows out and group sums block by block)."""
-        lib = self.parts[0].engine.lib
-        dst, gptr, grows, sums, sum_ptrs = plan
-        lib.check(lib.lib.nmx_host_stage_parts(data.ctypes.data, f64, ld, data.shape[0], a, b, dst.ctypes.data, len(sums),
-                                               gptr.ctypes.data, grows.ctypes.data, sum_ptrs.ctypes.data, self.stage_threads))
-        hilo = [chmod.split_hi_lo(v[a:b]) for v in sums]
-        for ids, rows, x in zip(self._part_groups, self._rows_i32, xs):
-            nl = len(rows)
-            for q, gi in enumerate(ids):
-                x[nl + 2 * q:nl + 2 * q + 2, a:b] = hilo[gi]
+        return [p.local.stage(p.engine._pinned.array("x_local", (p.local.n_rows, T), np.float32), data, lib,
+                              [hilo[g] for g in ids]) for p, ids in zip(self.parts, self._part_groups)]
 
     def _process_pipelined(self, data, starts, spare_cols: int = 0):
         """The whole batch with the coordinator's passes NEXT to the device work (HotPathEngine.run_pipelined): one
         thread stages the recording slice by slice for every part -- group sums and the part's rows with local input,
         one shared float32 copy otherwise -- and publishes its progress to every plan; every part widens its rows into
         its columns of the table as its chunks land."""
-        import threading
-
-        from .engine import parallel_cast
-
         data = np.asarray(data)
-        if not (data.dtype in (np.float32, np.float64) and data.strides[1] == data.itemsize and data.strides[0] > 0
-                and data.strides[0] % data.itemsize == 0):
+        if not _rows_ok(data, np.float32, np.float64):   # (libnmx reads float rows in place: a C-ordered copy otherwise)
             data = np.ascontiguousarray(data, dtype=np.float32 if data.dtype == np.float32 else np.float64)
         engines = [p.engine for p in self.parts]
         lib = engines[0].lib
         n, F, T = len(starts), len(self.keys), data.shape[1]
         f64, ld = int(data.dtype == np.float64), data.strides[0] // data.itemsize
         runs = self._column_runs()
-        n_builtin = int(sum(len(c) for c in self._cols))
-        table = table_empty((n, F + spare_cols), np.nan if F != n_builtin else None)
+        table = table_empty((n, F + spare_cols), np.nan if F != self.chain.n_feat else None)
         if self.local_input:
-            if getattr(self, "_rows_i32", None) is None:
-                self._rows_i32 = [np.ascontiguousarray(p.local_rows, dtype=np.int32) for p in self.parts]
+            if self._groups_i32 is None:
                 self._groups_i32 = [np.ascontiguousarray(g, dtype=np.int32) for g in self._groups]
-            xs = [e._pinned.array("x_local", (len(r) + 2 * len(ids), T), np.float32)
-                  for e, r, ids in zip(engines, self._rows_i32, self._part_groups)]
+            xs = [p.engine._pinned.array("x_local", (p.local.n_rows, T), np.float32) for p in self.parts]
 
             # where every source row goes (pointer to sample 0 of its destination row), the groups as CSR, their sums
             dst = np.zeros(data.shape[0], dtype=np.uint64)
-            for rows, x in zip(self._rows_i32, xs):
-                dst[rows] = x.ctypes.data + np.arange(len(rows), dtype=np.uint64) * np.uint64(x.strides[0])
+            for p, x in zip(self.parts, xs):
+                p.local.row_pointers(x, dst)
             gptr = np.concatenate([[0], np.cumsum([len(g) for g in self._groups_i32])]).astype(np.int32)
             grows = (np.concatenate(self._groups_i32) if self._groups_i32 else np.zeros(0)).astype(np.int32)
             sums = [np.empty(T) for _ in self._groups_i32]
             sum_ptrs = np.array([v.ctypes.data for v in sums], dtype=np.uint64)
-            plan = (dst, gptr, grows, sums, sum_ptrs)
 
             def stage(a, b):
-                self._stage_local_slice(data, f64, ld, a, b, xs, plan)
+                # samples [a, b) of every part's staging array: its rows, and the hi / lo rows of its group sums -- the
+                # recording is read once (nmx_host_stage_parts: rows out and group sums block by block)
+                lib.check(lib.lib.nmx_host_stage_parts(data.ctypes.data, f64, ld, data.shape[0], a, b, dst.ctypes.data,
+                                                       len(sums), gptr.ctypes.data, grows.ctypes.data, sum_ptrs.ctypes.data,
+                                                       self.stage_threads))
+                hilo = [chmod.split_hi_lo(v[a:b]) for v in sums]
+                for p, ids, x in zip(self.parts, self._part_groups, xs):
+                    p.local.fill_pairs(x, [hilo[g] for g in ids], a, b)
         else:
             dcs = [e._host_offsets(data) for e in engines]   # (every plan decides from the same rows: the same constants)
             x = engines[0]._pinned.array("x_shared", data.shape, np.float32)
@@ -476,19 +410,7 @@ class MultiDeviceProcessor:
         ctrs = [e.pipeline_counters() for e in engines]
         failed: list = []
 
-        def stage_all():
-            try:
-                edges = engines[0].pipeline_edges(starts, T)
-                for a, b in zip(edges[:-1], edges[1:]):
-                    stage(a, b)
-                    for c in ctrs:
-                        c[0] = b
-            except BaseException as e:   # noqa: BLE001 -- reported below; the plans run out on what is there
-                failed.append(e)
-                for c in ctrs:
-                    c[0] = T
-
-        th = threading.Thread(target=stage_all, daemon=True)
+        th = staging_thread(lambda: engines[0].pipeline_edges(starts, T), stage, ctrs, T, failed)
         th.start()
         try:
             masks = list(self._pool.map(
@@ -505,11 +427,7 @@ class MultiDeviceProcessor:
         """NaN mask over ALL input rows from every part's local rows (a group-sum row is never NaN)."""
         full = np.zeros((masks[0].shape[0], n_all), dtype=bool)
         for p, m in zip(self.parts, masks):
-            r, nl = p.local_rows, len(p.local_rows)
-            if nl and list(r) == list(range(r[0], r[0] + nl)):
-                full[:, r[0]:r[0] + nl] |= m[:, :nl]
-            else:
-                full[:, r] |= m[:, :nl]
+            p.local.mask_to_all(m, full)
         return full
 
     def _run_parts(self, data, starts, tapped: bool, staged: bool = False):
@@ -524,14 +442,14 @@ class MultiDeviceProcessor:
 
         W_in = self.parts[0].engine.W_in
         # nothing between the incoming rows and the features on any part (no re-reference, channel pick or filter): the
-        # plugins get the exact float64 window, as the one-plan stream gives them (DataProcessor._host_windows)
+        # plugins get the exact float64 window, as the one-plan stream gives them (DataProcessor.process_batch_tapped)
         identity = all(p.engine.preprocessing_is_identity for p in self.parts)
 
         def job(px):
             p, x = px
             if tapped and identity:
                 o, m = p.engine.process_batch(x, starts, want_nan_mask=True)
-                rows = list(p.local_rows)   # (identity: exactly the part's channels, no group-sum rows)
+                rows = list(p.local.rows)   # (identity: exactly the part's channels, no group-sum rows)
                 wins = np.stack([np.nan_to_num(np.asarray(data[rows, int(a):int(a) + W_in], dtype=np.float64)) for a in starts])
                 return o, m, wins
             if tapped:
@@ -547,7 +465,8 @@ class MultiDeviceProcessor:
     def process_batch(self, data: np.ndarray, starts: np.ndarray, spare_cols: int = 0) -> np.ndarray:
         """``spare_cols``: as DataProcessor.process_batch (extra columns behind the features, pipelined path only)."""
         starts = np.asarray(starts, dtype=np.int64)
-        if self._user is None and all(p.device_normalizer is None or p._norm_in_engine for p in self.parts):
+        user = self.chain.user
+        if user is None and all(p.chain.where["normalizer"] != "host" for p in self.parts):
             # nothing between the engines' rows and the table but the widening and the NaN policy
             if (len(starts) >= self.pipeline_min[0] and np.size(data) >= self.pipeline_min[1]
                     and os.environ.get("NMX_PIPELINE", "1") != "0"):
@@ -556,46 +475,33 @@ class MultiDeviceProcessor:
                 got = self._run_parts(data, starts, False, staged=True)
                 table = self._merge_widen([o for o, _, _ in got])
                 mask = got[0][1]   # over ALL incoming rows, the same for every part
-            return self._nan_cols.apply(table, mask)
-        if self._user is None:
+            return self.chain.finish_table(table, mask)
+        if user is None:
             got = self._run_parts(data, starts, False)
             return self._finish([o for o, _, _ in got], got[0][1])
         tables = []
         for i in range(0, len(starts), self._user_chunk):
             got = self._run_parts(data, starts[i:i + self._user_chunk], True)
             # contiguous channel blocks in device order: the joined window is the single-device one
-            user = self._user.rows(np.concatenate([w for _, _, w in got], axis=1))
-            tables.append(self._finish([o for o, _, _ in got], got[0][1], user))
+            rows = user.rows(np.concatenate([w for _, _, w in got], axis=1))
+            tables.append(self._finish([o for o, _, _ in got], got[0][1], rows))
         return np.concatenate(tables) if tables else np.empty((0, len(self.keys)))
 
-    # -- ragged window lengths: the protocol of DataProcessor.ragged_* over the parts --------------------------------
-    def ragged_prepare(self) -> None:
-        for p in self.parts:
-            p.ragged_prepare()
-        self._norm_in_engine = False
-
-    def ragged_state(self):
-        st = [p.engine.export_state() for p in self.parts]
-        return st if any(st) else None
-
-    def ragged_set_state(self, state) -> None:
-        for p, s_ in zip(self.parts, state):
-            if s_:
-                p.engine.import_state(s_)
-
+    # -- the ragged runs of a data_processor.LengthTable, over the parts (it hands one state blob per part along) ----------
     def ragged_run(self, data: np.ndarray, starts: np.ndarray):
-        got = self._run_parts(data, np.asarray(starts, dtype=np.int64), self._user is not None)
+        tapped = self.chain.user is not None
+        got = self._run_parts(data, np.asarray(starts, dtype=np.int64), tapped)
         # contiguous channel blocks in device order: the joined window is the single-device one
-        wins = np.concatenate([w for _, _, w in got], axis=1) if self._user is not None else None
+        wins = np.concatenate([w for _, _, w in got], axis=1) if tapped else None
         return [o for o, _, _ in got], got[0][1], wins
 
     def ragged_finish(self, runs) -> np.ndarray:
-        user = self._user.rows([w for r in runs for w in r[2]]) if self._user is not None else None
+        user = self.chain.user.rows([w for r in runs for w in r[2]]) if self.chain.user is not None else None
         return self._finish([np.concatenate([r[0][i] for r in runs]) for i in range(len(self.parts))],
                             np.concatenate([r[1] for r in runs]), user)
 
     def process(self, data: np.ndarray) -> dict:
-        if self._user is not None or self.local_input:
+        if self.chain.user is not None or self.local_input:
             row = self.process_batch(np.asarray(data), np.zeros(1, np.int64))[0]
             return dict(zip(self.keys, row.tolist()))
         parts = list(self._pool.map(lambda p: p.process(data), self.parts))

@@ -14,7 +14,7 @@ from pathlib import Path
 import numpy as np
 
 from . import channels as chmod
-from .data_processor import DataProcessor, _ragged_runs
+from .data_processor import DataProcessor, LengthTable
 from .generator import window_schedule
 from .settings import NMSettings
 
@@ -85,14 +85,13 @@ class Stream:
             dp = MultiDeviceProcessor(self.sfreq, self.settings, self.channels, line_noise=self.line_noise,
                                       devices=self.devices, window=window, lib=self._lib, verbose=self.verbose,
                                       resample_features_at_new_rate=self._resample_new_rate)
-            dp.settings_token = self._processor_token()
-            return dp
-        dp = DataProcessor(sfreq=self.sfreq, settings=self.settings, channels=self.channels,
-                           coord_names=self.coord_names, coord_list=self.coord_list, path_grids=self.path_grids,
-                           line_noise=self.line_noise, verbose=self.verbose,
-                           device=self.devices[0] if self.devices else self.device,
-                           window=window, lib=self._lib,
-                           resample_features_at_new_rate=self._resample_new_rate)
+        else:
+            dp = DataProcessor(sfreq=self.sfreq, settings=self.settings, channels=self.channels,
+                               coord_names=self.coord_names, coord_list=self.coord_list, path_grids=self.path_grids,
+                               line_noise=self.line_noise, verbose=self.verbose,
+                               device=self.devices[0] if self.devices else self.device,
+                               window=window, lib=self._lib,
+                               resample_features_at_new_rate=self._resample_new_rate)
         dp.settings_token = self._processor_token()
         return dp
 
@@ -169,17 +168,13 @@ class Stream:
             # a FRESH processing state per run, like the reference's new DataProcessor (:233-242), one
             # processor per window length.  The processor built by __init__ (or by the previous run) is
             # reused with its state reset when it fits -- same results, no second plan build.
-            procs = {}
-            for w in groups:
-                dp = self.data_processor
-                if (len(groups) == 1 and dp is not None and dp.engine.W_in == w
-                        and dp.settings_token == self._processor_token(settings_token)):
-                    dp.reset()
-                    procs[w] = dp
-                else:
-                    procs[w] = self._make_processor(w)
-            self.data_processor = dp0 = procs[groups[0]]
+            dp0 = self.data_processor
             if len(groups) == 1:
+                if (dp0 is not None and dp0.engine.W_in == groups[0]
+                        and dp0.settings_token == self._processor_token(settings_token)):
+                    dp0.reset()
+                else:
+                    self.data_processor = dp0 = self._make_processor(groups[0])
                 side = self._side_files(out_dir, experiment_name)
                 had = [f.exists() for f in side]
                 after = threading.Thread(target=write_after, daemon=True)
@@ -196,13 +191,12 @@ class Stream:
                         raise e from after_err[0]
                     raise
             else:
-                # ragged windows (float sampling rate): the normaliser is sequential over ALL hops, so it
-                # cannot run inside the per-length engines: detached, it normalises the merged rows afterwards.
-                # Hops in ORDER, as consecutive runs of one window length: the burst history (features/bursts.py:149-173)
-                # and the Kalman filters of the band powers (bandpower.py:147-163) carry over from hop to hop whatever
-                # the window length, so the state travels from processor to processor where the length changes
-                # (DataProcessor.ragged_* / MultiDeviceProcessor.ragged_*: one state blob per device there)
-                runs = _ragged_runs(procs, lens, lambda p, a, b: p.ragged_run(data, starts[a:b]))
+                # ragged windows (float sampling rate): hops in ORDER as consecutive runs of one window length; the burst
+                # history (features/bursts.py:149-173) and the Kalman filters of the band powers (bandpower.py:147-163)
+                # travel from processor to processor, the normaliser runs on the merged rows (data_processor.LengthTable)
+                table = LengthTable(self._make_processor)
+                runs = table.run_ragged(lens, lambda p, a, b: p.ragged_run(data, starts[a:b]))
+                self.data_processor = dp0 = table.by_len[groups[0]]
                 rows = dp0.ragged_finish(runs)
             keys = list(dp0.keys)   # after the first hop: user-feature keys are known once calc_feature has run
         last = starts + lens - 1   # the targets' column: the last sample of every window (stream/stream.py:319-329)

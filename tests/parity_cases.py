@@ -2799,7 +2799,7 @@ def case_processor_hop_by_hop_with_two_window_lengths(lib):
         df = Stream(sfreq=sfreq, channels=ch, settings=s, lib=lib, line_noise=50).run(data, save_csv=False)
         dp = DataProcessor(sfreq=sfreq, settings=s, channels=ch, line_noise=50, lib=lib, verbose=False)
         rows = [dp.process(data[:, a:a + n]) for a, n in zip(starts, lens)]
-        assert list(rows[0]) == list(df.columns[:-1]) and len(dp._by_len) == 2
+        assert list(rows[0]) == list(df.columns[:-1]) and len(dp._lengths.by_len) == 2
         got = np.array([list(r.values()) for r in rows])
         want = df.to_numpy(dtype=np.float64)[:, :-1]
         if not norm:

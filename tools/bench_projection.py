@@ -87,7 +87,7 @@ def main() -> None:
                 per_hop = 4 * (len(lay.gather) * lay.n_feat + lay.n_grid)
                 # the kernel alone on 1024 device-resident rows of the engine's width, timed with HIP events
                 rows = torch.randn((n, dp.engine.row_width), device="cuda", dtype=torch.float32)
-                proj = dp._proj_dev
+                proj = dp.chain.proj_dev
                 for _ in range(3):
                     proj.process_device(rows.data_ptr(), rows.shape[1], n)
                 kt = []
