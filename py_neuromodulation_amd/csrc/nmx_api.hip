@@ -544,10 +544,12 @@ static void be_launch_sharp(const NmxSharpArgs& A, NmxSharpKind kind, int n_item
 }
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
+extern "C" void nmx_hilbert_long_launch(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind kind, long long n_items, size_t lds, be_stream_t s) {
   be_init_once();
   if (kind == NMX_HIL_W500) nmx_wave_launch_hilbert_w500(&A, n_items, s);
   else if (kind == NMX_HIL_W1000) nmx_wave_launch_hilbert_w1000(&A, n_items, s);
+  else if (kind == NMX_HIL_LONG) nmx_hilbert_long_launch(&A, n_items, s);
   else nmx_hilbert_fixed_launch128(&A, n_items, lds, s);
 }
 extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, int nr, bool list_lds, size_t lds, hipStream_t s);

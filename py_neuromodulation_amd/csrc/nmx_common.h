@@ -208,10 +208,11 @@ struct NmxTimeOscArgs {
 
 // the time / oscillatory and Hilbert kernels a plan launches, chosen when it is built (build_timeosc, build_hilbert)
 enum NmxTimeOscKind { NMX_TO_SCAN, NMX_TO_SPECMM, NMX_TO_W1000_LOW, NMX_TO_W1000, NMX_TO_STFT500, NMX_TO_W510, NMX_TO_FIXED128, NMX_TO_GENERIC, NMX_TO_LONG };
-enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128 };
+enum NmxHilbertKind { NMX_HIL_W500, NMX_HIL_W1000, NMX_HIL_FIXED128, NMX_HIL_LONG };   // LONG: nmx_k_hilbert_long.h (3 W + 4 floats beyond LDS)
 // the run statistics of the bursts chain (build_bursts): the envelope in the registers of a wave, 16 / 32 chunks per lane, all rows
 // or only those the Hilbert kernel stored whole (NmxBurstStatArgs::full); or the LDS kernel
-enum NmxBurstStatKind { NMX_BSTAT_REG16, NMX_BSTAT_REG16_SPARSE, NMX_BSTAT_REG32, NMX_BSTAT_REG32_SPARSE, NMX_BSTAT_GENERIC };
+// (windows up to 16 384 samples), or the tile scan that reads the envelope from memory (NmxBurstStatArgs::scan_tile)
+enum NmxBurstStatKind { NMX_BSTAT_REG16, NMX_BSTAT_REG16_SPARSE, NMX_BSTAT_REG32, NMX_BSTAT_REG32_SPARSE, NMX_BSTAT_GENERIC, NMX_BSTAT_SCAN };
 // the sharp-wave launches (build_sharp): the list kernel over every item, or the compact-LDS dense launch + the list kernel over the
 // items it flagged; the list kernel's lists in LDS, or (long windows) in slabs of device memory (nmx_wave_slab.hip)
 enum NmxSharpKind { NMX_SHARP_LIST, NMX_SHARP_DENSE_LIST, NMX_SHARP_SLAB, NMX_SHARP_DENSE_SLAB };

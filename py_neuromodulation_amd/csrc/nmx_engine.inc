@@ -251,6 +251,7 @@ struct Plan {
   bool have_coh = false;
   int nt_bank = 256;
   int chunk_windows = 1024;
+  int burst_handoff_mb = 2048;   // windows above 16 384 samples: budget of the bursts chain's hand-off buffers (batch_chunk_sizes; NMX_BURST_HANDOFF_MB)
   bool tiny_inline = true;          // host batches of a few hops on ONE stream (nmx_engine_run.inc)
   bool starts_mod4 = false;         // every window start of the current batch is a multiple of 4 samples
   // scratch

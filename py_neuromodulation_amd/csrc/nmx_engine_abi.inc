@@ -65,14 +65,27 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   NMX_REQUIRE(desc->n_channels >= 1, "n_channels must be >= 1");
   // 16 384 samples for a plan in general; up to 40 000 (the partitioned FIR stage's bound) for a plan whose window-sized
   // stages are all sized for it: the FIR stages (notch, preprocessing_filter, the sharp-wave pre-filters), re-referencing,
-  // the sharp-wave analysis (long-window mode of build_sharp) and the long-window time / oscillatory kernel (build_timeosc:
-  // Hjorth, raw, line length, FFT, Welch)
+  // the sharp-wave analysis (long-window mode of build_sharp), the long-window time / oscillatory kernel (build_timeosc:
+  // Hjorth, raw, line length, FFT, Welch) and the bursts chain (partitioned bank, long Hilbert kernel, staged walk, scan
+  // statistics: build_hilbert, build_bursts)
   NMX_REQUIRE(desc->window >= 4 && desc->window <= 40000, "window must be in [4, 40 000 samples]");
-  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH;
-  NMX_REQUIRE(desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0),
+  // Bursts above 16 384 samples are OPT-IN (NMX_LONG_BURSTS=1).  The chain is sized for them like the stages above, but the
+  // refusal of such a plan is behaviour the suite pins (tests/timeosc_long_cases.py: a 20 000-sample plan with fft and bursts
+  // raises): a plan that was refused stays refused until the caller asks.  Making it the default is this one test and the
+  // default of this variable.
+  const bool long_bursts = env_int("NMX_LONG_BURSTS", 0) != 0;
+  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH |
+                           (long_bursts ? NMX_F_BURSTS : 0u);
+  const bool long_fits = desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0);
+  if (long_bursts)
+    NMX_REQUIRE(long_fits,
+                "window must be in [4, 16 384] samples for a plan with stft, bandpass_filter, coherence, raw_normalization or "
+                "raw_resampling; only raw_hjorth, return_raw, linelength, fft, welch, sharpwave_analysis and bursts run up to 40 000 samples, "
+                "behind re-referencing and FIR pre-processing");
+  NMX_REQUIRE(long_fits,
               "window must be in [4, 16 384] samples for a plan with stft, bandpass_filter, bursts, coherence, raw_normalization or "
               "raw_resampling; only raw_hjorth, return_raw, linelength, fft, welch and sharpwave_analysis run up to 40 000 samples, behind "
-              "re-referencing and FIR pre-processing");
+              "re-referencing and FIR pre-processing (bursts too with NMX_LONG_BURSTS=1 in the environment)");
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");
   NMX_REQUIRE(desc->n_extra_cols >= 0 && (long long)desc->n_outputs + desc->n_extra_cols < (1ll << 30),
@@ -126,6 +139,7 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   P->nt_bank = 256;
   P->tiny_inline = env_int("NMX_TINY_INLINE", 1) != 0;
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
+  P->burst_handoff_mb = std::max(1, env_int("NMX_BURST_HANDOFF_MB", P->burst_handoff_mb));
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
   if ((rc = build_front(*P)) || (rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) ||
       (rc = build_notch(*P)) || (rc = build_bursts(*P)) || (rc = build_sharp(*P)) || (rc = build_kalman(*P)) ||

@@ -1,12 +1,99 @@
 // nmx_engine_plan_bursts.inc -- the bursts chain as a stage: its plan-time choices (build_hilbert, build_bursts) and its launch
 // sequence for one chunk (launch_burst_stage).  Included by nmx_engine.inc.
 
+// Long Hilbert kernel (nmx_k_hilbert_long.h): the smallest D <= 64 that divides W and leaves a complex transform of M = W / D
+// <= 8192 points (two LDS buffers of 64 KiB) whose factors the FFT engine takes.  0: none (a prime above 8192, ...).
+static int hilbert_split(int W) {
+  for (int D = 2; D <= 64; ++D) {
+    if (W % D) continue;
+    int nc = W / D, twos = 0, stages = 0;
+    if (nc > 8192) continue;
+    if (nc < 2) break;
+    while (nc % 2 == 0) { nc /= 2; ++twos; }
+    bool ok = true;
+    for (int p = 3; nc > 1 && ok; ) {   // (build_fft: one stage per odd prime factor, radix 4 for pairs of twos)
+      if (nc % p == 0) { nc /= p; ++stages; if (p > 4096) ok = false; }
+      else if ((long long)p * p > nc) p = nc;
+      else p += 2;
+    }
+    if (ok && stages + (twos + 1) / 2 <= NMX_MAX_STAGES) return D;
+  }
+  return 0;
+}
+
+// the threshold history of a plan: ring length and top-K list entries (nmx_k_bursts.h), refused beyond NMX_THR_K_MAX
+static int burst_history(const nmx_plan_desc& d, int* n_ring, int* K) {
+  const double q = d.burst_threshold / 100.0;
+  NMX_REQUIRE(q >= 0.0 && q <= 1.0, "burst threshold must be a percentile in [0, 100]");
+  NMX_REQUIRE(d.sfreq * d.burst_time_duration_s < 2147483647.0, "burst ring buffer (sfreq x time_duration_s) too long");
+  *n_ring = (int)(d.sfreq * d.burst_time_duration_s);
+  NMX_REQUIRE(*n_ring >= 2, "burst ring buffer too short");
+  *K = std::min((int)std::floor((1.0 - q) * (double)(*n_ring - 1)) + 2, *n_ring);
+  if (*K > NMX_THR_K_MAX)
+    return nmx_fail(NMX_E_INVALID, "burst threshold history too long: floor((1 - threshold / 100) x (int(sfreq x time_duration_s) - 1)) + 2 = " +
+                    std::to_string(*K) + " top-K list entries, the limit is 1 048 576 (bursts_settings.threshold, "
+                    "bursts_settings.time_duration_s and the sampling rate the bursts see)");
+  return 0;
+}
+
+// ... for a series whose generic layout (3 W + 4 floats) does not fit LDS
+static int build_hilbert_long(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  NmxHilbertArgs& H = P.bursts.hil;
+  int rc, n_ring, K;
+  // (a history beyond the limit is refused before the slabs are allocated, as build_bursts refuses it before the state)
+  if ((d.features & NMX_F_BURSTS) && (rc = burst_history(d, &n_ring, &K))) return rc;
+  const int W = d.window, D = hilbert_split(W);
+  NMX_REQUIRE(D > 0, "bursts: no supported split of a " + spaced(W) + "-point Hilbert transform (a window above 13 650 samples "
+              "needs a divisor D <= 64 with window / D <= 8192 and prime factors <= 4096)");
+  H.long_mode = 1;
+  H.split_d = D;
+  H.sub_m = W / D;
+  if ((rc = build_fft(P, H.sub_m, &H.hil_c))) return rc;
+  auto it = P.twn_cache.find(W);
+  if (it == P.twn_cache.end()) {
+    std::vector<float> t(2 * (size_t)W);
+    for (int k = 0; k < W; ++k) {
+      const double a = -2.0 * kPi * (double)k / (double)W;
+      t[2 * k] = (float)std::cos(a);
+      t[2 * k + 1] = (float)std::sin(a);
+    }
+    const float2* p = (const float2*)upload(P, t.data(), t.size() * sizeof(float));
+    if (!p) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+    it = P.twn_cache.emplace(W, p).first;
+  }
+  H.tw_n = it->second;
+  H.off_a = 0;
+  H.off_b = al4(2 * H.sub_m);
+  H.off_y = 0;
+  H.lds_floats = H.off_b + al4(2 * H.sub_m) + 64;
+  NMX_REQUIRE((size_t)H.lds_floats * 4 <= 160 * 1024, "internal: long Hilbert kernel: LDS budget");
+  // one workgroup per CU (two where the buffers leave room); the slabs -- the one-sided spectrum, (W + 1) / 2 complex each --
+  // within 64 MiB of device memory
+  H.slab_floats = al4(2 * ((W + 1) / 2));
+  H.slab_blocks = 1;
+#ifndef NMX_HOST_EMU
+  const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)H.lds_floats * 4))));
+  size_t blocks = std::min((size_t)P.n_cu * per_cu, ((size_t)64 << 20) / ((size_t)H.slab_floats * 4));
+  H.slab_blocks = (int)std::max<size_t>(1, blocks);
+#endif
+  H.slab = (float*)plan_alloc(P, (size_t)H.slab_blocks * H.slab_floats * sizeof(float));
+  if (!H.slab) return nmx_fail(NMX_E_NOMEM, "Hilbert slab allocation failed");
+  H.w500_tab = nullptr;
+  H.w1000_tab = nullptr;
+  P.bursts.hil_kind = NMX_HIL_LONG;
+  return 0;
+}
+
 // the stand-alone Hilbert kernel of a bank that leaves its burst bands as series (build_bank calls this)
 int build_hilbert(Plan& P) {
   const nmx_plan_desc& d = P.d;
   NmxHilbertArgs& H = P.bursts.hil;
   H.W = d.window;
   H.hil_full = d.window & 1;
+  // (the layouts below: 2 x al4(2 W) floats for an odd window, 2 x al4(W + 2) + al4(W) for an even one)
+  if ((size_t)(H.hil_full ? 2 * al4(2 * d.window) : 2 * al4(d.window + 2) + al4(d.window)) * 4 > 160 * 1024)
+    return build_hilbert_long(P);
   int rc;
   if ((rc = build_fft(P, H.hil_full ? d.window : d.window / 2, &H.hil_r, true))) return rc;
   if ((rc = build_fft(P, d.window, &H.hil_c, true))) return rc;
@@ -97,10 +184,9 @@ int build_bursts(Plan& P) {
   T.n_bands = d.n_burst_bands;
   T.W = d.window;
   T.q = d.burst_threshold / 100.0;
-  NMX_REQUIRE(T.q >= 0.0 && T.q <= 1.0, "burst threshold must be a percentile in [0, 100]");
-  NMX_REQUIRE(d.sfreq * d.burst_time_duration_s < 2147483647.0, "burst ring buffer (sfreq x time_duration_s) too long");
-  T.n_ring = (int)(d.sfreq * d.burst_time_duration_s);
-  NMX_REQUIRE(T.n_ring >= 2, "burst ring buffer too short");
+  // (before anything of the chain is allocated: the state alone is n_channels x n_burst_bands x K floats)
+  int rc_hist;
+  if ((rc_hist = burst_history(d, &T.n_ring, &T.K))) return rc_hist;
   const double seg_s = d.segment_length_s > 0 ? d.segment_length_s : (double)d.window / d.sfreq;  // segment_length_features_ms / 1000
   T.overlap = (int)(d.sfreq * seg_s / d.feat_hz);
   // samples_overlap = 0 (30 kHz, 17 ms windows at a 1 kHz feature rate: int(0.51)): the reference's slice
@@ -109,13 +195,6 @@ int build_bursts(Plan& P) {
   // filtered_data[:, :, -1600:] of a 1000-sample array is the whole window as well
   if (T.overlap == 0 || T.overlap > d.window) T.overlap = d.window;
   NMX_REQUIRE(T.overlap >= 1 && T.overlap <= d.window, "burst overlap (sfreq * seg_s / feat_hz) out of range");
-  T.K = (int)std::floor((1.0 - T.q) * (double)(T.n_ring - 1)) + 2;
-  T.K = std::min(T.K, T.n_ring);
-  // (before anything of the chain is allocated: the state alone is n_channels x n_burst_bands x K floats)
-  if (T.K > NMX_THR_K_MAX)
-    return nmx_fail(NMX_E_INVALID, "burst threshold history too long: floor((1 - threshold / 100) x (int(sfreq x time_duration_s) - 1)) + 2 = " +
-                    std::to_string(T.K) + " top-K list entries, the limit is 1 048 576 (bursts_settings.threshold, "
-                    "bursts_settings.time_duration_s and the sampling rate the bursts see)");
   int p2 = 1;
   while (p2 < std::max(std::max(d.window, T.overlap) + 4, 1024)) p2 <<= 1;   // >= NMX_THR_P (flush staging)
   // (the three arrays are only indexed, never sorted as a network: a plan of the tiled kernel takes them as long as they have to be --
@@ -125,15 +204,25 @@ int build_bursts(Plan& P) {
   // NMX_THR_LIST_GLOBAL=1: the sorted top-K list is not copied to LDS (workgroups of ~20 KB instead of
   // ~50 KB leave room for the kernels that run next to the walk); every list access then goes to L2
   // It is also the fallback when the list does not fit (2 kHz x 30 s at the 50th percentile: 30 001 entries).
-  T.list_in_global = env_int("NMX_THR_LIST_GLOBAL", 0);
-  for (int pass = 0; pass < 2; ++pass) {
-    T.off_l0 = 0;
-    T.off_l1 = 0;                          // (single list: the merge is in place)
-    T.off_p = T.list_in_global ? 0 : al4(T.K);   // pc[P2], ps[P2], ins[P2]
-    T.off_red = T.off_p + 3 * p2 + 2 * 512 + 1024 + 8;   // + fringe x2, pending list, counters
-    T.lds_floats = T.off_red + 64;
-    if (T.lds_floats * 4 <= 160 * 1024 || T.list_in_global) break;
-    T.list_in_global = 1;
+  T.stage_tile = 0;
+  auto walk_layout = [&]() {
+    T.list_in_global = env_int("NMX_THR_LIST_GLOBAL", 0);
+    for (int pass = 0; pass < 2; ++pass) {
+      T.off_l0 = 0;
+      T.off_l1 = 0;                          // (single list: the merge is in place)
+      T.off_p = T.list_in_global ? 0 : al4(T.K);   // pc[P2], ps[P2], ins[P2]
+      T.off_red = T.off_p + 3 * T.P2 + 2 * 512 + 1024 + 8;   // + fringe x2, pending list, counters
+      T.lds_floats = T.off_red + 64;
+      if ((size_t)T.lds_floats * 4 <= 160 * 1024 || T.list_in_global) break;
+      T.list_in_global = 1;
+    }
+  };
+  walk_layout();
+  // Staging arrays for a whole hop that do not fit even with the list in global memory (windows above 8 188 samples, 12 900 with
+  // the tiled merge): arrays of NMX_THR_STAGE_TILE samples, and a longer hop is absorbed tile by tile (nmx_burst_thr_walk)
+  if ((size_t)T.lds_floats * 4 > 160 * 1024) {
+    T.P2 = T.stage_tile = NMX_THR_STAGE_TILE;
+    walk_layout();
   }
   // the workgroup walk's kernel (be_launch_burst_thr): a thread's share of the list in registers -- 128 entries x 256 threads, 64 x
   // 1024 in nmx_kern_burst_thr_wide --, beyond 65 536 entries the tiled merge of nmx_kern_burst_thr_tiled
@@ -151,7 +240,11 @@ int build_bursts(Plan& P) {
   S.out_mask = d.burst_out_mask;
   S.cols = cv(d.burst_cols);
   S.off_e = 0;
-  S.off_red = al4(d.window + d.window / 16 + 1);   // padded series (NMX_EP)
+  // the series in LDS, padded (NMX_EP) -- beyond 16 384 samples one tile of it: more than 69 KB of LDS per wave leaves a CU two
+  // waves, and from ~38 500 samples on the series does not fit at all
+  S.scan_tile = d.window > 16384 ? NMX_BSTAT_TILE : 0;
+  const int n_lds = S.scan_tile ? S.scan_tile : d.window;
+  S.off_red = al4(n_lds + n_lds / 16 + 1);
   S.lds_floats = S.off_red + 64;
   const size_t n_state = (size_t)d.n_channels * d.n_burst_bands;
   B.top_bytes = n_state * T.K * sizeof(float);
@@ -172,7 +265,7 @@ int build_bursts(Plan& P) {
   B.sparse_count = sparse == 2;
 #endif
   B.walk = nmx_burst_walk_plan(T, env_int("NMX_THR_FILL", 1) != 0, wave, env_int("NMX_THR_LIST_LDS", 1) != 0);
-  B.stat_kind = (d.window & 3) || d.window > 2048 ? NMX_BSTAT_GENERIC
+  B.stat_kind = S.scan_tile ? NMX_BSTAT_SCAN : (d.window & 3) || d.window > 2048 ? NMX_BSTAT_GENERIC
                 : d.window <= 1024 ? (B.sparse ? NMX_BSTAT_REG16_SPARSE : NMX_BSTAT_REG16)
                                    : (B.sparse ? NMX_BSTAT_REG32_SPARSE : NMX_BSTAT_REG32);
   P.have_bursts = true;

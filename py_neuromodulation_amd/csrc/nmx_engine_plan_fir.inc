@@ -299,13 +299,14 @@ int bank_partitioned_setup(Plan& P, NmxBankArgs& A, const std::vector<const doub
   A.M = 0;
   A.off_X = 0;
   A.partitioned = 1;
+  // (blocks of 128 samples only where 256 do not fit beside the window: from 39 873 samples on)
   int B = 2048;
-  while (B > 256 && (size_t)(al4(A.W) + 2 * al4(2 * B) + 64) * 4 > 160 * 1024) B >>= 1;
+  while (B > 128 && (size_t)(al4(A.W) + 2 * al4(2 * B) + 64) * 4 > 160 * 1024) B >>= 1;
   A.off_a = al4(A.W);
   A.off_b = A.off_a + al4(2 * B);
   A.off_red = A.off_b + al4(2 * B);
   A.lds_floats = A.off_red + 64;
-  NMX_REQUIRE((size_t)A.lds_floats * 4 <= 160 * 1024, "window too long for the partitioned FIR kernel (> 40 000 samples)");
+  NMX_REQUIRE((size_t)A.lds_floats * 4 <= 160 * 1024, "window too long for the partitioned FIR kernel (> 40 384 samples)");
   int hm = 0;
   for (int i = 0; i < A.n_filters; ++i) hm = std::max(hm, A.f[i].half);
   A.ups_B = B;

@@ -215,6 +215,16 @@ static ChunkSizes batch_chunk_sizes(const Plan& P, bool host) {
   z.host_first = std::min<int64_t>(z.host_big, P.host_first_chunk);
   if (host && P.have_bursts)   // a fresh stream: the whole fill phase of the burst history in ONE sort (nmx_k_burst_fill.h)
     z.host_first = std::max<int64_t>(z.host_first, P.bursts.fill_hops((int)z.host_big));
+  // Long windows: the bursts chain's hand-off buffers -- the band series and the envelope of both chunk parities, hops x
+  // channels x bands x window floats each -- bound the chunk (256 channels x 3 bands x 40 000 samples are 123 MB per hop and
+  // buffer): as many hops as fit NMX_BURST_HANDOFF_MB together, never fewer than one.  Plans up to 16 384 samples keep theirs.
+  if (P.have_bursts && P.d.window > 16384) {
+    const double per_hop = 3.0 * P.d.n_channels * P.d.n_burst_bands * (double)P.d.window * sizeof(float);
+    const int64_t cap = std::max<int64_t>(1, (int64_t)((double)P.burst_handoff_mb * 1048576.0 / per_hop));
+    z.dev_chunk = std::min(z.dev_chunk, cap);
+    z.host_big = std::min(z.host_big, cap);
+    z.host_first = std::min(z.host_first, cap);
+  }
   return z;
 }
 
@@ -313,7 +323,8 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
   int64_t prev_w0 = -1, prev_nw = 0;
   int k = 0, last_par = -1;
   P.pipe_marks.clear();
-  P.pipe_marks.reserve((size_t)(n_windows / std::max<int64_t>(1, std::min<int64_t>(P.host_first_chunk, P.chunk_windows)) + 8));
+  P.pipe_marks.reserve((size_t)(n_windows / std::max<int64_t>(1, std::min<int64_t>({P.host_first_chunk, P.chunk_windows, sizes.dev_chunk,
+                                                                                    sizes.host_first, sizes.host_big})) + 8));
   // an error in mid-batch leaves work in flight: host callbacks holding pointers into P.pipe_marks, copies into the caller's
   // out / mask.  Nothing returns to the caller -- who may free those buffers, or start the next batch, whose
   // pipe_marks.clear() + reserve() may move the marks -- before the batch's streams have drained.

@@ -816,9 +816,19 @@ struct NmxHilbertArgs {
   const float* floor;      // [n_seq]
   unsigned char* full;     // [n_items]
   int n_seq, overlap;
+  // long series (NMX_HIL_LONG, nmx_k_hilbert_long.h; 0 / NULL elsewhere): W = split_d x sub_m, hil_c then is the complex
+  // transform of sub_m points (hil_r is not used), [off_a, off_b + 2 sub_m) its two LDS buffers, tw_n the W-th roots of unity
+  int long_mode, split_d, sub_m;
+  const float2* tw_n;      // [W] exp(-2 pi i j / W), float64 on the host
+  int slab_floats;         // floats per slab: the one-sided spectrum, (W + 1) / 2 complex
+  int slab_blocks;         // slabs allocated = resident workgroups of the persistent kernel
+  float* slab;             // [slab_blocks][slab_floats] device memory owned by the plan (the emulator runs on slab 0)
 };
 
+NMX_DEV void nmx_hilbert_long_item(const NmxHilbertArgs& A, long long item, float* smem, float* slab);
+
 NMX_DEV void nmx_hilbert_item(const NmxHilbertArgs& A, long long item, float* smem) {
+  if (A.long_mode) { nmx_hilbert_long_item(A, item, smem, A.slab); return; }
   float2* bufA = (float2*)(smem + A.off_a);
   float2* bufB = (float2*)(smem + A.off_b);
   const int W = A.W, Wh = W >> 1;
@@ -970,3 +980,5 @@ NMX_DEV void nmx_hilbert_w1000_item(const NmxHilbertArgs& A, long long item, flo
   }
 }
 #endif
+
+#include "nmx_k_hilbert_long.h"

@@ -36,8 +36,10 @@ struct NmxBurstThrArgs {
   int n_ring;           // int(sfreq * time_duration_s)
   int overlap;          // samples appended per window after the first (bursts.py:81-85)
   double q;             // threshold / 100
-  int P2;               // length of pc / ps / ins: >= max(W, overlap) + 4 and >= NMX_THR_P (a power of two where K <= NMX_THR_REG_MAX)
+  int P2;               // length of pc / ps / ins: >= max(W, overlap) + 4 (or = stage_tile) and >= NMX_THR_P (a power of two where K <= NMX_THR_REG_MAX)
   int off_l0, off_l1, off_p, off_red, lds_floats;
+  int stage_tile;       // 0: a hop's new samples are staged at once.  > 0 (= P2; plans whose 3 x P2 for a whole hop does not fit
+                        // LDS): a hop that brings more is absorbed in tiles of this many samples (nmx_burst_thr_walk)
   int list_in_global;   // the top-K list stays in its global (L2-resident) state array, LDS holds only the working sets
   // [C][Bb] or nullptr.  A walk that ends with the ring full leaves here the lower of the two order statistics its threshold
   // interpolates between, a = desc[ia] = s[lo] (b = desc[ia - 1] = s[lo + 1] >= a).  It bounds every LATER threshold of the
@@ -252,6 +254,7 @@ NMX_DEV float nmx_lerp_thr(double a, double b, double frac, bool have_b) {
 #define NMX_THR_F 512     // capacity of the sorted low fringe
 #define NMX_THR_FREFILL 384
 #define NMX_THR_P 1024    // capacity of the pending (unsorted) list
+#define NMX_THR_STAGE_TILE 4096   // staging arrays of a plan whose whole hop does not fit LDS (NmxBurstThrArgs::stage_tile)
 
 // Threshold walk of one (channel, band) over the hops of a batch.
 //
@@ -312,12 +315,18 @@ NMX_DEV void nmx_burst_thr_walk(const NmxBurstThrArgs& A, int c, int bi, float* 
     const int n_new = (nwin == 0) ? W : A.overlap;
     const int n4 = (n_new + 3) & ~3;
     const float* e = A.env + (((long long)w * A.n_channels + c) * A.n_bands + bi) * W + (W - n_new);
-    if (have_pre) {
-      if (NMX_TID < n_new) pc[NMX_TID] = pre;
-    } else {
-      for (int i = NMX_TID; i < n_new; i += NMX_NT) pc[i] = e[i];
+    // a hop longer than the staging arrays (A.stage_tile) is staged tile by tile below: the first hop of a stream, and every
+    // hop of a plan whose overlap exceeds the tile (feature rates below ~W / 4096 per second), on a full ring as well.  Such a
+    // hop is never a steady one (the steady regime takes hops of at most 256 samples), so the tiles are only needed there.
+    const bool in_tiles = A.stage_tile > 0 && n_new > A.stage_tile;
+    if (!in_tiles) {
+      if (have_pre) {
+        if (NMX_TID < n_new) pc[NMX_TID] = pre;
+      } else {
+        for (int i = NMX_TID; i < n_new; i += NMX_NT) pc[i] = e[i];
+      }
+      for (int i = n_new + NMX_TID; i < n4; i += NMX_NT) pc[i] = -INFINITY;
     }
-    for (int i = n_new + NMX_TID; i < n4; i += NMX_NT) pc[i] = -INFINITY;
     have_pre = false;
     if (can_prefetch && w + 1 < A.n_windows) {
       const float* en = A.env + (((long long)(w + 1) * A.n_channels + c) * A.n_bands + bi) * W + (W - A.overlap);
@@ -339,9 +348,25 @@ NMX_DEV void nmx_burst_thr_walk(const NmxBurstThrArgs& A, int c, int bi, float* 
     if (NMX_TID == 0) { cnts[0] = 0; cnts[1] = 0; cnts[2] = 0; }
     NMX_SYNC();
     if (!steady) {
-      nmx_rank_sort_desc(pc, n_new, ps);
-      NMX_SYNC();
-      len = TILED ? nmx_merge_into_tiled(L, len, K, ps, ins, n_new) : nmx_merge_into<CH>(L, len, K, ps, ins, n_new, vals);
+      if (in_tiles) {
+        // Exact whatever the state of the ring: every merge truncates to K, and the top K of a multiset does not depend on
+        // the order its members were merged in (equal floats are indistinguishable).  The threshold is read once, behind
+        // the last tile.
+        for (int t0 = 0; t0 < n_new; t0 += A.stage_tile) {
+          const int nt = (n_new - t0) < A.stage_tile ? (n_new - t0) : A.stage_tile;
+          NMX_SYNC();   // (a merge that returns early has no barrier behind its last read)
+          for (int i = NMX_TID; i < nt; i += NMX_NT) pc[i] = e[t0 + i];
+          for (int i = nt + NMX_TID; i < ((nt + 3) & ~3); i += NMX_NT) pc[i] = -INFINITY;
+          NMX_SYNC();
+          nmx_rank_sort_desc(pc, nt, ps);
+          NMX_SYNC();
+          len = TILED ? nmx_merge_into_tiled(L, len, K, ps, ins, nt) : nmx_merge_into<CH>(L, len, K, ps, ins, nt, vals);
+        }
+      } else {
+        nmx_rank_sort_desc(pc, n_new, ps);
+        NMX_SYNC();
+        len = TILED ? nmx_merge_into_tiled(L, len, K, ps, ins, n_new) : nmx_merge_into<CH>(L, len, K, ps, ins, n_new, vals);
+      }
       total += n_new;
       nwin += 1;
       if (NMX_TID == 0) {
@@ -951,6 +976,8 @@ struct NmxBurstStatArgs {
   int off_e, off_red, lds_floats;
   const unsigned char* full;   // [n_windows][C][Bb] or nullptr (every row is whole): 0 = the Hilbert kernel found no sample of the
                                // row at or above a lower bound of its threshold and stored only the row's tail
+  int scan_tile;               // > 0 (NMX_BSTAT_SCAN): the row is read from memory in tiles of this many samples, LDS holds one
+                               // tile (nmx_burst_stat_scan_item); 0: the whole row in LDS
 };
 
 // A row without a sample >= thr: no run, no transition, nothing above -- the six statistics below are +0.f each (dmean =
@@ -1024,8 +1051,128 @@ NMX_DEV void nmx_wave_excl_latest(int& pos, double& val) {
 
 #define NMX_EP(i) ((i) + ((i) >> 4))
 
+#define NMX_BSTAT_TILE 2048   // samples per tile of the scan form (a wave's LDS slice: 9 KB)
+
+// the value lane 63 holds (the emulator's one thread is the wave)
+#ifdef NMX_HOST_EMU
+NMX_DEV int nmx_wave_last_i(int v) { return v; }
+NMX_DEV double nmx_wave_last_d(double v) { return v; }
+#else
+NMX_DEV int nmx_wave_last_i(int v) { return __builtin_amdgcn_readlane(v, 63); }
+NMX_DEV double nmx_wave_last_d(double v) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+#endif
+
+// nmx_burst_stat_item for a row that does not fit LDS (or need not occupy it): the same two passes over per-lane chunks,
+// tile by tile, the envelope re-read from memory.  What a tile hands to the next one is the state of the run scan at its
+// last sample: the prefix sum of the row so far, the position of the latest sample below the threshold and the prefix
+// there (an open run's length and sum are differences against them), and whether the last sample was above.  The counts,
+// the maxima and the sum of run means stay in the lanes' registers until the row ends.  A run that is still open at the
+// row's end is never closed: like nmx_burst_stat_item it counts for the duration mean but not for the mean of means.
+NMX_DEV void nmx_burst_stat_scan_item(const NmxBurstStatArgs& A, int w, int c, int bi, float* smem) {
+  float* e = smem + A.off_e;
+  float* red = smem + A.off_red;
+  const int W = A.W, TS = A.scan_tile;
+  const long long item = ((long long)w * A.n_channels + c) * A.n_bands + bi;
+  const float* src = A.env + item * W;
+  const float thr = A.thr[item];
+  int n_above = 0, n_trans = 0, n_valid = 0, max_len = 0;
+  double sum_means = 0.0;
+  float amax = 0.f;
+  // carried from tile to tile (wave-uniform)
+  double row_pre = 0.0;    // sum of the samples before the tile
+  int gz = -1;             // latest sample below the threshold before the tile
+  double gz_pre = 0.0;     // ... and the inclusive prefix there
+  bool gprev = false;      // the sample before the tile is at or above the threshold
+  for (int t0 = 0; t0 < W; t0 += TS) {
+    const int n = (W - t0) < TS ? (W - t0) : TS;
+    NMX_SYNC();   // (the previous tile's readers are done)
+    nmx_stage_row(src + t0, n, [=](int i, float v) { e[NMX_EP(i)] = v; });
+    NMX_SYNC();
+    const int chunk = (n + NMX_NT - 1) / NMX_NT;
+    const int i0 = NMX_TID * chunk, i1 = (i0 + chunk) < n ? (i0 + chunk) : n;
+    // pass 1: chunk sum, last below-threshold position in the chunk and the prefix there
+    double csum = 0.0;
+    int zpos = -1;
+    double zpre = 0.0;
+    for (int i = i0; i < i1; ++i) {
+      const float ev = e[NMX_EP(i)];
+      csum += (double)ev;
+      if (!(ev >= thr)) { zpos = t0 + i; zpre = csum; }
+    }
+    double total;
+    const double base = row_pre + nmx_wave_excl_sum_d(csum, &total);
+    int carry_z = zpos;
+    double carry_p = zpos < 0 ? 0.0 : zpre + base;
+    nmx_wave_excl_latest(carry_z, carry_p);   // latest zero of the tile before my chunk
+    if (carry_z < 0) { carry_z = gz; carry_p = gz_pre; }   // none: the one before the tile
+    // pass 2
+    double pre = base;
+    int lastz = carry_z;
+    double lastz_pre = carry_p;
+    bool prev = i0 > 0 ? (i0 < n ? (e[NMX_EP(i0 - 1)] >= thr) : false) : gprev;
+    for (int i = i0; i < i1; ++i) {
+      const float v = e[NMX_EP(i)];
+      const bool b = v >= thr;
+      if (b != prev) ++n_trans;
+      if (b) {
+        ++n_above;
+        amax = v > amax ? v : amax;
+      } else {
+        if (prev) {   // a run [lastz + 1, t0 + i - 1] just finished -> valid run
+          const int len = t0 + i - 1 - lastz;
+          const double rs = pre - lastz_pre;
+          sum_means += rs / (double)len;
+          ++n_valid;
+          max_len = len > max_len ? len : max_len;
+        }
+        lastz = t0 + i;
+      }
+      pre += (double)v;
+      if (!b) lastz_pre = pre;
+      prev = b;
+    }
+    // the state behind the tile's last sample: the last lane's view after its chunk (an empty chunk passes on what the
+    // lanes before it left)
+    gz = nmx_wave_last_i(lastz);
+    gz_pre = nmx_wave_last_d(lastz_pre);
+    gprev = e[NMX_EP(n - 1)] >= thr;
+    row_pre += total;
+  }
+  n_above = nmx_block_sum_i(n_above, red);
+  n_trans = nmx_block_sum_i(n_trans, red);
+  n_valid = nmx_block_sum_i(n_valid, red);
+  max_len = (int)nmx_block_max((float)max_len, red);
+  amax = nmx_block_max(amax, red);
+  const float hi = (float)sum_means;
+  const float lo = (float)(sum_means - (double)hi);
+  const double sm = (double)nmx_block_sum(hi, red) + (double)nmx_block_sum(lo, red);
+  if (NMX_TID == 0) {
+    const int num_bursts = n_trans / 2;
+    const float dmean = num_bursts ? ((float)n_above / (float)num_bursts) / A.sfreq : 0.f;
+    float vals[6];
+    vals[0] = dmean;
+    vals[1] = (float)max_len / A.sfreq;
+    vals[2] = n_valid ? (float)(sm / (double)n_valid) : 0.f;
+    vals[3] = amax;
+    vals[4] = dmean / A.seg_s;
+    vals[5] = gprev ? 1.f : 0.f;
+    float* row = A.out + (long long)w * A.n_outputs;
+    int col = A.cols.base + c * A.cols.ch_stride + bi * A.cols.a_stride;
+    for (int s = 0; s < 6; ++s)
+      if (A.out_mask & (1u << s)) {
+        row[col] = vals[s];
+        col += A.cols.b_stride;
+      }
+  }
+}
+
 // one WAVE (64 threads) per (window, channel, band)
 NMX_DEV void nmx_burst_stat_item(const NmxBurstStatArgs& A, int w, int c, int bi, float* smem) {
+  if (A.scan_tile) { nmx_burst_stat_scan_item(A, w, c, bi, smem); return; }
   float* e = smem + A.off_e;
   float* red = smem + A.off_red;
   const int W = A.W;

@@ -62,6 +62,15 @@ __global__ void __launch_bounds__(256) nmx_kern_burst_stat_reg(const NmxBurstSta
   nmx_burst_stat_item_reg<CH, SPARSE>(A, r / A.n_channels, r % A.n_channels, bi);
 }
 
+// the tile scan (NmxBurstStatArgs::scan_tile): the envelope stays in memory, a wave's LDS slice holds one tile of it
+__global__ void __launch_bounds__(256) nmx_kern_burst_stat_scan(const NmxBurstStatArgs A, int n_items) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int item = blockIdx.x * 4 + wave;
+  if (item >= n_items) return;
+  const int bi = item % A.n_bands, r = item / A.n_bands;
+  nmx_burst_stat_scan_item(A, r / A.n_channels, r % A.n_channels, bi, nmx_smem_wave + wave * A.lds_floats);
+}
+
 __global__ void __launch_bounds__(256) nmx_kern_sharp(const NmxSharpArgs A, int n_items, int slice) {
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform -> SGPR
   const int item = blockIdx.x * (blockDim.x >> 6) + wave;
@@ -436,6 +445,7 @@ extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, NmxBurstSt
     case NMX_BSTAT_REG16: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<16>"); return;
     case NMX_BSTAT_REG32_SPARSE: hipLaunchKernelGGL((nmx_kern_burst_stat_reg<32, true>), grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg_sparse<32>"); return;
     case NMX_BSTAT_REG32: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<32>"); return;
+    case NMX_BSTAT_SCAN: hipLaunchKernelGGL(nmx_kern_burst_stat_scan, grid4, dim3(256), (size_t)A->lds_floats * 4 * 4, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_scan"); return;
     case NMX_BSTAT_GENERIC: break;
   }
   const int k = waves_per_wg(lds);
