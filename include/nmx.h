@@ -326,7 +326,10 @@ int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
  * (1..8 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
  * (template arguments included).  Which variant runs depends on the shape, the batch size and the tuning
  * knobs, so measurement code names the kernel from here instead of hard-coding it.  NUL-terminated,
- * truncated to n - 1 characters. */
+ * truncated to n - 1 characters.
+ * which = 9 is no stage: the launch geometry of the channel-pair FIR kernels of that launch sequence, whatever their
+ * stage, "<kernel>: <channel pairs> pairs, <workgroups> x <waves per workgroup> waves" joined by " + " (what the batch
+ * size made of the launch: small batches run two waves per workgroup). */
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n);
 
 /* ---- Feature normalisation over a batch of hops (processing/normalization.py:31-111,150-163) ----

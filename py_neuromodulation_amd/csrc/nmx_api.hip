@@ -154,11 +154,22 @@ __global__ void __launch_bounds__(256) nmx_kern_tap(const NmxTapArgs A) {
 // ---- which kernels ran (per stage of the launch sequence; stage indices = nmx_last_timing_ms) ----
 static thread_local int g_stage = 0;
 static thread_local std::string g_stage_kernels[16];
+static thread_local const char* g_last_kernel = "";
 extern "C" void nmxi_note_kernel(const char* name) {
+  g_last_kernel = name;
   std::string& s = g_stage_kernels[g_stage & 15];
   if (s.find(name) != std::string::npos) return;
   if (!s.empty()) s += " + ";
   s += name;
+}
+// launch geometry of the channel-pair FIR kernel just noted (nmx_w64.hip), whatever the stage: nmx_last_kernels(plan, 9)
+#define NMX_GEOM_SLOT 15
+extern "C" void nmxi_note_pair_geom(int n_pairs, int grid, int nw) {
+  std::string& s = g_stage_kernels[NMX_GEOM_SLOT];
+  const std::string e = std::string(g_last_kernel) + ": " + std::to_string(n_pairs) + " pairs, " + std::to_string(grid) + " x " + std::to_string(nw) + " waves";
+  if (s.find(e) != std::string::npos) return;
+  if (!s.empty()) s += " + ";
+  s += e;
 }
 static void be_stage(int st) { g_stage = st; }
 static void be_stage_reset() { for (auto& s : g_stage_kernels) s.clear(); }

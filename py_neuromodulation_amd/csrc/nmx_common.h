@@ -78,6 +78,9 @@ static inline float2 make_float2(float x, float y) { return float2{x, y}; }
 // nmxi_note_kernel: every launcher records the kernel it actually launched (name as rocprofv3 prints it)
 // under the current stage; nmx_last_kernels() reports them (bench.py's roofline names the kernel from here).
 extern "C" void nmxi_note_kernel(const char* name);
+// nmxi_note_pair_geom: behind nmxi_note_kernel, the channel-pair FIR launchers also record what the batch size made of that
+// launch (channel pairs, workgroups x waves per workgroup); nmx_last_kernels(plan, 9) reports it
+extern "C" void nmxi_note_pair_geom(int n_pairs, int grid, int nw);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE opt-in: true the first time the calling
 // site runs on the current device (`seen` = a static bitmask of device ordinals owned by the call site)
 static inline bool nmx_first_on_device(unsigned long long& seen) {

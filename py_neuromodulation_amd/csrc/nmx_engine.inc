@@ -269,6 +269,7 @@ struct Plan {
   int w_in = 0;           // samples per incoming window (raw_window when resampling, else window)
   be_timer_t timers[ST_COUNT];
   std::string kernels[ST_COUNT];   // kernels of the first chunk of the last batch, per stage (nmx_last_kernels)
+  std::string pair_geom;           // ... and the launch geometry of its channel-pair FIR kernels (nmx_last_kernels 9)
   nmx_norm* norm = nullptr; // attached feature normaliser (not owned): applied to every chunk's rows on the device
   nmx_proj* proj = nullptr; // attached grid projection (not owned): behind the normaliser, on the same stream
   // offset split (nmx_engine_dc.inc): x = u + d per input row, the constants carried in float64 on the host

@@ -137,7 +137,10 @@ static int run_chunk(Plan& P, const BatchSched& b, const float* d_x, long long l
   if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
   P.sched.end_main(b);
   be_stage(ST_BATCH);
-  if (timed) for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (the projection's: chunk_finalize)
+  if (timed) {
+    for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (the projection's: chunk_finalize)
+    P.pair_geom = be_stage_kernels(15);   // (NMX_GEOM_SLOT: the channel-pair FIR launches of this chunk)
+  }
   return be_check_launch();
 }
 
@@ -465,6 +468,7 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   if ((rc = run_prep_stages(P, v, 1, s))) return rc;
   be_stage(ST_BATCH);
   for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
+  P.pair_geom = be_stage_kernels(15);
   be_d2h_async(yf.data(), v.x, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
@@ -504,6 +508,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
   be_stage(ST_BATCH);
   for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
+  P.pair_geom = be_stage_kernels(15);
   be_d2h_async(yf.data(), P.sharp.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];
@@ -638,8 +643,8 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
-  if (!P || !buf || n < 1 || which < ST_PREP || which >= ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
-  std::string k = P->kernels[which];
+  if (!P || !buf || n < 1 || which < ST_PREP || which > ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
+  std::string k = which == ST_COUNT ? P->pair_geom : P->kernels[which];   // (9: no stage, the pair kernels' launch geometry)
   if (which == ST_BURSTS && P->bursts.sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
     k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->bursts.env_tail_rows) + "/" + std::to_string(P->bursts.env_rows);
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);

@@ -20,18 +20,26 @@
 // traffic, a twelfth of the table traffic: ~1 900 instead of ~3 400 VALU instructions.
 //
 // CDNA4 mapping: 24 complex points per lane, three register passes (radix 24 = 3 x 8, 8, 8) and two exchanges
-// through one 13.5 KiB LDS tile per wave.  Forward = decimation in frequency (passes A, B, C), inverse = the
+// through one 4.5 KiB LDS tile per wave.  Forward = decimation in frequency (passes A, B, C), inverse = the
 // mirror image (C', B', A'): the spectrum is consumed in the order the forward transform leaves it, and the series
 // comes out in natural order (sample l + 64 j in register j of lane l: lane-consecutive stores, the W..M tail in
 // registers that are never formed).  tools/model_w64c.py is the lane / register model of the index maps and
 // proves every exchange access bank-conflict free per 32-lane half.
 //   n = l + 64 j,  k = ka + 24 (qa + 8 qb),  ka = u + 8 g,  lane = l_lo + 8 u (passes A, B) or qa + 8 u (pass C)
-//   P1: tile[ka(reg) 72 + l]                     A writes / A' reads      (reg 8 r + p holds ka = 3 p + r)
-//   P2: tile[u 72 + l_lo + 576 g + 8 i]          B reads  / B' writes     (reg 8 g + i, i = l_hi)
-//   P3: tile[u 72 + l_lo + 576 g + 9 i]          B writes / B' reads      (i = qa)
-//   P4: tile[u 72 + 9 (lane & 7) + 576 g + i]    C reads  / C' writes     (i = l_lo)
+//   P1: tile[(ka(reg) & 7) 72 + l]               A writes / A' reads      (reg 8 r + p holds ka = 3 p + r)
+//   P2: tile[u 72 + l_lo + 8 i]                  B reads  / B' writes     (reg 8 g + i, i = l_hi)
+//   P3: tile[u 72 + l_lo + 9 i]                  B writes / B' reads      (i = qa)
+//   P4: tile[u 72 + 9 (lane & 7) + i]            C reads  / C' writes     (i = l_lo)
+// The tile holds ONE row group (8 rows of 72 points), not the transform's 24 rows: registers 8 g .. 8 g + 7 of P2 .. P4
+// touch rows 8 g .. 8 g + 7 only, and every block of eight rows of P1 is written by eight known registers, so each
+// exchange runs as three rounds "write the eight registers of rows 8 g .. 8 g + 7, read group g" through the same rows.
+// A wave's LDS operations execute in issue order: all rounds are in flight at once, nothing is serialised, and a round
+// overwrites the rows behind the previous round's reads.  8 rows = 1152 words = 18 x 64 banks: the bank of every access is
+// that of the 24-row layout.  tests/test_w64_group_exchange_model.py is the model of the rounds (delivery, bounds, banks,
+// write-after-read order).
 // LDS per workgroup: H of every filter in register order (6 KiB each), exp(-2 pi i l ka / 1536) (12 KiB), one tile
-// per wave -- 156 KiB for six filters and eight waves.  All tile and table accesses are volatile 8-byte LDS
+// per wave -- 102 KiB for six filters and twelve waves (three per SIMD at 167 VGPRs; the whole-transform tile of
+// 13.5 KiB held it to eight).  All tile and table accesses are volatile 8-byte LDS
 // operations (unpaired; see nmx_device.h), in program order, so no fences are needed inside a wave.
 // Device only; W <= 1024, activity-only band power, every filter with W + (L - 1) / 2 <= 1536.
 #pragma once
@@ -39,7 +47,9 @@
 #include "nmx_k_bank_w64.h"
 
 #define NMX_W64C_M 1536
-#define NMX_W64C_TILE_FLOATS (2 * 24 * 72)        // one exchange tile (complex points: 24 rows of 64 + 8 pad)
+#define NMX_W64_GROUP_TILE_FLOATS (2 * 8 * 72)     // one exchange tile: ONE row group (complex points: 8 rows of 64 + 8 pad)
+#define NMX_W64C_TILE_FLOATS NMX_W64_GROUP_TILE_FLOATS
+#define NMX_W64C_ADMIT_TILE_FLOATS (2 * 24 * 72)  // the whole-transform tile (24 rows) the admitted filter counts were set with
 #define NMX_W64C_TWA_FLOATS (2 * 24 * 64)         // exp(-2 pi i l ka(reg) / 1536), [reg][lane]
 #define NMX_W64C_TWB_FLOATS (2 * 8 * 8)           // exp(-2 pi i a b / 64), [a][b]
 #define NMX_W64C_H_FLOATS 1536                    // per filter: [12][64] pairs (H[k(lane, 2 i)], H[k(lane, 2 i + 1)])
@@ -49,10 +59,12 @@
 static inline bool nmx_w64_pair_shape_ok(const NmxBankArgs& b) { return b.W <= 1024 && !(b.bp_features & 6u); }
 // exchange tiles (= waves) that fit a workgroup's LDS next to `fixed` floats of tables
 static inline int nmx_w64_pair_waves(int fixed, int tile) { return (NMX_W64_LDS_FLOATS - fixed) / tile; }
-// M = 1536: the filters' spectra and the pass-A twiddles; at least six waves per workgroup
+// M = 1536: the filters' spectra and the pass-A twiddles.  The admitted filter counts are those that left six waves a
+// 24-row tile each (at most eight filters): which shapes take this kernel did not move when the tile shrank to one row group
+// (tests/fir_kernel_choice_cases.py pins it)
 static inline int nmx_w64c_fixed(int n_filters) { return n_filters * NMX_W64C_H_FLOATS + NMX_W64C_TWA_FLOATS; }
 static inline bool nmx_w64c_fits(int n_filters) {
-  return n_filters >= 1 && nmx_w64_pair_waves(nmx_w64c_fixed(n_filters), NMX_W64C_TILE_FLOATS) >= 6;
+  return n_filters >= 1 && nmx_w64_pair_waves(nmx_w64c_fixed(n_filters), NMX_W64C_ADMIT_TILE_FLOATS) >= 6;
 }
 
 #if !defined(NMX_HOST_EMU) && defined(NMX_LDS_ASM)
@@ -171,21 +183,51 @@ NMX_DEV void nmx_dft24_inv(nmx_c2* v) {
   nmx_dft24_inv_col<4>(v); nmx_dft24_inv_col<5>(v); nmx_dft24_inv_col<6>(v); nmx_dft24_inv_col<7>(v);
 }
 
-// ---- exchange patterns: byte offsets of register I relative to the lane's base address --------------------------
-constexpr int nmx_w64c_p1(int i) { return 8 * 72 * (3 * (i & 7) + (i >> 3)); }
-constexpr int nmx_w64c_p2(int i) { return 8 * (576 * (i >> 3) + 8 * (i & 7)); }
-constexpr int nmx_w64c_p3(int i) { return 8 * (576 * (i >> 3) + 9 * (i & 7)); }
-constexpr int nmx_w64c_p4(int i) { return 8 * (576 * (i >> 3) + (i & 7)); }
-template <int... I> NMX_DEV void nmx_w64c_rd1(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64c_p1(I)>(a)), ...); }
-template <int... I> NMX_DEV void nmx_w64c_rd2(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64c_p2(I)>(a)), ...); }
-template <int... I> NMX_DEV void nmx_w64c_rd3(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64c_p3(I)>(a)), ...); }
-template <int... I> NMX_DEV void nmx_w64c_rd4(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64c_p4(I)>(a)), ...); }
-template <int... I> NMX_DEV void nmx_w64c_wr1(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64c_p1(I)>(a, v[I]), ...); }
-template <int... I> NMX_DEV void nmx_w64c_wr2(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64c_p2(I)>(a, v[I]), ...); }
-template <int... I> NMX_DEV void nmx_w64c_wr3(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64c_p3(I)>(a, v[I]), ...); }
-template <int... I> NMX_DEV void nmx_w64c_wr4(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64c_p4(I)>(a, v[I]), ...); }
+// ---- exchange patterns: byte offsets of register I relative to the lane's base address, inside the 8-row tile ----
+// (G = 3: this transform, G = 4: the M = 2048 sibling, nmx_k_bank_w64e.h).  Register I of P2 .. P4 belongs to row group
+// I >> 3, register I of P1 (pass-A order: k_a = G (I & 7) + (I >> 3)) to row group k_a >> 3; an exchange runs one row
+// group per round through the same eight rows.
+template <int G> constexpr int nmx_w64g_ka(int i) { return G * (i & 7) + (i >> 3); }
+template <int G> constexpr int nmx_w64g_p1(int i) { return 8 * 72 * (nmx_w64g_ka<G>(i) & 7); }
+constexpr int nmx_w64g_p2(int i) { return 8 * (8 * (i & 7)); }
+constexpr int nmx_w64g_p3(int i) { return 8 * (9 * (i & 7)); }
+constexpr int nmx_w64g_p4(int i) { return 8 * (i & 7); }
+// P1, round GRP: the eight registers whose rows are 8 GRP .. 8 GRP + 7
+template <int G, int GRP, int I> NMX_DEV void nmx_w64g_rd1_reg(nmx_c2* v, unsigned a) {
+  if constexpr ((nmx_w64g_ka<G>(I) >> 3) == GRP) v[I] = nmx_ds_read_b64<nmx_w64g_p1<G>(I)>(a);
+}
+template <int G, int GRP, int I> NMX_DEV void nmx_w64g_wr1_reg(const nmx_c2* v, unsigned a) {
+  if constexpr ((nmx_w64g_ka<G>(I) >> 3) == GRP) nmx_ds_write_b64<nmx_w64g_p1<G>(I)>(a, v[I]);
+}
+template <int G, int GRP, int... I> NMX_DEV void nmx_w64g_rd1(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_w64g_rd1_reg<G, GRP, I>(v, a), ...); }
+template <int G, int GRP, int... I> NMX_DEV void nmx_w64g_wr1(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_w64g_wr1_reg<G, GRP, I>(v, a), ...); }
+// P2 .. P4, one row group: v points at the group's eight registers
+template <int... I> NMX_DEV void nmx_w64g_rd2(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64g_p2(I)>(a)), ...); }
+template <int... I> NMX_DEV void nmx_w64g_rd3(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64g_p3(I)>(a)), ...); }
+template <int... I> NMX_DEV void nmx_w64g_rd4(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64g_p4(I)>(a)), ...); }
+template <int... I> NMX_DEV void nmx_w64g_wr2(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64g_p2(I)>(a, v[I]), ...); }
+template <int... I> NMX_DEV void nmx_w64g_wr3(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64g_p3(I)>(a, v[I]), ...); }
+template <int... I> NMX_DEV void nmx_w64g_wr4(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64g_p4(I)>(a, v[I]), ...); }
+#define NMX_W64G_SEQ8 std::make_integer_sequence<int, 8>{}
+// The four exchanges of a transform with G row groups, every LDS operation issued in one block (the caller fences): round
+// g writes its eight rows and reads them back in the next pass's pattern; a wave's LDS operations execute in issue order,
+// so round g + 1 overwrites the rows behind round g's reads with all rounds in flight.  The A <-> B exchanges read into a
+// second array: the registers a round's reads would land in may still hold values that a later round writes.
+template <int G, int... GRP> NMX_DEV void nmx_w64g_xch_ab(const nmx_c2* v, nmx_c2* b, unsigned a1, unsigned a2, std::integer_sequence<int, GRP...>) {
+  ((nmx_w64g_wr1<G, GRP>(v, a1, std::make_integer_sequence<int, 8 * G>{}), nmx_w64g_rd2(b + 8 * GRP, a2, NMX_W64G_SEQ8)), ...);
+}
+template <int G, int... GRP> NMX_DEV void nmx_w64g_xch_ba(const nmx_c2* v, nmx_c2* b, unsigned a1, unsigned a2, std::integer_sequence<int, GRP...>) {
+  ((nmx_w64g_wr2(v + 8 * GRP, a2, NMX_W64G_SEQ8), nmx_w64g_rd1<G, GRP>(b, a1, std::make_integer_sequence<int, 8 * G>{})), ...);
+}
+template <int... GRP> NMX_DEV void nmx_w64g_xch_bc(nmx_c2* v, unsigned a2, unsigned a4, std::integer_sequence<int, GRP...>) {
+  ((nmx_w64g_wr3(v + 8 * GRP, a2, NMX_W64G_SEQ8), nmx_w64g_rd4(v + 8 * GRP, a4, NMX_W64G_SEQ8)), ...);
+}
+template <int... GRP> NMX_DEV void nmx_w64g_xch_cb(nmx_c2* v, unsigned a2, unsigned a4, std::integer_sequence<int, GRP...>) {
+  ((nmx_w64g_wr4(v + 8 * GRP, a4, NMX_W64G_SEQ8), nmx_w64g_rd3(v + 8 * GRP, a2, NMX_W64G_SEQ8)), ...);
+}
 // table rows: register I of lane l at I * 512 + 8 l bytes
 template <int... I> NMX_DEV void nmx_w64c_rdt(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<512 * I>(a)), ...); }
+template <int I0, int... I> NMX_DEV void nmx_w64c_rdt8(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<512 * (I0 + I)>(a)), ...); }
 
 struct NmxW64cLane {   // per-lane constants of a wave, set up once per kernel
   unsigned a1, a2, a4;    // LDS byte addresses of the lane's base in patterns P1, P2 (= P3), P4
@@ -193,6 +235,7 @@ struct NmxW64cLane {   // per-lane constants of a wave, set up once per kernel
   nmx_c2 twb[8];          // exp(-2 pi i (lane & 7) q / 64), q = 0..7
 };
 #define NMX_W64C_SEQ24 std::make_integer_sequence<int, 24>{}
+#define NMX_W64C_SEQ3 std::make_integer_sequence<int, 3>{}
 
 // forward transform: v[j] = x[l + 64 j] (j < 16) -> v[8 g + qb] = X[u + 8 g + 24 ((lane & 7) + 8 qb)]
 NMX_DEV void nmx_w64c_forward(nmx_c2* v, const NmxW64cLane& Ln) {
@@ -205,19 +248,20 @@ NMX_DEV void nmx_w64c_forward(nmx_c2* v, const NmxW64cLane& Ln) {
   nmx_dft24_fwd(v);
   NMX_UNROLL
   for (int i = 1; i < 24; ++i) v[i] = nmx_cmul_tw<0>(v[i], w[i]);
-  nmx_w64c_wr1(v, Ln.a1, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd2(v, Ln.a2, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
+  {
+    nmx_c2 b[24];
+    nmx_w64g_xch_ab<3>(v, b, Ln.a1, Ln.a2, NMX_W64C_SEQ3);
+    NMX_SCHED_FENCE();
+    NMX_UNROLL
+    for (int i = 0; i < 24; ++i) v[i] = b[i];
+  }
   NMX_UNROLL
   for (int g = 0; g < 3; ++g) {
     nmx_dft8<-1>(v + 8 * g);
     NMX_UNROLL
     for (int q = 1; q < 8; ++q) v[8 * g + q] = nmx_cmul_tw<0>(v[8 * g + q], Ln.twb[q]);
   }
-  nmx_w64c_wr3(v, Ln.a2, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd4(v, Ln.a4, NMX_W64C_SEQ24);
+  nmx_w64g_xch_bc(v, Ln.a2, Ln.a4, NMX_W64C_SEQ3);
   NMX_SCHED_FENCE();
   NMX_UNROLL
   for (int g = 0; g < 3; ++g) nmx_dft8<-1>(v + 8 * g);
@@ -231,20 +275,26 @@ NMX_DEV void nmx_w64c_inverse(nmx_c2* v, const NmxW64cLane& Ln) {
     NMX_UNROLL
     for (int q = 1; q < 8; ++q) v[8 * g + q] = nmx_cmul_tw<1>(v[8 * g + q], Ln.twb[q]);
   }
-  nmx_w64c_wr4(v, Ln.a4, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd3(v, Ln.a2, NMX_W64C_SEQ24);
+  nmx_w64g_xch_cb(v, Ln.a2, Ln.a4, NMX_W64C_SEQ3);
   NMX_SCHED_FENCE();
   NMX_UNROLL
   for (int g = 0; g < 3; ++g) nmx_dft8<+1>(v + 8 * g);
-  nmx_w64c_wr2(v, Ln.a2, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
-  nmx_c2 w[24];
-  nmx_w64c_rd1(v, Ln.a1, NMX_W64C_SEQ24);
-  nmx_w64c_rdt(w, Ln.twa, NMX_W64C_SEQ24);
-  NMX_SCHED_FENCE();
-  NMX_UNROLL
-  for (int i = 1; i < 24; ++i) v[i] = nmx_cmul_tw<1>(v[i], w[i]);
+  {
+    nmx_c2 b[24];
+    nmx_w64g_xch_ba<3>(v, b, Ln.a1, Ln.a2, NMX_W64C_SEQ3);
+    // pass-A twiddles in three batches of eight behind the exchange (24 at once next to v[24] and the saved spectrum
+    // do not fit the 168 VGPRs of three waves per SIMD)
+    NMX_UNROLL
+    for (int k = 0; k < 3; ++k) {
+      nmx_c2 w[8];
+      if (k == 0) nmx_w64c_rdt8<0>(w, Ln.twa, NMX_W64G_SEQ8);
+      if (k == 1) nmx_w64c_rdt8<8>(w, Ln.twa, NMX_W64G_SEQ8);
+      if (k == 2) nmx_w64c_rdt8<16>(w, Ln.twa, NMX_W64G_SEQ8);
+      NMX_SCHED_FENCE();
+      NMX_UNROLL
+      for (int i = 0; i < 8; ++i) v[8 * k + i] = (8 * k + i) ? nmx_cmul_tw<1>(b[8 * k + i], w[i]) : b[0];
+    }
+  }
   nmx_dft24_inv(v);
 }
 

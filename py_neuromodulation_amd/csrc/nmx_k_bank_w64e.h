@@ -26,8 +26,9 @@
 // sample l + 64 j on the way in AND on the way out, no offset.  M >= W + 2 h keeps the two flanks apart.
 //
 // CDNA4 mapping: as nmx_k_bank_w64c.h with four groups of eight registers instead of three -- radix 32 (= 4 x 8), 8, 8,
-// decimation in frequency forward, the mirror image back, two exchanges through one 18 KiB tile per wave, the same
-// conflict-free patterns (tools/model_w64e.py is the lane / register model):
+// decimation in frequency forward, the mirror image back, two exchanges in four rounds through one 4.5 KiB tile per wave
+// (one row group: nmx_k_bank_w64c.h; the whole-transform tile was 18 KiB), the same conflict-free patterns
+// (tools/model_w64e.py is the lane / register model, tests/test_w64_group_exchange_model.py that of the rounds):
 //   n = l + 64 j,  k = ka + 32 (qa + 8 qb),  ka = u + 8 g;  pass-A register 8 r + p holds ka = 4 p + r.
 // Pruning: PAD = 0 reads 16 of the 32 input registers (W <= 1024), both modes form 16 of the 32 output registers.
 // Device only; W <= 1024, activity-only band power.
@@ -36,15 +37,17 @@
 #include "nmx_k_bank_w64c.h"
 
 #define NMX_W64E_M 2048
-#define NMX_W64E_TILE_FLOATS (2 * 32 * 72)        // one exchange tile (complex points: 32 rows of 64 + 8 pad)
+#define NMX_W64E_TILE_FLOATS NMX_W64_GROUP_TILE_FLOATS   // one exchange tile: one row group of 8 rows (nmx_k_bank_w64c.h)
+#define NMX_W64E_ADMIT_TILE_FLOATS (2 * 32 * 72)  // the whole-transform tile (32 rows) the admitted spectra counts were set with
 #define NMX_W64E_TWA_FLOATS (2 * 32 * 64)         // exp(-2 pi i l ka(reg) / 2048), [reg][lane]
 #define NMX_W64E_H_FLOATS 2048                    // per filter: [16][64] pairs (H[k(lane, 2 i)], H[k(lane, 2 i + 1)])
 
 // M = 2048 (host side: build_bank, build_notch, choose_notch_bank_fuse): `n_spectra` spectra and the pass-A twiddles next to
-// at least four waves' tiles; the notch (PAD = 1): one filter whose two reflected flanks stay apart, W + 2 h <= M
+// the waves' tiles (admitted: the counts that left four waves a 32-row tile each, as before the tile shrank to one row
+// group); the notch (PAD = 1): one filter whose two reflected flanks stay apart, W + 2 h <= M
 static inline int nmx_w64e_fixed(int n_spectra) { return n_spectra * NMX_W64E_H_FLOATS + NMX_W64E_TWA_FLOATS; }
 static inline bool nmx_w64e_fits(int n_spectra) {
-  return n_spectra >= 1 && nmx_w64_pair_waves(nmx_w64e_fixed(n_spectra), NMX_W64E_TILE_FLOATS) >= 4;
+  return n_spectra >= 1 && nmx_w64_pair_waves(nmx_w64e_fixed(n_spectra), NMX_W64E_ADMIT_TILE_FLOATS) >= 4;
 }
 static inline bool nmx_w64e_notch_ok(const NmxBankArgs& b) {
   return nmx_w64_pair_shape_ok(b) && b.pad_mode != 0 && b.n_filters == 1 && b.W + 2 * b.pad_half <= NMX_W64E_M && nmx_w64e_fits(1);
@@ -125,15 +128,14 @@ NMX_DEV void nmx_dft32_inv(nmx_c2* v) {
   nmx_dft32_inv_col<4>(v); nmx_dft32_inv_col<5>(v); nmx_dft32_inv_col<6>(v); nmx_dft32_inv_col<7>(v);
 }
 
-// ---- exchange patterns (byte offsets of register I relative to the lane's base address): P2 .. P4 are those of the
-// 1536-point kernel with a fourth group of rows; P1 follows this transform's pass-A register order
-constexpr int nmx_w64e_p1(int i) { return 8 * 72 * (4 * (i & 7) + (i >> 3)); }
-template <int... I> NMX_DEV void nmx_w64e_rd1(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<nmx_w64e_p1(I)>(a)), ...); }
-template <int... I> NMX_DEV void nmx_w64e_wr1(const nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { (nmx_ds_write_b64<nmx_w64e_p1(I)>(a, v[I]), ...); }
+// ---- exchange patterns: those of the 1536-point kernel (nmx_w64g_*, nmx_k_bank_w64c.h) with G = 4 row groups -- four
+// rounds through the same 8-row tile; P1 follows this transform's pass-A register order (k_a = 4 (I & 7) + (I >> 3))
+
 // table rows, registers I0 .. I0 + 15 of lane l at I * 512 + 8 l bytes
 template <int I0, int... I> NMX_DEV void nmx_w64e_rdt16(nmx_c2* v, unsigned a, std::integer_sequence<int, I...>) { ((v[I] = nmx_ds_read_b64<512 * (I0 + I)>(a)), ...); }
 #define NMX_W64E_SEQ32 std::make_integer_sequence<int, 32>{}
 #define NMX_W64E_SEQ16 std::make_integer_sequence<int, 16>{}
+#define NMX_W64E_SEQ4 std::make_integer_sequence<int, 4>{}
 
 // forward transform: v[j] = x[l + 64 j] -> v[8 g + qb] = X[u + 8 g + 32 ((lane & 7) + 8 qb)]
 template <int FULL>
@@ -150,19 +152,20 @@ NMX_DEV void nmx_w64e_forward(nmx_c2* v, const NmxW64cLane& Ln) {
     NMX_UNROLL
     for (int i = 0; i < 16; ++i) v[16 + i] = nmx_cmul_tw<0>(v[16 + i], w[i]);
   }
-  nmx_w64e_wr1(v, Ln.a1, NMX_W64E_SEQ32);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd2(v, Ln.a2, NMX_W64E_SEQ32);
-  NMX_SCHED_FENCE();
+  {
+    nmx_c2 b[32];
+    nmx_w64g_xch_ab<4>(v, b, Ln.a1, Ln.a2, NMX_W64E_SEQ4);
+    NMX_SCHED_FENCE();
+    NMX_UNROLL
+    for (int i = 0; i < 32; ++i) v[i] = b[i];
+  }
   NMX_UNROLL
   for (int g = 0; g < 4; ++g) {
     nmx_dft8<-1>(v + 8 * g);
     NMX_UNROLL
     for (int q = 1; q < 8; ++q) v[8 * g + q] = nmx_cmul_tw<0>(v[8 * g + q], Ln.twb[q]);
   }
-  nmx_w64c_wr3(v, Ln.a2, NMX_W64E_SEQ32);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd4(v, Ln.a4, NMX_W64E_SEQ32);
+  nmx_w64g_xch_bc(v, Ln.a2, Ln.a4, NMX_W64E_SEQ4);
   NMX_SCHED_FENCE();
   NMX_UNROLL
   for (int g = 0; g < 4; ++g) nmx_dft8<-1>(v + 8 * g);
@@ -175,15 +178,16 @@ NMX_DEV void nmx_w64e_inverse(nmx_c2* v, const NmxW64cLane& Ln) {
     NMX_UNROLL
     for (int q = 1; q < 8; ++q) v[8 * g + q] = nmx_cmul_tw<1>(v[8 * g + q], Ln.twb[q]);
   }
-  nmx_w64c_wr4(v, Ln.a4, NMX_W64E_SEQ32);
-  NMX_SCHED_FENCE();
-  nmx_w64c_rd3(v, Ln.a2, NMX_W64E_SEQ32);
+  nmx_w64g_xch_cb(v, Ln.a2, Ln.a4, NMX_W64E_SEQ4);
   NMX_SCHED_FENCE();
   NMX_UNROLL
   for (int g = 0; g < 4; ++g) nmx_dft8<+1>(v + 8 * g);
-  nmx_w64c_wr2(v, Ln.a2, NMX_W64E_SEQ32);
-  NMX_SCHED_FENCE();
-  nmx_w64e_rd1(v, Ln.a1, NMX_W64E_SEQ32);
+  {
+    nmx_c2 b[32];
+    nmx_w64g_xch_ba<4>(v, b, Ln.a1, Ln.a2, NMX_W64E_SEQ4);
+    NMX_UNROLL
+    for (int i = 0; i < 32; ++i) v[i] = b[i];
+  }
   {
     nmx_c2 w[16];
     nmx_w64e_rdt16<0>(w, Ln.twa, NMX_W64E_SEQ16);
@@ -379,7 +383,7 @@ NMX_DEV void nmx_bank_w64e_item(const NmxBankW64Args& AA, int w, int c, const Nm
     }
   }
   // the notch in residual form (NmxBankArgs::residual) stores x - g * x_ext: the window's samples stay in registers
-  // (the workgroup's exchange tiles bound the kernel at two waves per SIMD: 256 VGPRs each, 158 in use without them;
+  // (the kernel's launch bounds are two waves per SIMD, 256 VGPRs each, 158 in use without them;
   // re-reading them from L2 behind the inverse transform cost 0.15 ms of the 0.71 ms launch)
   // (the table-driven form of the reflection is at 236 VGPRs already: it reads them again)
   constexpr bool KEEP = PAD && WC;

@@ -45,6 +45,7 @@ static NmxW64PairGeom nmx_w64_pair_geom(int fixed, int tile, int cap, int n_item
   g.chunk = (g.n_pairs + g.grid * g.nw - 1) / (g.grid * g.nw);
   return g;
 }
+static void nmx_w64_note_geom(const NmxW64PairGeom& g) { nmxi_note_pair_geom(g.n_pairs, g.grid, g.nw); }
 
 // register budgets: the FIR-bank instantiation fits 168 VGPRs (3 waves/SIMD, 12 per CU, 5 spilled
 // dwords); the notch instantiation (odd-reflection staging) needs the 256-VGPR budget.
@@ -187,11 +188,11 @@ extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args* A, int n_items, int 
   }
 }
 
-// M = 1536, one wave per (window, channel pair) (nmx_k_bank_w64c.h): workgroups of `nw` waves; LDS = the real spectra of
-// all filters, the pass-A twiddles, one exchange tile per wave.  A wave walks a CONTIGUOUS run of `chunk` items in the
+// M = 1536, one wave per (window, channel pair) (nmx_k_bank_w64c.h): workgroups of `nw` waves (twelve: three per SIMD at
+// <= 168 VGPRs); LDS = the real spectra of all filters, the pass-A twiddles, one 4.5 KiB exchange tile per wave.  A wave walks a CONTIGUOUS run of `chunk` items in the
 // order (channel pair, window): consecutive items are consecutive hops of the same two channels, whose windows
 // overlap by W - hop samples -- after the first item of a run most of the window comes from L2.
-__global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64c_rd64(const NmxBankW64Args A, int n_windows, int n_pairs, int chunk) {
+__global__ void __launch_bounds__(64 * 12) nmx_kern_bank_w64c_rd64(const NmxBankW64Args A, int n_windows, int n_pairs, int chunk) {
   float* tab = nmx_smem_w64;
   const int hf = A.b.n_filters * NMX_W64C_H_FLOATS;
   for (int i = threadIdx.x; i < hf; i += blockDim.x) tab[i] = A.hc[i];
@@ -239,15 +240,21 @@ extern "C" void nmx_w64d_launch_rd64(const NmxBankW64Args* A, int n_items, int n
   if (A->b.W <= 512) {
     hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
     nmxi_note_kernel("nmx_kern_bank_w64d_rd64<1>");
+    nmx_w64_note_geom(g);
   } else {
     hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
     nmxi_note_kernel("nmx_kern_bank_w64d_rd64<0>");
+    nmx_w64_note_geom(g);
   }
 }
 
 // M = 2048, one wave per (window, channel pair) (nmx_k_bank_w64e.h): PAD = 0 the "same" FIR bank of the filters the
 // M = 1536 kernel cannot take, PAD = 1 the notch (odd-reflected window, one filter, the window back to HBM).  LDS = the
-// real spectra of the filters, the pass-A twiddles, one 18 KiB exchange tile per wave; contiguous runs of hops per wave.
+// real spectra of the filters, the pass-A twiddles, one 4.5 KiB exchange tile per wave; contiguous runs of hops per wave.
+// Seven waves per workgroup, as the 18 KiB tiles allowed: the eighth that LDS now has room for (two on every SIMD, the
+// register budget's limit) shortens these kernels alone by ~9 % and takes as much from the kernels on the plan's other
+// streams -- the step did not move (profiles/fir_group_exchange.md), so the geometry stays what it was.
+#define NMX_W64E_WAVES 7
 template <int PAD, int WC = 0, int HC = 0>
 __global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64e_rd64(const NmxBankW64Args A0, int n_windows, int n_pairs, int chunk) {
   // (kernel-argument pointer laundered once per item: the plan is re-read with s_load, not hoisted into scalar
@@ -281,8 +288,8 @@ __global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64e_rd64(const NmxBankW
 
 // The notch with the PAD = 0 filters behind it in ONE item (nmx_k_bank_w64e.h, FUSE): the window the notch stores is the
 // window those filters load, in the same registers.  LDS = the filters' spectra, (FUSE = 2: the notch's,) the pass-A
-// twiddles, one exchange tile per wave; FUSE = 1 reads the notch's spectrum from global memory, which leaves the seven
-// tiles of the two launches it replaces.
+// twiddles, one exchange tile per wave; FUSE = 1 reads the notch's spectrum from global memory (the default since the
+// tiles were 18 KiB and its 8 KiB cost a wave; with 4.5 KiB tiles both forms run NMX_W64E_WAVES waves).
 template <int WC, int HC, int FUSE>
 __global__ void __launch_bounds__(64 * 8) nmx_kern_notch_bank_w64e_rd64(const NmxW64eFusedArgs A0, int n_windows,
                                                             int n_pairs, int chunk) {
@@ -323,37 +330,43 @@ extern "C" void nmx_w64e_launch_fused_rd64(const NmxBankW64Args* F, const NmxBan
   A.f = *F;
   A.n.x = Nn->b.x; A.n.ch_stride = Nn->b.ch_stride; A.n.win_stride = Nn->b.win_stride; A.n.starts = Nn->b.starts;
   A.n.y_out = Nn->b.y_out; A.n.hg = Nn->hc; A.n.clean_on_load = Nn->b.clean_on_load; A.n.residual = Nn->b.residual;
-  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(F->b.n_filters + (g_lds ? 1 : 0)), NMX_W64E_TILE_FLOATS, 8, n_items,
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(F->b.n_filters + (g_lds ? 1 : 0)), NMX_W64E_TILE_FLOATS, NMX_W64E_WAVES, n_items,
                                              F->b.n_channels, n_cu);
   if (g_lds) {
     hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
     nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>");
+    nmx_w64_note_geom(g);
   } else {
     hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
     nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>");
+    nmx_w64_note_geom(g);
   }
 }
 
 extern "C" void nmx_w64e_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
   nmx_w64_allow_lds();
-  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(A->b.n_filters), NMX_W64E_TILE_FLOATS, 8, n_items, A->b.n_channels, n_cu);
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(A->b.n_filters), NMX_W64E_TILE_FLOATS, NMX_W64E_WAVES, n_items, A->b.n_channels, n_cu);
   if (nmx_w64e_notch_w1000(A->b)) {
     hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1, 1000, 499>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
     nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1, 1000, 499>");
+    nmx_w64_note_geom(g);
   } else if (A->b.pad_mode != 0) {
     hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
     nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1>");
+    nmx_w64_note_geom(g);
   } else {
     hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
     nmxi_note_kernel("nmx_kern_bank_w64e_rd64<0>");
+    nmx_w64_note_geom(g);
   }
 }
 
 extern "C" void nmx_w64c_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
   nmx_w64_allow_lds();
-  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64c_fixed(A->b.n_filters), NMX_W64C_TILE_FLOATS, 8, n_items, A->b.n_channels, n_cu);
+  const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64c_fixed(A->b.n_filters), NMX_W64C_TILE_FLOATS, 12, n_items, A->b.n_channels, n_cu);
   hipLaunchKernelGGL(nmx_kern_bank_w64c_rd64, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
   nmxi_note_kernel("nmx_kern_bank_w64c_rd64");
+  nmx_w64_note_geom(g);
 }
 
 // One channel per M = 2048 transform; `lds`: one item's LDS (the one-wave-per-workgroup kernels).  The form follows the
