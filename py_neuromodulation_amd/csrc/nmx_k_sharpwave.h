@@ -600,6 +600,9 @@ NMX_DEV int nmx_popc_below128(const NmxMask128& K, int r) {
 // before raw trough e is e or e + 1 (whichever kind comes first) and the number of KEPT peaks before
 // it is a popcount of the keep mask below that index.  The alternation is verified against the raw
 // lists (two independent LDS reads per trough); if it ever fails the bisection version runs instead.
+// (Between two strict maxima of a sequence lies a minimum, plateaus included, so no series can make the check fail:
+// the fallback is unreachable by construction and no test runs it -- tests/test_sharpwave_probes_cpu.py confirms the
+// alternation on every constructed row.)
 template <int NSL>
 NMX_DEV void nmx_dense_pair(const NmxMask128& KP, const int* ppos, const nmx_u16* rawP, int n_rawP,
                             const NmxMask128& KT, const int* tpos, int n_rawT,
@@ -624,7 +627,7 @@ NMX_DEV void nmx_dense_pair(const NmxMask128& KP, const int* ppos, const nmx_u16
     }
     lo[sl] = nmx_popc_below128(KP, r);
   }
-  if (!__all(ok)) {   // wave-uniform; never seen on real or synthetic data
+  if (!__all(ok)) {   // wave-uniform; unreachable by construction (see above), kept as a guard
     nmx_dense_pair_bisect<NSL>(KP, ppos, KT, tpos, selP, selT, lf, rt, nTr_out, n_pairs_out, first_valid_out, nT_out);
     return;
   }
