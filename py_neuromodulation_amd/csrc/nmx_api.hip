@@ -25,8 +25,6 @@
 #include "nmx_k_timeosc.h"
 #include "nmx_k_timeosc_w510.h"   // (the kernel predicates build_timeosc chooses with)
 
-#include <cstdlib>
-#include <map>
 #include <mutex>
 #include <string>
 
@@ -163,7 +161,6 @@ extern "C" void nmxi_note_kernel(const char* name) {
   s += name;
 }
 // launch geometry of the channel-pair FIR kernel just noted (nmx_w64.hip), whatever the stage: nmx_last_kernels(plan, 9)
-#define NMX_GEOM_SLOT 15
 extern "C" void nmxi_note_pair_geom(int n_pairs, int grid, int nw) {
   std::string& s = g_stage_kernels[NMX_GEOM_SLOT];
   const std::string e = std::string(g_last_kernel) + ": " + std::to_string(n_pairs) + " pairs, " + std::to_string(grid) + " x " + std::to_string(nw) + " waves";
@@ -453,26 +450,6 @@ static int be_check_launch() {
   return rc;
 }
 
-template <typename K>
-static void be_allow_lds(K kern) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-static void be_init_once() {
-  static unsigned long long seen = 0;   // per device (the opt-in is a per-device attribute)
-  if (!nmx_first_on_device(seen)) return;
-  be_allow_lds(nmx_kern_timeosc);
-  be_allow_lds(nmx_kern_bank);
-  be_allow_lds(nmx_kern_resample);
-  be_allow_lds(nmx_kern_burst_thr<32>);
-  be_allow_lds(nmx_kern_burst_thr<64>);
-  be_allow_lds(nmx_kern_burst_thr<128>);
-  be_allow_lds(nmx_kern_burst_thr_wide);
-  be_allow_lds(nmx_kern_burst_thr_tiled);
-  be_allow_lds(nmx_kern_burst_fill);
-  be_allow_lds(nmx_kern_burst_fill_sort);
-  be_allow_lds(nmx_kern_rawnorm_order);   // 24 * (window + hop) + 8 KiB: above 64 KiB from ~2390 samples
-}
-
 extern "C" void nmx_wave_launch_scan(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_timeosc_w1000_low(const NmxTimeOscArgs* A, int n_items, int n_cu, hipStream_t s);
 extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
@@ -483,7 +460,6 @@ extern "C" void nmx_wave_launch_timeosc_w1000_todo(const NmxTimeOscArgs* A, int 
 extern "C" void nmx_timeosc_long_launch(const NmxTimeOscArgs* A, int n_items, hipStream_t s);
 // `kind`: the plan's choice (build_timeosc).  The matrix-pipe kernel leaves flagged windows to be_launch_timeosc_redo.
 static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind kind, int n_items, int nt, size_t lds, int n_cu, be_stream_t s) {
-  be_init_once();
   switch (kind) {
     case NMX_TO_SCAN: nmx_wave_launch_scan(&A, n_items, s); return;
     case NMX_TO_SPECMM: nmx_specmm_launch(&A, n_items, n_cu, s); return;
@@ -494,8 +470,7 @@ static void be_launch_timeosc(const NmxTimeOscArgs& A, NmxTimeOscKind kind, int 
     case NMX_TO_FIXED128: nmx_timeosc_fixed_launch128(&A, n_items, lds, s); return;
     case NMX_TO_LONG: nmx_timeosc_long_launch(&A, n_items, s); return;
     case NMX_TO_GENERIC:
-      hipLaunchKernelGGL(nmx_kern_timeosc, dim3(n_items), dim3(nt), lds, s, A);
-      nmxi_note_kernel("nmx_kern_timeosc");
+      NMX_LAUNCH(nmx_kern_timeosc, dim3(n_items), dim3(nt), lds, s, A);
       return;
   }
 }
@@ -503,10 +478,8 @@ static void be_launch_timeosc_redo(const NmxTimeOscArgs& A, int n_items, be_stre
   nmx_wave_launch_timeosc_w1000_todo(&A, n_items, s);
 }
 static void be_launch_bank(const NmxBankArgs& A, int n_items, int nt, size_t lds, be_stream_t s) {
-  be_init_once();
   const int grid = (A.partitioned && n_items > NMX_UPS_SLOTS) ? NMX_UPS_SLOTS : n_items;
-  hipLaunchKernelGGL(nmx_kern_bank, dim3(grid), dim3(nt), lds, s, A, n_items);
-  nmxi_note_kernel("nmx_kern_bank");
+  NMX_LAUNCH(nmx_kern_bank, dim3(grid), dim3(nt), lds, s, A, n_items);
 }
 extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args*, int, size_t, int, hipStream_t);
 extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);
@@ -541,23 +514,21 @@ static void be_launch_notch_bank_fused(const NmxBankW64Args& F, const NmxBankW64
                                        be_stream_t s) {
   nmx_w64e_launch_fused_rd64(&F, &N, g_lds ? 1 : 0, n_items, n_cu, s);
 }
-extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, NmxSharpKind kind, int n_items, hipStream_t s);
+extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_sharp_slab(const NmxSharpArgs* A, int n_items, const unsigned char* todo, hipStream_t s);
 // `kind`: the plan's choice (build_sharp).  A dense-first kind flags the items it leaves to the list kernel in A.todo.
 static void be_launch_sharp(const NmxSharpArgs& A, NmxSharpKind kind, int n_items, size_t lds, be_stream_t s) {
-  be_init_once();
   switch (kind) {
     case NMX_SHARP_LIST: nmx_wave_launch_sharp(&A, n_items, lds, s); return;
     case NMX_SHARP_SLAB: nmx_wave_launch_sharp_slab(&A, n_items, nullptr, s); return;
-    case NMX_SHARP_DENSE_LIST: nmx_wave_launch_sharp_dense(&A, kind, n_items, s); nmx_wave_launch_sharp_todo(&A, n_items, lds, A.todo, s); return;
-    case NMX_SHARP_DENSE_SLAB: nmx_wave_launch_sharp_dense(&A, kind, n_items, s); nmx_wave_launch_sharp_slab(&A, n_items, A.todo, s); return;
+    case NMX_SHARP_DENSE_LIST: nmx_wave_launch_sharp_dense(&A, n_items, s); nmx_wave_launch_sharp_todo(&A, n_items, lds, A.todo, s); return;
+    case NMX_SHARP_DENSE_SLAB: nmx_wave_launch_sharp_dense(&A, n_items, s); nmx_wave_launch_sharp_slab(&A, n_items, A.todo, s); return;
   }
 }
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 extern "C" void nmx_hilbert_long_launch(const NmxHilbertArgs* A, long long n_items, hipStream_t s);
 static void be_launch_hilbert(const NmxHilbertArgs& A, NmxHilbertKind kind, long long n_items, size_t lds, be_stream_t s) {
-  be_init_once();
   if (kind == NMX_HIL_W500) nmx_wave_launch_hilbert_w500(&A, n_items, s);
   else if (kind == NMX_HIL_W1000) nmx_wave_launch_hilbert_w1000(&A, n_items, s);
   else if (kind == NMX_HIL_LONG) nmx_hilbert_long_launch(&A, n_items, s);
@@ -568,106 +539,91 @@ extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items,
 // its first hop -- the barrier-free one-wave walk, its list in L2 or (g.list_lds) in LDS; else the workgroup kernel
 static void be_launch_burst_thr(const NmxBurstThrArgs& A, const NmxBurstWalk& K, const NmxBurstWalkSeg& g, int n_items, int nt, size_t lds,
                                 be_stream_t s) {
-  be_init_once();
   if (g.kind == NMX_WALK_WAVE) { nmx_wave_launch_burst_thr(&A, n_items, K.nr, g.list_lds, g.list_lds ? K.lds_list : K.lds, s); return; }
   const int chunk = (A.K + nt - 1) / nt;
-  if (nmx_burst_thr_tiled(A.K)) { hipLaunchKernelGGL(nmx_kern_burst_thr_tiled, dim3(n_items), dim3(NMX_THR_TILE_NT), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_tiled"); }
-  else if (nt > 256) { hipLaunchKernelGGL(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr_wide"); }
-  else if (chunk <= 32) { hipLaunchKernelGGL(nmx_kern_burst_thr<32>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<32>"); }
-  else if (chunk <= 64) { hipLaunchKernelGGL(nmx_kern_burst_thr<64>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<64>"); }
-  else { hipLaunchKernelGGL(nmx_kern_burst_thr<128>, dim3(n_items), dim3(nt), lds, s, A); nmxi_note_kernel("nmx_kern_burst_thr<128>"); }
+  if (nmx_burst_thr_tiled(A.K)) NMX_LAUNCH(nmx_kern_burst_thr_tiled, dim3(n_items), dim3(NMX_THR_TILE_NT), lds, s, A);
+  else if (nt > 256) NMX_LAUNCH(nmx_kern_burst_thr_wide, dim3(n_items), dim3(1024), lds, s, A);
+  else if (chunk <= 32) NMX_LAUNCH(nmx_kern_burst_thr<32>, dim3(n_items), dim3(nt), lds, s, A);
+  else if (chunk <= 64) NMX_LAUNCH(nmx_kern_burst_thr<64>, dim3(n_items), dim3(nt), lds, s, A);
+  else NMX_LAUNCH(nmx_kern_burst_thr<128>, dim3(n_items), dim3(nt), lds, s, A);
 }
 // split: the sort and the walk as two launches
 static void be_launch_burst_fill(const NmxBurstThrArgs& A, int n_items, unsigned short* slots, float* sorted, bool split, be_stream_t s) {
-  be_init_once();
   int n2 = 2048;
   while (n2 < A.W + (A.n_windows - 1) * A.overlap) n2 <<= 1;
   const size_t lds_walk = nmx_burst_fill_walk_lds(n2, A.n_windows);
   if (split && lds_walk <= 48 * 1024) {   // (a hop count whose slot pairs do not fit: the one-launch form)
-    hipLaunchKernelGGL(nmx_kern_burst_fill_sort, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_sort_lds(n2), s, A, n2, slots, sorted);
-    hipLaunchKernelGGL(nmx_kern_burst_fill_walk, dim3(n_items), dim3(64), lds_walk, s, A, n2, (const unsigned short*)slots,
-                       (const float*)sorted);
-    nmxi_note_kernel("nmx_kern_burst_fill_sort");
-    nmxi_note_kernel("nmx_kern_burst_fill_walk");
+    NMX_LAUNCH(nmx_kern_burst_fill_sort, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_sort_lds(n2), s, A, n2, slots, sorted);
+    NMX_LAUNCH(nmx_kern_burst_fill_walk, dim3(n_items), dim3(64), lds_walk, s, A, n2, (const unsigned short*)slots, (const float*)sorted);
     return;
   }
-  hipLaunchKernelGGL(nmx_kern_burst_fill, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_lds(n2), s, A, n2, slots);
-  nmxi_note_kernel("nmx_kern_burst_fill");
+  NMX_LAUNCH(nmx_kern_burst_fill, dim3(n_items), dim3(NMX_FILL_NT), nmx_burst_fill_lds(n2), s, A, n2, slots);
 }
 static void be_launch_burst_stat(const NmxBurstStatArgs& A, NmxBurstStatKind kind, int n_items, size_t lds, be_stream_t s) {
-  be_init_once();
   nmx_wave_launch_burst_stat(&A, kind, n_items, lds, s);
 }
 static void be_launch_reref(const NmxRerefArgs& A, be_stream_t s) {
   dim3 grid((unsigned)((A.T + 255) / 256), (unsigned)((A.C + NMX_REREF_ROWS - 1) / NMX_REREF_ROWS));
-  hipLaunchKernelGGL(nmx_kern_reref, grid, dim3(256), 0, s, A);
-  nmxi_note_kernel("nmx_kern_reref");
+  NMX_LAUNCH(nmx_kern_reref, grid, dim3(256), 0, s, A);
 }
 static void be_launch_resample(const NmxResampleArgs& A, int n_items, int nt, size_t lds, be_stream_t s) {
-  be_init_once();
-  hipLaunchKernelGGL(nmx_kern_resample, dim3(n_items), dim3(nt), lds, s, A);
-  nmxi_note_kernel("nmx_kern_resample");
+  NMX_LAUNCH(nmx_kern_resample, dim3(n_items), dim3(nt), lds, s, A);
 }
 static void be_launch_rawnorm(const NmxRawNormArgs& A, be_stream_t s) {
-  be_init_once();
   if (A.method >= NMX_RAWNORM_MEDIAN && A.method != NMX_RAWNORM_POWER) {
     // lists in LDS + reduction scratch, or (lists in device memory) reduction scratch + subsample scratch
     const size_t lds = A.lists ? (size_t)8 * NMX_RAWNORM_ORDER_NT + 4 * (2 * NMX_RAWNORM_ORDER_NT + 272)
                                : (size_t)24 * A.max_list + 8 * NMX_RAWNORM_ORDER_NT;
-    hipLaunchKernelGGL(nmx_kern_rawnorm_order, dim3(A.n_channels), dim3(NMX_RAWNORM_ORDER_NT), lds, s, A);
+    NMX_LAUNCH_QUIET(nmx_kern_rawnorm_order, dim3(A.n_channels), dim3(NMX_RAWNORM_ORDER_NT), lds, s, A);   // (24 * (window + hop) + 8 KiB: above 64 KiB from ~2390 samples)
     const long long n = (long long)A.n_windows * A.n_channels * A.W;
-    hipLaunchKernelGGL(nmx_kern_rawnorm_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);
-    nmxi_note_kernel("nmx_kern_rawnorm_order + nmx_kern_rawnorm_apply");
+    // (the pair reports as ONE entry: the stage list's de-duplication then sees "order + apply" and "stats + apply" as different)
+    NMX_LAUNCH_AS("nmx_kern_rawnorm_order + nmx_kern_rawnorm_apply", nmx_kern_rawnorm_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);
     return;
   }
-  hipLaunchKernelGGL(nmx_kern_rawnorm_stats, dim3(A.n_channels), dim3(64), 0, s, A);
+  NMX_LAUNCH_QUIET(nmx_kern_rawnorm_stats, dim3(A.n_channels), dim3(64), 0, s, A);
   const long long n = (long long)A.n_windows * A.n_channels * A.W;
-  hipLaunchKernelGGL(nmx_kern_rawnorm_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);
-  nmxi_note_kernel("nmx_kern_rawnorm_stats + nmx_kern_rawnorm_apply");
+  NMX_LAUNCH_AS("nmx_kern_rawnorm_stats + nmx_kern_rawnorm_apply", nmx_kern_rawnorm_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A);   // (one entry, as above)
 }
 static void be_launch_kalman(const NmxKalmanArgs& A, be_stream_t s) {
   const int n = A.n_channels * A.n_bands;
-  hipLaunchKernelGGL(nmx_kern_kalman, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A);
-  nmxi_note_kernel("nmx_kern_kalman");
+  NMX_LAUNCH(nmx_kern_kalman, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, A);
 }
 static void be_launch_norm(const NmxNormArgs& A, be_stream_t s) {
   // one thread per column, one wave per workgroup: columns spread over as many CUs as possible
-  hipLaunchKernelGGL(nmx_kern_norm, dim3((unsigned)((A.n_cols + 63) / 64)), dim3(64), 0, s, A);
+  NMX_LAUNCH_QUIET(nmx_kern_norm, dim3((unsigned)((A.n_cols + 63) / 64)), dim3(64), 0, s, A);
 }
 static void be_launch_norm_scan(const NmxNormArgs& A, const NmxNormScan& S, be_stream_t s) {
   const unsigned cb = (unsigned)((A.n_cols + 63) / 64);
   const dim3 cells((unsigned)A.n_rows, (unsigned)((A.n_cols + 255) / 256));
-  if (S.n_hseg) hipLaunchKernelGGL(nmx_kern_norm_seg_hist, dim3(cb, (unsigned)S.n_hseg), dim3(64), 0, s, A, S);
-  hipLaunchKernelGGL(nmx_kern_norm_seg_batch, dim3(cb, (unsigned)S.n_bseg), dim3(64), 0, s, A, S);
-  hipLaunchKernelGGL(nmx_kern_norm_seg_offsets, dim3(cb), dim3(64), 0, s, A, S);
-  hipLaunchKernelGGL(nmx_kern_norm_cell, cells, dim3(256), 0, s, A, S);
-  hipLaunchKernelGGL(nmx_kern_norm_ring, cells, dim3(256), 0, s, A, S);
+  if (S.n_hseg) NMX_LAUNCH_QUIET(nmx_kern_norm_seg_hist, dim3(cb, (unsigned)S.n_hseg), dim3(64), 0, s, A, S);
+  NMX_LAUNCH_QUIET(nmx_kern_norm_seg_batch, dim3(cb, (unsigned)S.n_bseg), dim3(64), 0, s, A, S);
+  NMX_LAUNCH_QUIET(nmx_kern_norm_seg_offsets, dim3(cb), dim3(64), 0, s, A, S);
+  NMX_LAUNCH_QUIET(nmx_kern_norm_cell, cells, dim3(256), 0, s, A, S);
+  NMX_LAUNCH_QUIET(nmx_kern_norm_ring, cells, dim3(256), 0, s, A, S);
 }
 static void be_launch_power(const NmxPowerPrepArgs& P, const NmxPowerArgs& A, be_stream_t s) {
   const unsigned gy = (unsigned)((P.n_cols + 255) / 256);
-  hipLaunchKernelGGL(nmx_kern_power_prep, dim3((unsigned)(P.have + P.n_rows), gy), dim3(256), 0, s, P);
+  NMX_LAUNCH_QUIET(nmx_kern_power_prep, dim3((unsigned)(P.have + P.n_rows), gy), dim3(256), 0, s, P);
   // one wave per 64 columns of one hop: the ~30 likelihood evaluations of a fit diverge little inside a wave
-  hipLaunchKernelGGL(nmx_kern_power, dim3((unsigned)A.n_rows, (unsigned)((A.n_cols + 63) / 64)), dim3(64), 0, s, A);
-  hipLaunchKernelGGL(nmx_kern_power_ring, dim3((unsigned)P.n_rows, gy), dim3(256), 0, s, P);
+  NMX_LAUNCH_QUIET(nmx_kern_power, dim3((unsigned)A.n_rows, (unsigned)((A.n_cols + 63) / 64)), dim3(64), 0, s, A);
+  NMX_LAUNCH_QUIET(nmx_kern_power_ring, dim3((unsigned)P.n_rows, gy), dim3(256), 0, s, P);
 }
 static void be_launch_car(const NmxCarArgs& A, be_stream_t s) {
-  if (A.T <= 4096 && A.C >= 64) hipLaunchKernelGGL(nmx_kern_car<16>, dim3((unsigned)((A.T + 63) / 64)), dim3(1024), 0, s, A);
-  else hipLaunchKernelGGL(nmx_kern_car<4>, dim3((unsigned)((A.T + 63) / 64)), dim3(256), 0, s, A);
-  nmxi_note_kernel("nmx_kern_car");
+  // (reported without the waves-per-workgroup argument: the name is the same whatever the batch)
+  if (A.T <= 4096 && A.C >= 64) NMX_LAUNCH_AS("nmx_kern_car", nmx_kern_car<16>, dim3((unsigned)((A.T + 63) / 64)), dim3(1024), 0, s, A);
+  else NMX_LAUNCH_AS("nmx_kern_car", nmx_kern_car<4>, dim3((unsigned)((A.T + 63) / 64)), dim3(256), 0, s, A);
 }
 static void be_launch_reref_struct(const NmxRerefStructArgs& A, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_reref_struct, dim3((unsigned)((A.T + 63) / 64)), dim3(256), 0, s, A);
-  nmxi_note_kernel("nmx_kern_reref_struct");
+  NMX_LAUNCH(nmx_kern_reref_struct, dim3((unsigned)((A.T + 63) / 64)), dim3(256), 0, s, A);
 }
 static void be_launch_shift(const NmxShiftArgs& A, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_shift, dim3((unsigned)((A.T + 255) / 256), (unsigned)A.C), dim3(256), 0, s, A);
-  nmxi_note_kernel("nmx_kern_shift");
+  NMX_LAUNCH(nmx_kern_shift, dim3((unsigned)((A.T + 255) / 256), (unsigned)A.C), dim3(256), 0, s, A);
 }
 __global__ void __launch_bounds__(256) nmx_kern_reref64(const NmxReref64Args A) {
   nmx_reref64_tile(A, (long long)blockIdx.x * 256 + threadIdx.x, (int)blockIdx.y * NMX_REREF64_ROWS);
 }
 static void be_launch_reref64(const NmxReref64Args& A, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_reref64, dim3((unsigned)((A.T + 255) / 256), (unsigned)((A.C + NMX_REREF64_ROWS - 1) / NMX_REREF64_ROWS)),
+  NMX_LAUNCH_QUIET(nmx_kern_reref64, dim3((unsigned)((A.T + 255) / 256), (unsigned)((A.C + NMX_REREF64_ROWS - 1) / NMX_REREF64_ROWS)),
                      dim3(256), 0, s, A);
 }
 __global__ void __launch_bounds__(256) nmx_kern_rs64_elem(const NmxResample64Args A, int mode, const NmxCplx64* src, NmxCplx64* dst) {
@@ -679,18 +635,18 @@ __global__ void __launch_bounds__(256) nmx_kern_rs64_pass(const NmxCplx64* src, 
 }
 static void be_launch_rs64_elem(const NmxResample64Args& A, int mode, const NmxCplx64* src, NmxCplx64* dst, long long n, int rows,
                                 be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_rs64_elem, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0, s, A, mode, src, dst);
+  NMX_LAUNCH_QUIET(nmx_kern_rs64_elem, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0, s, A, mode, src, dst);
 }
 static void be_launch_rs64_pass(const NmxCplx64* src, NmxCplx64* dst, long long ld, long long n, long long ns, long long st, int sign,
                                 int rows, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_rs64_pass, dim3((unsigned)((n / 2 + 255) / 256), (unsigned)rows), dim3(256), 0, s, src, dst, ld, n, ns,
+  NMX_LAUNCH_QUIET(nmx_kern_rs64_pass, dim3((unsigned)((n / 2 + 255) / 256), (unsigned)rows), dim3(256), 0, s, src, dst, ld, n, ns,
                      st, sign);
 }
 static void be_launch_nanmask(const NmxNanMaskArgs& A, int n_items, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_nanmask, dim3(n_items), dim3(64), 64 * sizeof(float), s, A);
+  NMX_LAUNCH_QUIET(nmx_kern_nanmask, dim3(n_items), dim3(64), 64 * sizeof(float), s, A);
 }
 static void be_launch_tap(const NmxTapArgs& A, int n_items, be_stream_t s) {
-  hipLaunchKernelGGL(nmx_kern_tap, dim3(n_items), dim3(256), 0, s, A);
+  NMX_LAUNCH_QUIET(nmx_kern_tap, dim3(n_items), dim3(256), 0, s, A);
 }
 
 #include "nmx_engine.inc"

@@ -26,6 +26,7 @@ static inline float2 make_float2(float x, float y) { return float2{x, y}; }
 #define NMX_RESTRICT
 #else
 #include <hip/hip_runtime.h>
+#include <atomic>
 #define NMX_DEV __device__ __forceinline__
 #define NMX_DEVM __device__ __forceinline__
 #ifdef NMX_NT_FIXED
@@ -75,21 +76,58 @@ static inline float2 make_float2(float x, float y) { return float2{x, y}; }
 // global-memory writes of this thread become visible to the other threads of the workgroup (followed by NMX_SYNC)
 #define NMX_GLOBAL_FENCE() __threadfence_block()
 // host-side helpers shared by the translation units of libnmx.so
-// nmxi_note_kernel: every launcher records the kernel it actually launched (name as rocprofv3 prints it)
-// under the current stage; nmx_last_kernels() reports them (bench.py's roofline names the kernel from here).
+// nmxi_note_kernel: every launch records the kernel it launched (name as rocprofv3 prints it) under the current
+// stage -- through NMX_LAUNCH below, never by hand; nmx_last_kernels() reports them (bench.py's roofline names the kernel from here).
 extern "C" void nmxi_note_kernel(const char* name);
 // nmxi_note_pair_geom: behind nmxi_note_kernel, the channel-pair FIR launchers also record what the batch size made of that
 // launch (channel pairs, workgroups x waves per workgroup); nmx_last_kernels(plan, 9) reports it
 extern "C" void nmxi_note_pair_geom(int n_pairs, int grid, int nw);
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE opt-in: true the first time the calling
-// site runs on the current device (`seen` = a static bitmask of device ordinals owned by the call site)
-static inline bool nmx_first_on_device(unsigned long long& seen) {
+// true the first time the calling site runs on the current device (`seen` = a static bitmask of device ordinals owned by
+// the call site; atomic: the plans of a multi-device stream run one host thread each)
+static inline bool nmx_first_on_device(std::atomic<unsigned long long>& seen) {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d > 63) return true;
-  if ((seen >> d) & 1ull) return false;
-  seen |= 1ull << d;
-  return true;
+  return !((seen.fetch_or(1ull << d, std::memory_order_relaxed) >> d) & 1ull);
 }
+// ---- the one way to launch a kernel ----
+//   NMX_LAUNCH(kernel, grid, block, lds_bytes, stream, args...)           launches and reports the kernel's own spelling
+//   NMX_LAUNCH_AS("name", kernel, grid, block, lds_bytes, stream, args...) ... reports `name` (say why beside it)
+//   NMX_LAUNCH_QUIET(kernel, grid, block, lds_bytes, stream, args...)     ... reports nothing
+// A template-id with commas comes parenthesised, `(nmx_kern_x<1, 2>)`; the reported name drops those parentheses.  More than
+// 64 KiB of dynamic LDS is a per-device opt-in of the kernel (up to the CU's 160 KiB): a launch that asks for it opts in,
+// once per device -- every launch site owns the mask of its kernel instantiation; the others pay one comparison.
+static inline void nmx_launch_allow_lds(const void* kern, size_t lds, std::atomic<unsigned long long>& seen) {
+  if (lds > 64 * 1024 && nmx_first_on_device(seen))
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+template <size_t N>
+struct NmxKernName {
+  char s[N];
+};
+template <size_t N>
+constexpr NmxKernName<N> nmx_kern_name(const char (&t)[N]) {
+  NmxKernName<N> r{};
+  const size_t par = (N >= 3 && t[0] == '(' && t[N - 2] == ')') ? 1 : 0;
+  for (size_t i = 0; i + 1 + 2 * par < N; ++i) r.s[i] = t[i + par];
+  return r;
+}
+#define NMX_LAUNCH_QUIET(kern, grid, block, lds, stream, ...)                   \
+  do {                                                                          \
+    static std::atomic<unsigned long long> nmx_seen_{0};                        \
+    const size_t nmx_lds_ = (size_t)(lds);                                      \
+    nmx_launch_allow_lds((const void*)kern, nmx_lds_, nmx_seen_);               \
+    hipLaunchKernelGGL(kern, grid, block, nmx_lds_, stream, __VA_ARGS__);       \
+  } while (0)
+#define NMX_LAUNCH_AS(name, kern, grid, block, lds, stream, ...)                \
+  do {                                                                          \
+    NMX_LAUNCH_QUIET(kern, grid, block, lds, stream, __VA_ARGS__);              \
+    nmxi_note_kernel(name);                                                     \
+  } while (0)
+#define NMX_LAUNCH(kern, grid, block, lds, stream, ...)                         \
+  do {                                                                          \
+    static constexpr auto nmx_name_ = nmx_kern_name(#kern);                     \
+    NMX_LAUNCH_AS(nmx_name_.s, kern, grid, block, lds, stream, __VA_ARGS__);    \
+  } while (0)
 #endif
 
 // Values that are wave-uniform by construction but that the compiler cannot prove uniform (results
@@ -107,6 +145,8 @@ __device__ __forceinline__ long long nmx_uniform_ll(long long v) {
 }
 #endif
 
+// slot of the per-stage kernel lists (nmx_last_kernels) that holds the pair launches' geometry text, whatever the stage
+#define NMX_GEOM_SLOT 15
 #define NMX_MAX_STAGES 12
 #define NMX_MAX_BANDS_DEV 16
 // table of the matrix-pipe spectrum kernel (nmx_k_specmm.h): granules of four n, n < 250 live

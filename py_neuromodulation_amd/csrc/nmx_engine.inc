@@ -324,6 +324,23 @@ int env_int(const char* name, int dflt) {
   return (v && v[0] >= '0' && v[0] <= '9') ? atoi(v) : dflt;
 }
 
+// Workgroups of a persistent kernel that owns one slab of device memory each: as many per CU as `lds_bytes` of LDS leave room
+// for (two at the most), the slabs of `slab_floats` floats (0: none) within 64 MiB, at most `cap` (0: no cap); at least one.
+int slab_workgroups(const Plan& P, size_t lds_bytes, size_t slab_floats, int cap = 0) {
+  const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / lds_bytes)));
+  size_t blocks = (size_t)P.n_cu * per_cu;
+  if (slab_floats > 0) blocks = std::min(blocks, ((size_t)64 << 20) / (slab_floats * 4));
+  if (cap > 0) blocks = std::min(blocks, (size_t)cap);
+  return (int)std::max<size_t>(1, blocks);
+}
+
+// nmx_last_kernels: what the launches behind be_stage_reset() reported, per stage (the projection's: chunk_finalize), and the
+// geometry of the channel-pair FIR launches among them
+void snapshot_kernels(Plan& P) {
+  for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);
+  P.pair_geom = be_stage_kernels(NMX_GEOM_SLOT);
+}
+
 #include "nmx_engine_dc.inc"
 #include "nmx_engine_plan_spectral.inc"
 #include "nmx_engine_plan_bursts.inc"

@@ -73,9 +73,7 @@ static int build_hilbert_long(Plan& P) {
   H.slab_floats = al4(2 * ((W + 1) / 2));
   H.slab_blocks = 1;
 #ifndef NMX_HOST_EMU
-  const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)H.lds_floats * 4))));
-  size_t blocks = std::min((size_t)P.n_cu * per_cu, ((size_t)64 << 20) / ((size_t)H.slab_floats * 4));
-  H.slab_blocks = (int)std::max<size_t>(1, blocks);
+  H.slab_blocks = slab_workgroups(P, (size_t)H.lds_floats * 4, (size_t)H.slab_floats);
 #endif
   H.slab = (float*)plan_alloc(P, (size_t)H.slab_blocks * H.slab_floats * sizeof(float));
   if (!H.slab) return nmx_fail(NMX_E_NOMEM, "Hilbert slab allocation failed");

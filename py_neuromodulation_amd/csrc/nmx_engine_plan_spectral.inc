@@ -358,12 +358,7 @@ int build_timeosc(Plan& P) {
     // where a plan needs them: at most 3 x 20 001 floats each -- within 64 MiB of device memory
     A.slab_blocks = 1;
 #ifndef NMX_HOST_EMU
-    const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)A.lds_floats * 4))));
-    size_t blocks = (size_t)P.n_cu * per_cu;
-    if (A.slab_floats > 0) blocks = std::min(blocks, ((size_t)64 << 20) / ((size_t)A.slab_floats * 4));
-    const int cap = env_int("NMX_TIMEOSC_LONG_BLOCKS", 0);
-    if (cap > 0) blocks = std::min(blocks, (size_t)cap);
-    A.slab_blocks = (int)std::max<size_t>(1, blocks);
+    A.slab_blocks = slab_workgroups(P, (size_t)A.lds_floats * 4, (size_t)A.slab_floats, env_int("NMX_TIMEOSC_LONG_BLOCKS", 0));
 #endif
     if (A.slab_floats > 0) {
       A.slab = (float*)plan_alloc(P, (size_t)A.slab_blocks * A.slab_floats * sizeof(float));

@@ -394,9 +394,7 @@ int build_sharp(Plan& P) {
     A.slab_floats = A.off_res - A.off_emax;
 #ifndef NMX_HOST_EMU
     // one slab per resident workgroup: as many as the LDS copies of the series allow per CU, within 64 MiB of scratch
-    const int per_cu = std::max(1, std::min(2, (int)((size_t)160 * 1024 / ((size_t)A.lz_lds_floats * 4))));
-    const size_t cap = ((size_t)64 << 20) / ((size_t)A.slab_floats * 4);
-    A.slab_blocks = (int)std::max<size_t>(1, std::min<size_t>((size_t)P.n_cu * per_cu, cap));
+    A.slab_blocks = slab_workgroups(P, (size_t)A.lz_lds_floats * 4, (size_t)A.slab_floats);
 #endif
   }
   int ns = 0;

@@ -137,10 +137,7 @@ static int run_chunk(Plan& P, const BatchSched& b, const float* d_x, long long l
   if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
   P.sched.end_main(b);
   be_stage(ST_BATCH);
-  if (timed) {
-    for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (the projection's: chunk_finalize)
-    P.pair_geom = be_stage_kernels(15);   // (NMX_GEOM_SLOT: the channel-pair FIR launches of this chunk)
-  }
+  if (timed) snapshot_kernels(P);
   return be_check_launch();
 }
 
@@ -467,8 +464,7 @@ int nmx_preprocess_window(nmx_plan* plan, const double* x, int64_t ldx, double* 
   if ((rc = launch_front(P, v.x, W, 0, W, false, s, v))) return rc;
   if ((rc = run_prep_stages(P, v, 1, s))) return rc;
   be_stage(ST_BATCH);
-  for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
-  P.pair_geom = be_stage_kernels(15);
+  snapshot_kernels(P);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), v.x, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (int c = 0; c < C; ++c)
@@ -507,8 +503,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   be_stage(P.bank.launches[0].stage);
   launch_fir_stage(P, P.bank, A, C, s, false, true);   // (no notch here: a launch the plan fused into it runs stand-alone)
   be_stage(ST_BATCH);
-  for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);   // (nmx_last_kernels: what this call launched)
-  P.pair_geom = be_stage_kernels(15);
+  snapshot_kernels(P);   // (nmx_last_kernels: what this call launched)
   be_d2h_async(yf.data(), P.sharp.swy[0].p, yf.size() * sizeof(float), s);
   if ((rc = be_sync(s))) return rc;
   for (size_t i = 0; i < yf.size(); ++i) y[i] = (double)yf[i];

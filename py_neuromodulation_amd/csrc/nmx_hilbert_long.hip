@@ -22,10 +22,5 @@ __global__ void __launch_bounds__(NMX_BLOCK_FIXED) nmx_kern_hilbert_long(const N
 extern "C" void nmx_hilbert_long_launch(const NmxHilbertArgs* A, long long n_items, hipStream_t s) {
   if (n_items <= 0 || A->slab_blocks <= 0 || !A->slab) return;
   const int grid = (int)(n_items < (long long)A->slab_blocks ? n_items : (long long)A->slab_blocks);
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_hilbert_long, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  hipLaunchKernelGGL(nmx_kern_hilbert_long, dim3(grid), dim3(NMX_BLOCK_FIXED), (size_t)A->lds_floats * 4, s, *A, n_items);
-  nmxi_note_kernel("nmx_kern_hilbert_long");
+  NMX_LAUNCH(nmx_kern_hilbert_long, dim3(grid), dim3(NMX_BLOCK_FIXED), (size_t)A->lds_floats * 4, s, *A, n_items);
 }

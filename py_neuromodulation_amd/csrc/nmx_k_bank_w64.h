@@ -364,9 +364,9 @@ NMX_DEV void nmx_w64_reflect_table(const NmxBankArgs& A, unsigned* rtab, int tid
 // PAD = 0: zero-padded window ("same" FIR bank);  PAD = 1: odd-reflected window (notch)
 // TAB = 1: the A/B tables of all filters sit in LDS at `tab` ([filter][A[n], B[n]]), staged once
 // per (persistent, multi-wave) workgroup; TAB = 0: read from global memory (L2).
-// HALF = 1 (PAD = 0, W <= 1024): only the output registers v[4 t + r], r < 2 (samples < 1024) exist -- the
-// others are never computed, reduced or stored.
-template <int PAD, int TAB, int MC, int HALF = 0, int HOIST = 1>
+// MC = 0: compiled for the band-power activity only (no mobility / complexity path).
+// (Windows of at most 1024 samples, whose upper output registers need not exist: nmx_bank_w64_item_pipe<1>, nmx_k_bank_w64p.h.)
+template <int PAD, int TAB, int MC>
 NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* smem, const float* tab,
                                const unsigned* rtab = nullptr) {
   w = nmx_uniform_i(w);   // one item per wave: (w, c) and everything derived from them is scalar
@@ -561,7 +561,7 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
   // conjugate partners Z[n - k] of this lane's points: one cross-lane read per point, ONCE per item (they
   // do not depend on the filter; inside the filter loop they were a third of its LDS-crossbar traffic)
   nmx_c2 zcr[16];
-  if (PAD == 0 && HOIST) {   // (the notch has one filter: nothing to hoist, and it needs its 3 waves/SIMD)
+  if (PAD == 0) {   // (the notch has one filter: nothing to hoist, and it needs its 3 waves/SIMD)
     const int l = (int)(threadIdx.x & 63);
     NMX_UNROLL
     for (int r = 0; r < 16; ++r) {
@@ -591,7 +591,7 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
         if (l == 0) zc = (r == 0) ? zr[NMX_LI][0] : zr[NMX_LI][NMX_J2I((16 - r) & 15)];
 #else
         nmx_c2 zc;
-        if (PAD == 0 && HOIST) {
+        if (PAD == 0) {
           zc = zcr[r];
         } else {
           const nmx_c2 zs = zr[0][NMX_J2I(15 - r)];
@@ -614,10 +614,7 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
     NMX_LANE_LOOP { nmx_w64_passB_store(v[NMX_LI], X, l); }
     NMX_WSYNC();
     NMX_PROF(3)
-    NMX_LANE_LOOP {
-      if (HALF) nmx_w64_passC_lds_half<+1, TAB>(v[NMX_LI], X, twC, l);
-      else nmx_w64_passC_lds<+1, TAB>(v[NMX_LI], X, twC, l);
-    }
+    NMX_LANE_LOOP { nmx_w64_passC_lds<+1, TAB>(v[NMX_LI], X, twC, l); }
     NMX_PROF(4)
     // now lane l holds y[2 m], y[2 m + 1] in v[4 t + r] for m = l + 64 t + 256 r
 
@@ -637,7 +634,6 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
 #if defined(NMX_HOST_EMU)
           NMX_UNROLL
           for (int i = 0; i < 16; ++i) {
-            if (HALF && (i & 3) >= 2) continue;
             const int mb = 64 * (i >> 2) + 256 * (i & 3);
             if (2 * mb + 127 < lo || 2 * mb >= hi) continue;
             nmx_c2 val = v[NMX_LI][i];
@@ -655,7 +651,6 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
           const int s_l = 2 * l - lo;
           NMX_UNROLL
           for (int i = 0; i < 16; ++i) {
-            if (HALF && (i & 3) >= 2) continue;
             const int sb = s_l + 2 * (64 * (i >> 2) + 256 * (i & 3));
             nmx_c2 val = v[NMX_LI][i];
             val.x = (unsigned)sb < span ? val.x : 0.f;
@@ -680,7 +675,6 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
             const nmx_c2 mean2 = nmx_mk2(mean, mean);
             NMX_UNROLL
             for (int i = 0; i < 16; ++i) {
-              if (HALF && (i & 3) >= 2) continue;
               const int mb = 64 * (i >> 2) + 256 * (i & 3);
               if (2 * mb + 127 < lo || 2 * mb >= hi) continue;
               nmx_c2 d = nmx_csub(v[NMX_LI][i], mean2);
@@ -742,13 +736,11 @@ NMX_DEV void nmx_bank_w64_item(const NmxBankW64Args& AA, int w, int c, float* sm
         if ((W & 1) == 0) {
           NMX_UNROLL
           for (int i = 0; i < 16; ++i) {
-            if (HALF && (i & 3) >= 2) continue;
             __builtin_amdgcn_raw_buffer_store_b64(v[0][i], rs, 8 * l + 512 * (i >> 2) + 2048 * (i & 3), 0, NMX_SERIES_STORE_AUX);
           }
         } else {
           NMX_UNROLL
           for (int i = 0; i < 16; ++i) {
-            if (HALF && (i & 3) >= 2) continue;
             const int off = 8 * l + 512 * (i >> 2) + 2048 * (i & 3);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0][i].x), rs, off, 0, NMX_SERIES_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0][i].y), rs, off + 4, 0, NMX_SERIES_STORE_AUX);

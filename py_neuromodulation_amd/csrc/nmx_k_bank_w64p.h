@@ -1,6 +1,6 @@
 // nmx_k_bank_w64p.h -- the FIR-bank item of the PERSISTENT kernel, software-pipelined by hand.
 //
-// Same arithmetic, operation for operation, as nmx_bank_w64_item<0, 1, 0, 0, 0, HALF, 1> (nmx_k_bank_w64.h) --
+// Same arithmetic, operation for operation, as nmx_bank_w64_item<0, 1, 0> (nmx_k_bank_w64.h: PAD, TAB, MC) --
 // the results are bit-identical (tests: batch == one-window call) -- but the wave no longer sits idle while
 // its LDS traffic drains.  Per-phase s_memtime counters of the straight-line version (-DNMX_BANK_PROFILE)
 // showed, per filter: ~600 cycles waiting for the A/B table values in four dependent groups, ~1000 cycles

@@ -211,11 +211,7 @@ __global__ void __launch_bounds__(128) nmx_kern_coh(const NmxCohArgs A) {
 }
 // one workgroup per (window, pair): 64 threads up to 512-point segments, 128 beyond
 static void be_launch_coh(const NmxCohArgs& A, int n_items, be_stream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen))
-    (void)hipFuncSetAttribute((const void*)nmx_kern_coh, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const int nt = A.n <= 512 ? 64 : 128;
-  hipLaunchKernelGGL(nmx_kern_coh, dim3(n_items), dim3(nt), (size_t)A.lds_floats * 4, s, A);
-  nmxi_note_kernel("nmx_kern_coh");
+  NMX_LAUNCH(nmx_kern_coh, dim3(n_items), dim3(nt), (size_t)A.lds_floats * 4, s, A);
 }
 #endif

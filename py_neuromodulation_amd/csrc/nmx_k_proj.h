@@ -103,8 +103,6 @@ __global__ void __launch_bounds__(NMX_PROJ_NT) nmx_kern_proj(const NmxProjArgs A
 // one workgroup of 256 threads per (row, feature tile); at most 48 KiB of LDS, below the default limit
 static void be_launch_proj(const NmxProjArgs& A, be_stream_t s) {
   if (A.n_rows <= 0) return;
-  hipLaunchKernelGGL(nmx_kern_proj, dim3((unsigned)((long long)A.n_rows * A.n_tiles)), dim3(NMX_PROJ_NT),
-                     nmx_proj_lds_bytes(A), s, A);
-  nmxi_note_kernel("nmx_kern_proj");
+  NMX_LAUNCH(nmx_kern_proj, dim3((unsigned)((long long)A.n_rows * A.n_tiles)), dim3(NMX_PROJ_NT), nmx_proj_lds_bytes(A), s, A);
 }
 #endif

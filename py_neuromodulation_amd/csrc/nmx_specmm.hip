@@ -65,26 +65,20 @@ extern "C" void nmx_specmm_launch(const NmxTimeOscArgs* A, int n_items, int n_cu
   if (grid > n_cu) grid = n_cu;
   const size_t lds = (size_t)NMX_SMM_LDS_BYTES;
   const bool td = (A->features & (NMXD_F_HJORTH | NMXD_F_LINELENGTH | NMXD_F_RAW)) != 0, clean = false;   // (cleaning is the todo kernel's: nmx_k_specmm.h, finish())
-#define NMX_SMM_LAUNCH(NB, TD, CL)                                                                                       \
-  do {                                                                                                                   \
-    static unsigned long long seen = 0; /* per instantiation and device */                                               \
-    if (nmx_first_on_device(seen)) (void)hipFuncSetAttribute((const void*)nmx_kern_specmm_w1000<NB, TD, CL>,                                 \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, NMX_SMM_LDS_BYTES);                 \
-    hipLaunchKernelGGL((nmx_kern_specmm_w1000<NB, TD, CL>), dim3((unsigned)grid), dim3(256), lds, s, *A, (long long)n_items); \
-  } while (0)
-#ifdef NMX_SMM_SINGLE
+#ifdef NMX_SMM_SINGLE   // (one instantiation only; this form has never reported a name)
   (void)td; (void)clean;
-  NMX_SMM_LAUNCH(4, true, false);
+  NMX_LAUNCH_QUIET((nmx_kern_specmm_w1000<4, true, false>), dim3((unsigned)grid), dim3(256), lds, s, *A, (long long)n_items);
 #else
+  // (reported by the band count alone, whatever TD and CLEAN: the name the tests and bench.py's roofline know)
+#define NMX_SMM_LAUNCH(NB, TD, CL) \
+  NMX_LAUNCH_AS("nmx_kern_specmm_w1000<" #NB ">", (nmx_kern_specmm_w1000<NB, TD, CL>), dim3((unsigned)grid), dim3(256), lds, s, *A, (long long)n_items)
   if (A->n_bands <= 4) {
     if (td && clean) NMX_SMM_LAUNCH(4, true, true); else if (td) NMX_SMM_LAUNCH(4, true, false);
     else if (clean) NMX_SMM_LAUNCH(4, false, true); else NMX_SMM_LAUNCH(4, false, false);
-    nmxi_note_kernel("nmx_kern_specmm_w1000<4>");
   } else {
     if (td && clean) NMX_SMM_LAUNCH(8, true, true); else if (td) NMX_SMM_LAUNCH(8, true, false);
     else if (clean) NMX_SMM_LAUNCH(8, false, true); else NMX_SMM_LAUNCH(8, false, false);
-    nmxi_note_kernel("nmx_kern_specmm_w1000<8>");
   }
-#endif
 #undef NMX_SMM_LAUNCH
+#endif
 }

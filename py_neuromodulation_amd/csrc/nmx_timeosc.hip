@@ -28,21 +28,12 @@ __global__ void __launch_bounds__(NMX_BLOCK_FIXED) NMX_CAT(nmx_kern_hilbert_fixe
 
 
 extern "C" void NMX_CAT(nmx_hilbert_fixed_launch, NMX_BLOCK_FIXED)(const NmxHilbertArgs* A, long long n_items, size_t lds, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_hilbert_fixed, NMX_BLOCK_FIXED), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  }
-  hipLaunchKernelGGL(NMX_CAT(nmx_kern_hilbert_fixed, NMX_BLOCK_FIXED), dim3((unsigned)n_items), dim3(NMX_BLOCK_FIXED), lds, s, *A);
-  nmxi_note_kernel("nmx_kern_hilbert_fixed" NMX_STR(NMX_BLOCK_FIXED));
+  // (the kernel's name is pasted together from the width: reported as the pasted name, not as the macro call)
+  NMX_LAUNCH_AS("nmx_kern_hilbert_fixed" NMX_STR(NMX_BLOCK_FIXED), NMX_CAT(nmx_kern_hilbert_fixed, NMX_BLOCK_FIXED), dim3((unsigned)n_items),
+                dim3(NMX_BLOCK_FIXED), lds, s, *A);
 }
 
 extern "C" void NMX_CAT(nmx_timeosc_fixed_launch, NMX_BLOCK_FIXED)(const NmxTimeOscArgs* A, int n_items, size_t lds, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)NMX_CAT(nmx_kern_timeosc_fixed, NMX_BLOCK_FIXED), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  }
-  hipLaunchKernelGGL(NMX_CAT(nmx_kern_timeosc_fixed, NMX_BLOCK_FIXED), dim3(n_items), dim3(NMX_BLOCK_FIXED), lds, s, *A);
-  nmxi_note_kernel("nmx_kern_timeosc_fixed" NMX_STR(NMX_BLOCK_FIXED));
+  NMX_LAUNCH_AS("nmx_kern_timeosc_fixed" NMX_STR(NMX_BLOCK_FIXED), NMX_CAT(nmx_kern_timeosc_fixed, NMX_BLOCK_FIXED), dim3(n_items),   // (pasted, as above)
+                dim3(NMX_BLOCK_FIXED), lds, s, *A);
 }

@@ -23,10 +23,5 @@ __global__ void __launch_bounds__(NMX_BLOCK_FIXED) nmx_kern_timeosc_long(const N
 extern "C" void nmx_timeosc_long_launch(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   if (n_items <= 0 || A->slab_blocks <= 0 || (A->long_spec_slab && !A->slab)) return;
   const int grid = n_items < A->slab_blocks ? n_items : A->slab_blocks;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_timeosc_long, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  hipLaunchKernelGGL(nmx_kern_timeosc_long, dim3(grid), dim3(NMX_BLOCK_FIXED), (size_t)A->lds_floats * 4, s, *A, n_items);
-  nmxi_note_kernel("nmx_kern_timeosc_long");
+  NMX_LAUNCH(nmx_kern_timeosc_long, dim3(grid), dim3(NMX_BLOCK_FIXED), (size_t)A->lds_floats * 4, s, *A, n_items);
 }

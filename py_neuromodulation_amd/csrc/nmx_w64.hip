@@ -22,9 +22,6 @@
 
 extern __shared__ __attribute__((aligned(16))) float nmx_smem_w64[];
 
-// every kernel here may use the 160 KiB of LDS: the opt-in, once per device (defined behind the kernels)
-static void nmx_w64_allow_lds();
-
 // Launch geometry of the channel-pair kernels (M = 1024 / 1536 / 2048 and the fused notch + filters): `fixed` floats of
 // tables and one tile of `tile` floats per wave, at most `cap` waves per workgroup -- two when the batch is a hop or two, to
 // spread the few items over many CUs.  One workgroup per CU; a wave walks `chunk` consecutive (channel pair, window) items.
@@ -61,7 +58,6 @@ __global__ void __launch_bounds__(64, 2) nmx_kern_notch_w64_rd64(const NmxBankW6
 // Persistent variant: one workgroup of `nw` waves per CU; the A/B tables of all filters are
 // staged in LDS once per workgroup (instead of being re-fetched from L2 for every item: 27 % of
 // the kernel's time), then every wave walks its own items with wave-local fences only.
-// HIL = 1: Hilbert envelopes of the burst bands inside the kernel (tables after the twiddles in LDS).
 // HALF = 1: windows of at most 1024 samples -- the upper half of each inverse transform's outputs is never formed.
 // Pipelined persistent kernel (nmx_k_bank_w64p.h): the A / B tables are staged INTERLEAVED ((A_k, B_k) pairs: one
 // 8-byte read per point), everything else as below.
@@ -173,19 +169,13 @@ __global__ void __launch_bounds__(64 * 8) nmx_kern_bank_w64x2_rd64(const NmxBank
 }
 
 extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  nmx_w64_allow_lds();
   const int nw = NMX_W64X2_WAVES, x_floats = A->lds_floats;
   const int n_tab = nmx_w64x2_lds_tables(x_floats) < A->b.n_filters ? nmx_w64x2_lds_tables(x_floats) : A->b.n_filters;
   const size_t lds = (size_t)(n_tab * 4096 + nmx_w64x2_fixed(x_floats)) * 4;
   int grid = n_cu > 0 ? n_cu : 256;
   if (grid * nw > n_items) grid = (n_items + nw - 1) / nw;
-  if (A->b.W <= 2048) {
-    hipLaunchKernelGGL((nmx_kern_bank_w64x2_rd64<1>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
-    nmxi_note_kernel("nmx_kern_bank_w64x2_rd64<1>");
-  } else {
-    hipLaunchKernelGGL((nmx_kern_bank_w64x2_rd64<0>), dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
-    nmxi_note_kernel("nmx_kern_bank_w64x2_rd64<0>");
-  }
+  if (A->b.W <= 2048) NMX_LAUNCH(nmx_kern_bank_w64x2_rd64<1>, dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
+  else NMX_LAUNCH(nmx_kern_bank_w64x2_rd64<0>, dim3(grid), dim3(64 * nw), lds, s, *A, n_items, x_floats, n_tab);
 }
 
 // M = 1536, one wave per (window, channel pair) (nmx_k_bank_w64c.h): workgroups of `nw` waves (twelve: three per SIMD at
@@ -233,19 +223,12 @@ __global__ void __launch_bounds__(64 * (HALF ? 12 : 8)) nmx_kern_bank_w64d_rd64(
 }
 
 extern "C" void nmx_w64d_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  nmx_w64_allow_lds();
   const int x_floats = A->lds_floats;
   // W <= 512: 114 VGPRs, three waves per SIMD fit
   const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64d_fixed(A->b.n_filters), x_floats, A->b.W <= 512 ? 12 : 8, n_items, A->b.n_channels, n_cu);
-  if (A->b.W <= 512) {
-    hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
-    nmxi_note_kernel("nmx_kern_bank_w64d_rd64<1>");
-    nmx_w64_note_geom(g);
-  } else {
-    hipLaunchKernelGGL((nmx_kern_bank_w64d_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
-    nmxi_note_kernel("nmx_kern_bank_w64d_rd64<0>");
-    nmx_w64_note_geom(g);
-  }
+  if (A->b.W <= 512) NMX_LAUNCH(nmx_kern_bank_w64d_rd64<1>, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
+  else NMX_LAUNCH(nmx_kern_bank_w64d_rd64<0>, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk, x_floats);
+  nmx_w64_note_geom(g);
 }
 
 // M = 2048, one wave per (window, channel pair) (nmx_k_bank_w64e.h): PAD = 0 the "same" FIR bank of the filters the
@@ -325,47 +308,28 @@ __global__ void __launch_bounds__(64 * 8) nmx_kern_notch_bank_w64e_rd64(const Nm
 // fields patched in); g_lds: the notch's spectrum in LDS too
 extern "C" void nmx_w64e_launch_fused_rd64(const NmxBankW64Args* F, const NmxBankW64Args* Nn, int g_lds, int n_items, int n_cu,
                                            hipStream_t s) {
-  nmx_w64_allow_lds();
   NmxW64eFusedArgs A;
   A.f = *F;
   A.n.x = Nn->b.x; A.n.ch_stride = Nn->b.ch_stride; A.n.win_stride = Nn->b.win_stride; A.n.starts = Nn->b.starts;
   A.n.y_out = Nn->b.y_out; A.n.hg = Nn->hc; A.n.clean_on_load = Nn->b.clean_on_load; A.n.residual = Nn->b.residual;
   const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(F->b.n_filters + (g_lds ? 1 : 0)), NMX_W64E_TILE_FLOATS, NMX_W64E_WAVES, n_items,
                                              F->b.n_channels, n_cu);
-  if (g_lds) {
-    hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
-    nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>");
-    nmx_w64_note_geom(g);
-  } else {
-    hipLaunchKernelGGL((nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
-    nmxi_note_kernel("nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>");
-    nmx_w64_note_geom(g);
-  }
+  if (g_lds) NMX_LAUNCH((nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
+  else NMX_LAUNCH((nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, A, g.n_windows, g.n_pairs, g.chunk);
+  nmx_w64_note_geom(g);
 }
 
 extern "C" void nmx_w64e_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  nmx_w64_allow_lds();
   const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64e_fixed(A->b.n_filters), NMX_W64E_TILE_FLOATS, NMX_W64E_WAVES, n_items, A->b.n_channels, n_cu);
-  if (nmx_w64e_notch_w1000(A->b)) {
-    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1, 1000, 499>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
-    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1, 1000, 499>");
-    nmx_w64_note_geom(g);
-  } else if (A->b.pad_mode != 0) {
-    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<1>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
-    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<1>");
-    nmx_w64_note_geom(g);
-  } else {
-    hipLaunchKernelGGL((nmx_kern_bank_w64e_rd64<0>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
-    nmxi_note_kernel("nmx_kern_bank_w64e_rd64<0>");
-    nmx_w64_note_geom(g);
-  }
+  if (nmx_w64e_notch_w1000(A->b)) NMX_LAUNCH((nmx_kern_bank_w64e_rd64<1, 1000, 499>), dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+  else if (A->b.pad_mode != 0) NMX_LAUNCH(nmx_kern_bank_w64e_rd64<1>, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+  else NMX_LAUNCH(nmx_kern_bank_w64e_rd64<0>, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
+  nmx_w64_note_geom(g);
 }
 
 extern "C" void nmx_w64c_launch_rd64(const NmxBankW64Args* A, int n_items, int n_cu, hipStream_t s) {
-  nmx_w64_allow_lds();
   const NmxW64PairGeom g = nmx_w64_pair_geom(nmx_w64c_fixed(A->b.n_filters), NMX_W64C_TILE_FLOATS, 12, n_items, A->b.n_channels, n_cu);
-  hipLaunchKernelGGL(nmx_kern_bank_w64c_rd64, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
-  nmxi_note_kernel("nmx_kern_bank_w64c_rd64");
+  NMX_LAUNCH(nmx_kern_bank_w64c_rd64, dim3(g.grid), dim3(64 * g.nw), g.lds, s, *A, g.n_windows, g.n_pairs, g.chunk);
   nmx_w64_note_geom(g);
 }
 
@@ -373,47 +337,24 @@ extern "C" void nmx_w64c_launch_rd64(const NmxBankW64Args* A, int n_items, int n
 // batch: >= 4096 items the persistent pipelined bank (nmx_k_bank_w64p.h) where the plan allows it; the notch from 1024 items
 // four items per workgroup, from eight items per wave of a full device its persistent form; else a workgroup per item.
 extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args* A, int n_items, size_t lds, int n_cu, hipStream_t s) {
-  nmx_w64_allow_lds();
   const int x_floats = A->lds_floats;   // per-wave exchange tile (+ scratch)
   if (n_items >= 4096 && A->pipelined) {
     const int nw = NMX_W64P_WAVES, tab_floats = A->b.n_filters * 2 * NMX_W64_N;
     const size_t ldsp = (size_t)(tab_floats + NMX_W64_TWL_FLOATS + nw * x_floats) * 4;
     int grid = n_cu > 0 ? n_cu : 256;
     if (grid * nw > n_items) grid = (n_items + nw - 1) / nw;
-    if (A->b.W <= 1024) {   // the upper half of every inverse transform's outputs is never formed
-      hipLaunchKernelGGL((nmx_kern_bank_w64pp_rd64<1>), dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
-      nmxi_note_kernel("nmx_kern_bank_w64pp_rd64<1>");
-    } else {
-      hipLaunchKernelGGL((nmx_kern_bank_w64pp_rd64<0>), dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
-      nmxi_note_kernel("nmx_kern_bank_w64pp_rd64<0>");
-    }
+    // (W <= 1024: the upper half of every inverse transform's outputs is never formed)
+    if (A->b.W <= 1024) NMX_LAUNCH(nmx_kern_bank_w64pp_rd64<1>, dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
+    else NMX_LAUNCH(nmx_kern_bank_w64pp_rd64<0>, dim3(grid), dim3(64 * nw), ldsp, s, *A, n_items, x_floats);
   } else if (A->b.pad_mode != 0 && n_items >= 3 * 256 * 4 * 8) {
     const size_t ldsp = (size_t)(2 * NMX_W64_N + NMX_W64_TWL_FLOATS + 1024 + NMX_NOTCH_QP_WAVES * x_floats) * 4;
-    hipLaunchKernelGGL(nmx_kern_notch_w64qp_rd64, dim3((12 / NMX_NOTCH_QP_WAVES) * 256), dim3(64 * NMX_NOTCH_QP_WAVES), ldsp, s, *A, n_items, x_floats);
-    nmxi_note_kernel("nmx_kern_notch_w64qp_rd64");
+    NMX_LAUNCH(nmx_kern_notch_w64qp_rd64, dim3((12 / NMX_NOTCH_QP_WAVES) * 256), dim3(64 * NMX_NOTCH_QP_WAVES), ldsp, s, *A, n_items, x_floats);
   } else if (A->b.pad_mode != 0 && n_items >= 1024) {
     const size_t ldsq = (size_t)(2 * NMX_W64_N + NMX_W64_TWL_FLOATS + 4 * x_floats) * 4;
-    hipLaunchKernelGGL(nmx_kern_notch_w64q_rd64, dim3((n_items + 3) / 4), dim3(256), ldsq, s, *A, n_items, x_floats);
-    nmxi_note_kernel("nmx_kern_notch_w64q_rd64");
+    NMX_LAUNCH(nmx_kern_notch_w64q_rd64, dim3((n_items + 3) / 4), dim3(256), ldsq, s, *A, n_items, x_floats);
   } else if (A->b.pad_mode == 0) {
-    hipLaunchKernelGGL(nmx_kern_bank_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
-    nmxi_note_kernel("nmx_kern_bank_w64_rd64");
+    NMX_LAUNCH(nmx_kern_bank_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
   } else {
-    hipLaunchKernelGGL(nmx_kern_notch_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
-    nmxi_note_kernel("nmx_kern_notch_w64_rd64");
+    NMX_LAUNCH(nmx_kern_notch_w64_rd64, dim3(n_items), dim3(64), lds, s, *A);
   }
-}
-
-static void nmx_w64_allow_lds() {
-  static unsigned long long seen = 0;   // per device: the opt-in is a per-device attribute
-  if (!nmx_first_on_device(seen)) return;
-  const void* kernels[] = {(const void*)nmx_kern_bank_w64_rd64, (const void*)nmx_kern_notch_w64_rd64,
-                           (const void*)nmx_kern_bank_w64pp_rd64<0>, (const void*)nmx_kern_bank_w64pp_rd64<1>,
-                           (const void*)nmx_kern_notch_w64q_rd64, (const void*)nmx_kern_notch_w64qp_rd64,
-                           (const void*)nmx_kern_bank_w64x2_rd64<0>, (const void*)nmx_kern_bank_w64x2_rd64<1>,
-                           (const void*)nmx_kern_bank_w64c_rd64, (const void*)nmx_kern_bank_w64d_rd64<0>,
-                           (const void*)nmx_kern_bank_w64d_rd64<1>, (const void*)nmx_kern_bank_w64e_rd64<0>,
-                           (const void*)nmx_kern_bank_w64e_rd64<1>, (const void*)nmx_kern_bank_w64e_rd64<1, 1000, 499>,
-                           (const void*)nmx_kern_notch_bank_w64e_rd64<1000, 499, 1>, (const void*)nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>};
-  for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

@@ -10,8 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <cstdlib>
-
 #include "nmx_k_bursts.h"
 #include "nmx_k_bank_w64.h"
 #include "nmx_k_burst_stat_reg.h"
@@ -90,21 +88,11 @@ __global__ void __launch_bounds__(64) nmx_kern_burst_thr_wave(const NmxBurstThrA
 
 // nr, list_lds, lds: the plan's constants and the schedule's verdict for this launch (nmx_burst_walk_plan, nmx_burst_walk_schedule)
 extern "C" void nmx_wave_launch_burst_thr(const NmxBurstThrArgs* A, int n_items, int nr, bool list_lds, size_t lds, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // (K / 64 block counters of the flush: beyond ~639 000 list entries the working set passes 64 KiB)
-    (void)hipFuncSetAttribute((const void*)nmx_kern_burst_thr_wave<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  if (nr == 2) {
-    if (list_lds) hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, true>), dim3(n_items), dim3(64), lds, s, *A);
-    else hipLaunchKernelGGL((nmx_kern_burst_thr_wave<2, false>), dim3(n_items), dim3(64), lds, s, *A);
-    nmxi_note_kernel(list_lds ? "nmx_kern_burst_thr_wave<2, true>" : "nmx_kern_burst_thr_wave<2, false>");
-  } else {
-    hipLaunchKernelGGL((nmx_kern_burst_thr_wave<4, false>), dim3(n_items), dim3(64), lds, s, *A);
-    nmxi_note_kernel("nmx_kern_burst_thr_wave<4, false>");
-  }
+  // (<2, false>: K / 64 block counters of the flush -- beyond ~639 000 list entries the working set passes 64 KiB.  The arms
+  // stand in the order the three instantiations have always been named in: it is the order the compiler emits them in)
+  if (nr == 2 && list_lds) NMX_LAUNCH((nmx_kern_burst_thr_wave<2, true>), dim3(n_items), dim3(64), lds, s, *A);
+  else if (nr != 2) NMX_LAUNCH((nmx_kern_burst_thr_wave<4, false>), dim3(n_items), dim3(64), lds, s, *A);
+  else NMX_LAUNCH((nmx_kern_burst_thr_wave<2, false>), dim3(n_items), dim3(64), lds, s, *A);
 }
 
 // Hilbert envelope of length-1000 series, one wave per series (wave-level 500-point transforms)
@@ -120,15 +108,9 @@ __global__ void __launch_bounds__(256) nmx_kern_hilbert_w500_sparse(const NmxHil
 
 extern "C" void nmx_wave_launch_hilbert_w500(const NmxHilbertArgs* A, long long n_items, hipStream_t s) {
   const int k = waves_per_wg((size_t)NMX_W500_LDS_FLOATS * 4);
-  if (A->full) {
-    hipLaunchKernelGGL(nmx_kern_hilbert_w500_sparse, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k),
-                       (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
-    nmxi_note_kernel("nmx_kern_hilbert_w500_sparse");
-    return;
-  }
-  hipLaunchKernelGGL(nmx_kern_hilbert_w500, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k),
-                     (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
-  nmxi_note_kernel("nmx_kern_hilbert_w500");
+  const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
+  if (A->full) NMX_LAUNCH(nmx_kern_hilbert_w500_sparse, grid, block, (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
+  else NMX_LAUNCH(nmx_kern_hilbert_w500, grid, block, (size_t)NMX_W500_LDS_FLOATS * 4 * k, s, *A, (int)n_items);
 }
 
 // Hilbert envelope of length-2000 series (BASELINE config 3), one wave per series, four per workgroup (16 KB of LDS each)
@@ -146,18 +128,9 @@ __global__ void __launch_bounds__(256) nmx_kern_hilbert_w1000_sparse(const NmxHi
 }
 
 extern "C" void nmx_wave_launch_hilbert_w1000(const NmxHilbertArgs* A, long long n_items, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_hilbert_w1000, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)nmx_kern_hilbert_w1000_sparse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  if (A->full) {
-    hipLaunchKernelGGL(nmx_kern_hilbert_w1000_sparse, dim3((unsigned)((n_items + 3) / 4)), dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_hilbert_w1000_sparse");
-    return;
-  }
-  hipLaunchKernelGGL(nmx_kern_hilbert_w1000, dim3((unsigned)((n_items + 3) / 4)), dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
-  nmxi_note_kernel("nmx_kern_hilbert_w1000");
+  const dim3 grid((unsigned)((n_items + 3) / 4));
+  if (A->full) NMX_LAUNCH(nmx_kern_hilbert_w1000_sparse, grid, dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
+  else NMX_LAUNCH(nmx_kern_hilbert_w1000, grid, dim3(256), (size_t)4 * NMX_W1000_LDS_FLOATS * 4, s, *A, n_items);
 }
 
 // time-domain + FFT / Welch / STFT band means of the default shape, one wave per (window, channel)
@@ -243,19 +216,14 @@ extern "C" void nmx_wave_launch_timeosc_w1000_low(const NmxTimeOscArgs* A, int n
   if (grid > n_items) grid = n_items;
   const size_t lds = (size_t)NMX_TOW_LOW_LDS_FLOATS * 4;
   const unsigned spec = nmx_tow_spec(*A);
-  if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_C2) {
-    hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_C2>), dim3(grid), dim3(64), lds, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 65809u>");
-  } else if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_DEFAULT) {
-    hipLaunchKernelGGL((nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_DEFAULT>), dim3(grid), dim3(64), lds, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4, 196915u>");
-  } else if (A->n_bands <= 4) {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<4>");
-  } else {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w1000_low<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000_low<8>");
-  }
+  // (the SPEC masks are reported as the numbers the profiler prints, not as the macros' names)
+  static_assert(NMX_TOW_SPEC_C2 == 65809u && NMX_TOW_SPEC_DEFAULT == 196915u && NMX_TOW_SPEC_ALL == 196923u, "reported kernel names");
+  if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_C2)
+    NMX_LAUNCH_AS("nmx_kern_timeosc_w1000_low<4, 65809u>", (nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_C2>), dim3(grid), dim3(64), lds, s, *A, n_items);
+  else if (A->n_bands <= 4 && spec == NMX_TOW_SPEC_DEFAULT)
+    NMX_LAUNCH_AS("nmx_kern_timeosc_w1000_low<4, 196915u>", (nmx_kern_timeosc_w1000_low<4, NMX_TOW_SPEC_DEFAULT>), dim3(grid), dim3(64), lds, s, *A, n_items);
+  else if (A->n_bands <= 4) NMX_LAUNCH(nmx_kern_timeosc_w1000_low<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
+  else NMX_LAUNCH(nmx_kern_timeosc_w1000_low<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
 }
 
 extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
@@ -263,16 +231,10 @@ extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_ite
   const int k = waves_per_wg(lds);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
   const int slice = (int)(lds / 4);
-  if (A->n_bands <= 4 && nmx_tow_spec(*A) == NMX_TOW_SPEC_ALL) {   // the headline set: feature tests folded
-    hipLaunchKernelGGL((nmx_kern_timeosc_w1000<4, NMX_TOW_SPEC_ALL>), grid, block, lds * k, s, *A, n_items, slice);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000<4, 196923u>");
-  } else if (A->n_bands <= 4) {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w1000<4>, grid, block, lds * k, s, *A, n_items, slice);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000<4>");
-  } else {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w1000<8>, grid, block, lds * k, s, *A, n_items, slice);
-    nmxi_note_kernel("nmx_kern_timeosc_w1000<8>");
-  }
+  if (A->n_bands <= 4 && nmx_tow_spec(*A) == NMX_TOW_SPEC_ALL)   // the headline set: feature tests folded (the mask reported as its number, as above)
+    NMX_LAUNCH_AS("nmx_kern_timeosc_w1000<4, 196923u>", (nmx_kern_timeosc_w1000<4, NMX_TOW_SPEC_ALL>), grid, block, lds * k, s, *A, n_items, slice);
+  else if (A->n_bands <= 4) NMX_LAUNCH(nmx_kern_timeosc_w1000<4>, grid, block, lds * k, s, *A, n_items, slice);
+  else NMX_LAUNCH(nmx_kern_timeosc_w1000<8>, grid, block, lds * k, s, *A, n_items, slice);
 }
 
 // The windows the matrix-pipe kernel (nmx_k_specmm.h) flagged -- a NaN or an infinity among the samples: it does not clean
@@ -313,9 +275,9 @@ extern "C" void nmx_wave_launch_timeosc_w1000_todo(const NmxTimeOscArgs* A, int 
   const int n_windows = n_items / A->n_channels, n_tiles = ((n_windows + 15) / 16) * A->n_channels;
   const int blocks = (n_tiles + 63) / 64;
   const int grid = blocks < 256 * 8 ? blocks : 256 * 8;
-  if (A->n_bands <= 4) hipLaunchKernelGGL(nmx_kern_timeosc_w1000_todo<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
-  else hipLaunchKernelGGL(nmx_kern_timeosc_w1000_todo<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
-  nmxi_note_kernel("nmx_kern_timeosc_w1000_todo");
+  // (reported without the band-count argument: one name behind the matrix-pipe kernel's, whatever the plan)
+  if (A->n_bands <= 4) NMX_LAUNCH_AS("nmx_kern_timeosc_w1000_todo", nmx_kern_timeosc_w1000_todo<4>, dim3(grid), dim3(64), lds, s, *A, n_items);
+  else NMX_LAUNCH_AS("nmx_kern_timeosc_w1000_todo", nmx_kern_timeosc_w1000_todo<8>, dim3(grid), dim3(64), lds, s, *A, n_items);
 }
 
 // STFT with 500-sample segments on windows of other lengths (<= 2048), the only time / oscillatory feature
@@ -327,13 +289,8 @@ __global__ void __launch_bounds__(256) nmx_kern_timeosc_stft500(const NmxTimeOsc
 extern "C" void nmx_wave_launch_timeosc_stft500(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   const int k = waves_per_wg((size_t)NMX_TOS_LDS_FLOATS * 4);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
-  if (A->n_bands <= 4) {
-    hipLaunchKernelGGL(nmx_kern_timeosc_stft500<4>, grid, block, (size_t)NMX_TOS_LDS_FLOATS * 4 * k, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_stft500<4>");
-  } else {
-    hipLaunchKernelGGL(nmx_kern_timeosc_stft500<8>, grid, block, (size_t)NMX_TOS_LDS_FLOATS * 4 * k, s, *A, n_items);
-    nmxi_note_kernel("nmx_kern_timeosc_stft500<8>");
-  }
+  if (A->n_bands <= 4) NMX_LAUNCH(nmx_kern_timeosc_stft500<4>, grid, block, (size_t)NMX_TOS_LDS_FLOATS * 4 * k, s, *A, n_items);
+  else NMX_LAUNCH(nmx_kern_timeosc_stft500<8>, grid, block, (size_t)NMX_TOS_LDS_FLOATS * 4 * k, s, *A, n_items);
 }
 
 // 510-sample transforms (17 ms at 30 kHz): prime-factor transform per wave (nmx_k_timeosc_w510.h)
@@ -357,13 +314,8 @@ extern "C" void nmx_wave_launch_timeosc_w510(const NmxTimeOscArgs* A, int n_item
   const int slice = NMX_TO510_LDS_FLOATS(A->W);
   const int k = waves_per_wg((size_t)slice * 4);
   const dim3 grid((unsigned)((n_items + k - 1) / k)), block(64 * k);
-  if (A->n_bands <= 4) {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w510<4>, grid, block, (size_t)slice * 4 * k, s, *A, n_items, slice);
-    nmxi_note_kernel("nmx_kern_timeosc_w510<4>");
-  } else {
-    hipLaunchKernelGGL(nmx_kern_timeosc_w510<8>, grid, block, (size_t)slice * 4 * k, s, *A, n_items, slice);
-    nmxi_note_kernel("nmx_kern_timeosc_w510<8>");
-  }
+  if (A->n_bands <= 4) NMX_LAUNCH(nmx_kern_timeosc_w510<4>, grid, block, (size_t)slice * 4 * k, s, *A, n_items, slice);
+  else NMX_LAUNCH(nmx_kern_timeosc_w510<8>, grid, block, (size_t)slice * 4 * k, s, *A, n_items, slice);
 }
 
 // register-resident scan (Hjorth / Raw / LineLength only): four waves per workgroup, no LDS
@@ -377,8 +329,7 @@ __global__ void __launch_bounds__(256) nmx_kern_scan(const NmxTimeOscArgs A, int
 
 extern "C" void nmx_wave_launch_scan(const NmxTimeOscArgs* A, int n_items, hipStream_t s) {
   const int order = 0;
-  hipLaunchKernelGGL(nmx_kern_scan, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items, n_items / A->n_channels, order);
-  nmxi_note_kernel("nmx_kern_scan");
+  NMX_LAUNCH(nmx_kern_scan, dim3((n_items + 3) / 4), dim3(256), 0, s, *A, n_items, n_items / A->n_channels, order);
 }
 
 // dense-first launch: compact LDS layout (more waves per CU); overflowing items are flagged
@@ -389,18 +340,10 @@ __global__ void __launch_bounds__(256) nmx_kern_sharp_dense(const NmxSharpArgs A
 }
 
 // (the list kernel of the long-window kinds: nmx_wave_slab.hip)
-extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, NmxSharpKind kind, int n_items, hipStream_t s) {
-  if (kind == NMX_SHARP_DENSE_SLAB) {
-    static unsigned long long seen = 0;   // (the series alone is beyond the 64 KiB a kernel gets without asking)
-    if (nmx_first_on_device(seen)) {
-      (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_dense, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-  }
-  const int slice = (A->dz_lds_floats + 3) & ~3;
+extern "C" void nmx_wave_launch_sharp_dense(const NmxSharpArgs* A, int n_items, hipStream_t s) {
+  const int slice = (A->dz_lds_floats + 3) & ~3;   // (NMX_SHARP_DENSE_SLAB: the series alone is beyond 64 KiB)
   const int k = waves_per_wg((size_t)slice * 4, 2);
-  hipLaunchKernelGGL(nmx_kern_sharp_dense, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k), (size_t)slice * 4 * k, s, *A,
-                     n_items, slice);
-  nmxi_note_kernel("nmx_kern_sharp_dense");
+  NMX_LAUNCH(nmx_kern_sharp_dense, dim3((unsigned)((n_items + k - 1) / k)), dim3(64 * k), (size_t)slice * 4 * k, s, *A, n_items, slice);
 }
 
 // items the fused bank kernel could not finish (more than 128 extrema of a kind): generic list code.
@@ -424,45 +367,28 @@ __global__ void __launch_bounds__(64) nmx_kern_sharp_todo(const NmxSharpArgs A, 
 
 extern "C" void nmx_wave_launch_sharp_todo(const NmxSharpArgs* A, int n_items, size_t lds, const unsigned char* todo,
                                            hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_todo, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   const int blocks = (n_items + 63) / 64;
   const int grid = blocks < 256 * 14 ? blocks : 256 * 14;
-  hipLaunchKernelGGL(nmx_kern_sharp_todo, dim3(grid), dim3(64), lds, s, *A, n_items, todo);
-  nmxi_note_kernel("nmx_kern_sharp_todo");
+  NMX_LAUNCH(nmx_kern_sharp_todo, dim3(grid), dim3(64), lds, s, *A, n_items, todo);
 }
 
 extern "C" void nmx_wave_launch_burst_stat(const NmxBurstStatArgs* A, NmxBurstStatKind kind, int n_items, size_t lds, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_burst_stat, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   const dim3 grid4((n_items + 3) / 4);
-  switch (kind) {   // (the register forms: no LDS)
-    case NMX_BSTAT_REG16_SPARSE: hipLaunchKernelGGL((nmx_kern_burst_stat_reg<16, true>), grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg_sparse<16>"); return;
-    case NMX_BSTAT_REG16: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<16>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<16>"); return;
-    case NMX_BSTAT_REG32_SPARSE: hipLaunchKernelGGL((nmx_kern_burst_stat_reg<32, true>), grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg_sparse<32>"); return;
-    case NMX_BSTAT_REG32: hipLaunchKernelGGL(nmx_kern_burst_stat_reg<32>, grid4, dim3(256), 0, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_reg<32>"); return;
-    case NMX_BSTAT_SCAN: hipLaunchKernelGGL(nmx_kern_burst_stat_scan, grid4, dim3(256), (size_t)A->lds_floats * 4 * 4, s, *A, n_items); nmxi_note_kernel("nmx_kern_burst_stat_scan"); return;
+  switch (kind) {   // (the register forms: no LDS; the sparse ones report `_sparse<CH>`, the name the kernel-choice tests know them by)
+    case NMX_BSTAT_REG16_SPARSE: NMX_LAUNCH_AS("nmx_kern_burst_stat_reg_sparse<16>", (nmx_kern_burst_stat_reg<16, true>), grid4, dim3(256), 0, s, *A, n_items); return;
+    case NMX_BSTAT_REG16: NMX_LAUNCH(nmx_kern_burst_stat_reg<16>, grid4, dim3(256), 0, s, *A, n_items); return;
+    case NMX_BSTAT_REG32_SPARSE: NMX_LAUNCH_AS("nmx_kern_burst_stat_reg_sparse<32>", (nmx_kern_burst_stat_reg<32, true>), grid4, dim3(256), 0, s, *A, n_items); return;
+    case NMX_BSTAT_REG32: NMX_LAUNCH(nmx_kern_burst_stat_reg<32>, grid4, dim3(256), 0, s, *A, n_items); return;
+    case NMX_BSTAT_SCAN: NMX_LAUNCH(nmx_kern_burst_stat_scan, grid4, dim3(256), (size_t)A->lds_floats * 4 * 4, s, *A, n_items); return;
     case NMX_BSTAT_GENERIC: break;
   }
   const int k = waves_per_wg(lds);
   const int slice = (int)((lds / 4 + 3) & ~(size_t)3);
-  hipLaunchKernelGGL(nmx_kern_burst_stat, dim3((n_items + k - 1) / k), dim3(64 * k), (size_t)slice * 4 * k, s, *A,
-                     n_items, slice);
-  nmxi_note_kernel("nmx_kern_burst_stat");
+  NMX_LAUNCH(nmx_kern_burst_stat, dim3((n_items + k - 1) / k), dim3(64 * k), (size_t)slice * 4 * k, s, *A, n_items, slice);
 }
 
 extern "C" void nmx_wave_launch_sharp(const NmxSharpArgs* A, int n_items, size_t lds, hipStream_t s) {
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_sharp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   const int k = waves_per_wg(lds, 2);
   const int slice = (int)((lds / 4 + 3) & ~(size_t)3);
-  hipLaunchKernelGGL(nmx_kern_sharp, dim3((n_items + k - 1) / k), dim3(64 * k), (size_t)slice * 4 * k, s, *A,
-                     n_items, slice);
-  nmxi_note_kernel("nmx_kern_sharp");
+  NMX_LAUNCH(nmx_kern_sharp, dim3((n_items + k - 1) / k), dim3(64 * k), (size_t)slice * 4 * k, s, *A, n_items, slice);
 }

@@ -35,10 +35,5 @@ __global__ void __launch_bounds__(64) nmx_kern_sharp_slab(const NmxSharpArgs A, 
 extern "C" void nmx_wave_launch_sharp_slab(const NmxSharpArgs* A, int n_items, const unsigned char* todo, hipStream_t s) {
   if (n_items <= 0 || A->slab_blocks <= 0 || !A->slab) return;
   const int grid = n_items < A->slab_blocks ? n_items : A->slab_blocks;
-  static unsigned long long seen = 0;
-  if (nmx_first_on_device(seen)) {
-    (void)hipFuncSetAttribute((const void*)nmx_kern_sharp_slab, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  hipLaunchKernelGGL(nmx_kern_sharp_slab, dim3(grid), dim3(64), (size_t)A->lz_lds_floats * 4, s, *A, n_items, todo);
-  nmxi_note_kernel("nmx_kern_sharp_slab");
+  NMX_LAUNCH(nmx_kern_sharp_slab, dim3(grid), dim3(64), (size_t)A->lz_lds_floats * 4, s, *A, n_items, todo);
 }

@@ -69,7 +69,7 @@ accepted miss.
 
 Further rows: notch_one_ref (the one-channel notch behind a common average), tap_fused2 (NMX_NOTCH_SW_FUSE=2:
 nmx_kern_notch_bank_w64e_rd64<1000, 499, 2>), tap_nofuse and tap_4x40 (the plans tap_fused and tap_chunks are compared
-with byte for byte).  Every kernel of nmx_w64_allow_lds()'s list and nmx_kern_bank is reached through one of the three
+with byte for byte).  Every kernel nmx_w64.hip launches and nmx_kern_bank is reached through one of the three
 outlets and asserted by name (test_fir_sample_probes_cpu.py checks the tables against the launchers' source); none is
 left out.  HotPathEngine.kernels() names what the last filter_window / preprocess_window call launched.
 

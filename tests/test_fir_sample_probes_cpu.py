@@ -108,10 +108,11 @@ def test_restated_plan_arithmetic_and_inputs():
 
 
 def test_every_one_wave_fir_kernel_is_asserted_by_a_case():
-    """The names the launchers of nmx_w64.hip report (those of nmx_w64_allow_lds()'s list) and nmx_kern_bank against the
-    kernels the case tables assert."""
+    """The names the launchers of nmx_w64.hip report (NMX_LAUNCH: the kernel expression, without the parentheses around a
+    template-id with commas) and nmx_kern_bank against the kernels the case tables assert."""
     src = (ROOT / "py_neuromodulation_amd" / "csrc" / "nmx_w64.hip").read_text()
-    launched = set(re.findall(r'nmxi_note_kernel\("([^"]+)"\)', src)) | {"nmx_kern_bank"}
+    assert "NMX_LAUNCH_AS(" not in src and "NMX_LAUNCH_QUIET(" not in src
+    launched = set(re.findall(r"NMX_LAUNCH\(\(?(nmx_kern_\w+(?:<[^>]*>)?)\)?, ", src)) | {"nmx_kern_bank"}
     assert len(launched) == 17, sorted(launched)
     asserted = set()
     for table, col in ((cases.BANK_CASES, 6), (cases.NOTCH_CASES, 6), (cases.TAP_CASES, 4)):

@@ -89,7 +89,7 @@ def test_case_tables_against_the_launch_conditions_in_the_sources():
     """be_launch_car's NW rule, build_front's order of kernels, build_resample's plan choice and the NaN mask's launcher, read
     from the sources; the case tables reach both sides of every condition."""
     api = (CSRC / "nmx_api.hip").read_text()
-    m = re.search(r"if \(A\.T <= (\d+) && A\.C >= (\d+)\) hipLaunchKernelGGL\(nmx_kern_car<(\d+)>.*\n\s*else hipLaunchKernelGGL\(nmx_kern_car<(\d+)>", api)
+    m = re.search(r'if \(A\.T <= (\d+) && A\.C >= (\d+)\) NMX_LAUNCH_AS\("nmx_kern_car", nmx_kern_car<(\d+)>.*\n\s*else NMX_LAUNCH_AS\("nmx_kern_car", nmx_kern_car<(\d+)>', api)
     assert m and [int(g) for g in m.groups()] == [4096, 64, 16, 4], "be_launch_car's condition changed: the case table follows it"
     T = cases.W + (cases.HOPS - 1) * cases.HOP
     T_long, T_short = cases.W + (cases.LONG_HOPS - 1) * cases.HOP, cases.W + (cases.SHORT_HOPS - 1) * cases.HOP
@@ -119,10 +119,12 @@ def test_case_tables_against_the_launch_conditions_in_the_sources():
             trips, j = walk(C, q, 64, 48)
             nw16.add((trips, len(range(j, C, 16))))
     assert {t for t, _ in nw16} == {1, 2, 4} and {n for _, n in nw16} == {0, 1, 2, 3}, sorted(nw16)
-    for name in ("nmx_kern_car", "nmx_kern_reref_struct", "nmx_kern_reref", "nmx_kern_shift", "nmx_kern_resample"):
-        assert f'nmxi_note_kernel("{name}")' in api, name
+    # (the launch helper of nmx_common.h: NMX_LAUNCH reports the kernel's spelling, NMX_LAUNCH_AS the name it is given, NMX_LAUNCH_QUIET nothing)
+    for name in ("nmx_kern_reref_struct", "nmx_kern_reref", "nmx_kern_shift", "nmx_kern_resample"):
+        assert f"NMX_LAUNCH({name}," in api, name
     launcher = re.search(r"static void be_launch_nanmask\([^)]*\) \{\n(.*?)\n\}", api, re.S).group(1)
-    assert "nmx_kern_nanmask" in launcher and "nmxi_note_kernel" not in launcher and api.count("hipLaunchKernelGGL(nmx_kern_nanmask") == 1
+    assert launcher.lstrip().startswith("NMX_LAUNCH_QUIET(nmx_kern_nanmask,") and launcher.count("NMX_LAUNCH") == 1
+    assert len(re.findall(r"NMX_LAUNCH\w*\([^;]*nmx_kern_nanmask\b", api)) == 1
     prep = (CSRC / "nmx_k_prep.h").read_text()
     assert "#define NMX_REREF_ROWS 16" in prep and "#define NMX_RS_TAPS 4" in prep and "#define NMX_RS_GROUPS 4" in prep
     assert "m + 12 < end" in prep and "j + 12 < A.C" in prep and "j + 48 < A.C" in prep

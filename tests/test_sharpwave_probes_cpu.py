@@ -119,7 +119,7 @@ def test_restated_plan_choices_are_the_sources():
         called = set(re.findall(r"nmx_wave_launch_(sharp\w*)\(", row))
         assert {"nmx_kern_" + n for n in called} == names, (kind, row)
         assert launch[kind] in row
-    noted = set(re.findall(r'nmxi_note_kernel\("(nmx_kern_sharp\w*)"\)', (CSRC / "nmx_wave.hip").read_text() +
+    noted = set(re.findall(r"NMX_LAUNCH\((nmx_kern_sharp\w*),", (CSRC / "nmx_wave.hip").read_text() +   # (reports the kernel's spelling)
                            (CSRC / "nmx_wave_slab.hip").read_text()))
     assert noted == set().union(*cases.KERNELS.values()), noted
     assert cases.plan_choice(1000, 1000.0, 5, 10, cases.DEFAULT_COMBOS) == \
