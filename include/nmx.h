@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 13
+#define NMX_ABI_VERSION 14
 
 /* error codes */
 #define NMX_OK 0
@@ -56,6 +56,14 @@ extern "C" {
 #define NMX_F_BURSTS (1u << 7)     /* features/bursts.py:60-298       */
 #define NMX_F_LINELENGTH (1u << 8) /* features/linelength.py:11-21    */
 #define NMX_F_COHERENCE (1u << 9)  /* features/coherence.py (pairs of channels) */
+#define NMX_F_NOLDS (1u << 10)     /* features/nolds.py (sample entropy)        */
+
+/* measures of the nolds family, NoldsFeatures field order (features/nolds.py:14-19); only NMX_NOLDS_SAMPEN has a kernel */
+#define NMX_NOLDS_SAMPEN 1u
+#define NMX_NOLDS_CORR_DIM 2u
+#define NMX_NOLDS_LYAP 4u
+#define NMX_NOLDS_HURST 8u
+#define NMX_NOLDS_DFA 16u
 
 /* estimator bits (oscillatory: mean/median/std/max, features/oscillatory.py:29-34) */
 #define NMX_EST_MEAN 1u
@@ -118,7 +126,7 @@ typedef struct {
   int32_t abi_version;      /* NMX_ABI_VERSION */
   int32_t device;           /* HIP device ordinal */
   int32_t n_channels;       /* C: channels the features are computed for */
-  int32_t window;           /* W: samples per window (int(seg_ms/1000*sfreq)) */
+  int32_t window;           /* W: samples per window (int(seg_ms/1000*sfreq)): 4 .. 40 000 (from 1 on for a plan of nolds alone) */
   double sfreq;
   double feat_hz;           /* sampling_rate_features_hz (burst ring: samples_overlap) */
   uint32_t features;        /* NMX_F_* */
@@ -222,6 +230,27 @@ typedef struct {
   double coh_df;
   nmx_cols coh_cols;
 
+  /* nolds (features/nolds.py): sample entropy (nolds.sampen defaults: emb_dim 2, lag 1, Chebyshev distance, open
+   * comparison) of every channel's window ("raw") and of band-pass series of it.  Used when NMX_F_NOLDS is set; all zero =
+   * off.  Stateless.
+   *   nolds_raw         1: series 0 is the pre-processed window itself
+   *   nolds_n_bands     band series behind it, <= NMX_MAX_BANDS.  Series j is the window filtered with nolds_taps[j]
+   *                     (zero-padded "same" convolution, MNEFilter.filter_data; odd length, float64, copied at plan creation)
+   *                     -- the reference reads data_filt[:, j, :] of the bank over ALL frequency_ranges_hz with j the position
+   *                     in ITS OWN band list, so series j is global band j under the key of nolds band j: the host resolves
+   *                     that and hands over the taps it means
+   *   nolds_measures    NMX_NOLDS_* bit mask; anything but NMX_NOLDS_SAMPEN -> NMX_E_UNSUPPORTED
+   *   nolds_tol_factor  tol = nolds_tol_factor * std(x, ddof = nolds_ddof), both formed on the host
+   *   nolds_cols        a = series (raw first, then the bands in list order) */
+  int32_t nolds_raw;
+  int32_t nolds_n_bands;
+  const double* nolds_taps[NMX_MAX_BANDS];
+  int32_t nolds_n_taps[NMX_MAX_BANDS];
+  uint32_t nolds_measures;
+  double nolds_tol_factor;
+  int32_t nolds_ddof;
+  nmx_cols nolds_cols;
+
   /* Room behind the features: every output row of the plan is n_outputs + n_extra_cols floats (its row stride); the
    * features fill columns [0, n_outputs), the extra columns are left to an attached grid projection (nmx_proj below)
    * and hold NaN without one.  0 = today's layout. */
@@ -317,13 +346,14 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
 /* Timing of the last nmx_process_batch, measured with HIP events on the launch stream:
  * which = 0 whole batch, 1 pre-processing, 2 time/oscillatory kernel, 3 FIR-bank kernel,
  * 4 bursts kernels, 5 sharp-wave kernel, 6 second FIR-bank launch (the filters whose taps are too long for the
- * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel, 8 grid-projection kernel (attached nmx_proj).
- * Stages 1..8 are those of the first chunk of the batch.  Blocks until the events have completed. */
+ * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel, 8 grid-projection kernel (attached nmx_proj),
+ * 10 the nolds stage (its band filters and the sample-entropy kernel; 9 is no timer: see nmx_last_kernels).
+ * Stages 1..10 are those of the first chunk of the batch.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
 /* Names of the kernels the first launch sequence of the last nmx_process_batch -- or the last
  * nmx_preprocess_window / nmx_filter_window, whichever came last -- ran in stage `which`
- * (1..8 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
+ * (1..8 and 10 as above; several kernels are joined by " + "), spelled as rocprofv3 --kernel-trace prints them
  * (template arguments included).  Which variant runs depends on the shape, the batch size and the tuning
  * knobs, so measurement code names the kernel from here instead of hard-coding it.  NUL-terminated,
  * truncated to n - 1 characters.
@@ -331,6 +361,17 @@ int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
  * stage, "<kernel>: <channel pairs> pairs, <workgroups> x <waves per workgroup> waves" joined by " + " (what the batch
  * size made of the launch: small batches run two waves per workgroup). */
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n);
+
+/* nmx_process_batch from host memory (memspace 0, synchronous; state, timers and kernel names advance as there) of a plan
+ * with a nolds stage, which ALSO hands back what the sample-entropy kernel counted, item by item:
+ *   a, b, tol, sum_zero  [n_windows][n_series][n_channels] (series: raw first, then the bands): the kernel's pair counts A
+ *                        and B, its float32 tolerance, 1 when its float64 sum of the series is exactly 0
+ *   series               [n_windows][n_series][n_channels][window] float32: the samples the walk read -- the cleaned window,
+ *                        the band series the stage's filters wrote
+ * out ([n_windows][row stride]) and every array above may be NULL.  For tests that judge the counts and not only their
+ * logarithm, on the series the kernel itself read.  NMX_E_INVALID for a plan without a nolds stage. */
+int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                    float* out, uint32_t* a, uint32_t* b, float* tol, uint8_t* sum_zero, float* series);
 
 /* ---- Feature normalisation over a batch of hops (processing/normalization.py:31-111,150-163) ----
  * The reference post-processes every feature vector with a rolling normaliser (on by default,

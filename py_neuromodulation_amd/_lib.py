@@ -12,14 +12,17 @@ import ctypes as C
 import os
 from pathlib import Path
 
-NMX_ABI_VERSION = 13
+NMX_ABI_VERSION = 14
 NMX_MAX_BANDS = 16
 NMX_MAX_FILTERS = 24
 NMX_MAX_SW_COMBOS = 48
 
 # feature bits (FeatureSelector order, stream/settings.py:41-55)
-F_HJORTH, F_RAW, F_BANDPOWER, F_STFT, F_FFT, F_WELCH, F_SHARPWAVE, F_BURSTS, F_LINELENGTH, F_COHERENCE = (
-    1 << i for i in range(10))
+F_HJORTH, F_RAW, F_BANDPOWER, F_STFT, F_FFT, F_WELCH, F_SHARPWAVE, F_BURSTS, F_LINELENGTH, F_COHERENCE, F_NOLDS = (
+    1 << i for i in range(11))
+# measures of the nolds family, NoldsFeatures field order (features/nolds.py:14-19): bit i = NOLDS_MEASURES[i]
+NOLDS_MEASURES = ["sample_entropy", "correlation_dimension", "lyapunov_exponent", "hurst_exponent",
+                  "detrended_fluctuation_analysis"]
 EST_BITS = {"mean": 1, "median": 2, "std": 4, "max": 8}
 SW_FEATURES = ["peak_left", "peak_right", "num_peaks", "trough", "width", "prominence",
                "interval", "decay_time", "rise_time", "sharpness", "rise_steepness",
@@ -73,6 +76,9 @@ class PlanDesc(C.Structure):
         ("coh_n_pairs", C.c_int32), ("coh_pairs", C.POINTER(C.c_int32)), ("coh_nperseg", C.c_int32),
         ("coh_n_bands", C.c_int32), ("coh_bin_lo", C.c_int32 * NMX_MAX_BANDS), ("coh_bin_hi", C.c_int32 * NMX_MAX_BANDS),
         ("coh_features", C.c_uint32), ("coh_methods", C.c_uint32), ("coh_df", C.c_double), ("coh_cols", Cols),
+        ("nolds_raw", C.c_int32), ("nolds_n_bands", C.c_int32), 
+        ("nolds_taps", C.POINTER(C.c_double) * NMX_MAX_BANDS), ("nolds_n_taps", C.c_int32 * NMX_MAX_BANDS),
+        ("nolds_measures", C.c_uint32), ("nolds_tol_factor", C.c_double), ("nolds_ddof", C.c_int32), ("nolds_cols", Cols),
         ("n_extra_cols", C.c_int32),
     ]
 
@@ -98,7 +104,7 @@ _EXPORTS = [
     "nmx_plan_attach_norm", "nmx_host_alloc", "nmx_host_free", "nmx_device_pool_trim", "nmx_reref_f64", "nmx_resample_f64",
     "nmx_plan_carries_offsets", "nmx_plan_set_offsets", "nmx_plan_get_offsets", "nmx_plan_set_pipeline",
     "nmx_host_stage_rows", "nmx_host_group_sums", "nmx_host_stage_parts", "nmx_host_widen_rows",
-    "nmx_proj_create", "nmx_proj_destroy", "nmx_proj_process", "nmx_plan_attach_proj",
+    "nmx_proj_create", "nmx_proj_destroy", "nmx_proj_process", "nmx_plan_attach_proj", "nmx_nolds_probe",
 ]
 
 
@@ -169,6 +175,8 @@ class NmxLibrary:
         L.nmx_proj_destroy.argtypes = [C.c_void_p]
         L.nmx_proj_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
         L.nmx_plan_attach_proj.argtypes = [C.c_void_p, C.c_void_p]
+        L.nmx_nolds_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nmx_host_alloc.argtypes = [C.c_int64, C.POINTER(C.c_void_p)]
         L.nmx_host_free.argtypes = [C.c_void_p]
         L.nmx_device_pool_trim.argtypes = [C.c_int64, C.POINTER(C.c_int64)]

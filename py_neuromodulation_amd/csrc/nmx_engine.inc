@@ -26,6 +26,7 @@
 #include "../../include/nmx.h"
 #include "nmx_k_coh.h"   // coherence kernel + its be_launch_coh (HIP launcher, or the emulator's loop)
 #include "nmx_k_proj.h"  // grid-projection kernel + its be_launch_proj (likewise)
+#include "nmx_k_nolds.h" // sample-entropy kernel of the nolds feature + its be_launch_nolds (likewise)
 
 static thread_local std::string g_nmx_err;
 static int nmx_fail(int code, const std::string& msg) {
@@ -90,6 +91,8 @@ enum Stage {
   ST_BANK2 = 6,      // the bank's second launch, when its filters are split over two kernels
   ST_COH = 7,
   ST_PROJ = 8,       // grid projection: launched by chunk_finalize, behind the stages of run_chunk
+  ST_GEOM = 9,       // no stage: nmx_last_kernels(9) is the launch geometry of the channel-pair FIR kernels
+  ST_NOLDS = 10,     // nolds: its band filters and the sample-entropy kernel
   ST_COUNT
 };
 
@@ -160,6 +163,24 @@ struct FirStage {
   std::vector<FirLaunch> launches;   // (the LDS kernels: one entry, for its stage)
   bool takes_dc = true;   // its kernels add the carried offset on load (NmxBankArgs::dcf; else they read a copy of the windows
                           // with the offset added back, dc_windows): set by fir_stage_finish
+};
+
+// nolds (nmx_k_nolds.h; nmx_engine_plan_spectral.inc: build_nolds, launch_nolds_stage): stateless.  Its band series come
+// from a FIR stage of its own over the pre-processed windows -- the bank's kernels and the bank's taps, but not the bank's
+// launch: a band series is the filter's output alone (no band-power, burst or sharp-wave epilogue next to it), which is
+// what nmx_filter_window runs through those kernels as well, and a plan without nolds launches what it launched before.
+struct NoldsStage {
+  NmxNoldsArgs a{};           // argument template
+  FirStage fir;               // zero-padded "same" band filters, series out (sw_out)
+  bool have_fir = false;
+  std::vector<std::vector<double>> taps;   // deep copies
+  Buf yb;                     // band series of a chunk, [nw][C][n_band][W]
+  // nmx_nolds_probe: while h_probe is set every chunk also leaves its items' counts (and, with h_series, the series the
+  // walk read) in the caller's host arrays, rows [probe_w0, probe_w0 + nw) of them
+  unsigned* h_probe = nullptr;
+  float* h_series = nullptr;
+  long long probe_w0 = 0;
+  Buf d_probe, d_series;
 };
 
 // The bursts chain -- Hilbert envelope (where the bank leaves band series), threshold walk, run statistics -- with its kernels
@@ -249,6 +270,8 @@ struct Plan {
   bool have_timeosc = false;
   CohStage coherence;                 // coherence between channel pairs
   bool have_coh = false;
+  NoldsStage nolds;                   // sample entropy of the window and of band series of it
+  bool have_nolds = false;
   int nt_bank = 256;
   int chunk_windows = 1024;
   int burst_handoff_mb = 2048;   // windows above 16 384 samples: budget of the bursts chain's hand-off buffers (batch_chunk_sizes; NMX_BURST_HANDOFF_MB)
@@ -338,6 +361,7 @@ int slab_workgroups(const Plan& P, size_t lds_bytes, size_t slab_floats, int cap
 // geometry of the channel-pair FIR launches among them
 void snapshot_kernels(Plan& P) {
   for (int i = 0; i < ST_PROJ; ++i) P.kernels[i] = be_stage_kernels(i);
+  P.kernels[ST_NOLDS] = be_stage_kernels(ST_NOLDS);
   P.pair_geom = be_stage_kernels(NMX_GEOM_SLOT);
 }
 

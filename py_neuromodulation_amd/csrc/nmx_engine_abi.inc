@@ -68,13 +68,15 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   // the sharp-wave analysis (long-window mode of build_sharp), the long-window time / oscillatory kernel (build_timeosc:
   // Hjorth, raw, line length, FFT, Welch) and the bursts chain (partitioned bank, long Hilbert kernel, staged walk, scan
   // statistics: build_hilbert, build_bursts)
-  NMX_REQUIRE(desc->window >= 4 && desc->window <= 40000, "window must be in [4, 40 000 samples]");
+  // (a plan of nolds alone takes any window from one sample on: the reference's Nolds does -- NaN below four samples)
+  NMX_REQUIRE((desc->window >= 4 || (desc->features == NMX_F_NOLDS && desc->window >= 1)) && desc->window <= 40000,
+              "window must be in [4, 40 000 samples]");
   // Bursts above 16 384 samples are OPT-IN (NMX_LONG_BURSTS=1).  The chain is sized for them like the stages above, but the
   // refusal of such a plan is behaviour the suite pins (tests/timeosc_long_cases.py: a 20 000-sample plan with fft and bursts
   // raises): a plan that was refused stays refused until the caller asks.  Making it the default is this one test and the
   // default of this variable.
   const bool long_bursts = env_int("NMX_LONG_BURSTS", 0) != 0;
-  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH |
+  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_NOLDS |
                            (long_bursts ? NMX_F_BURSTS : 0u);
   const bool long_fits = desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0);
   if (long_bursts)
@@ -141,7 +143,7 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   P->chunk_windows = env_int("NMX_CHUNK_WINDOWS", 1024);
   P->burst_handoff_mb = std::max(1, env_int("NMX_BURST_HANDOFF_MB", P->burst_handoff_mb));
   P->norm_chunk_windows = std::max(1, env_int("NMX_NORM_CHUNK_WINDOWS", P->norm_chunk_windows));
-  if ((rc = build_front(*P)) || (rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_bank(*P)) ||
+  if ((rc = build_front(*P)) || (rc = build_timeosc(*P)) || (rc = build_coh(*P)) || (rc = build_nolds(*P)) || (rc = build_bank(*P)) ||
       (rc = build_notch(*P)) || (rc = build_bursts(*P)) || (rc = build_sharp(*P)) || (rc = build_kalman(*P)) ||
       (rc = build_resample(*P)) || (rc = build_prefilters(*P)) || (rc = build_rawnorm(*P)) || (rc = dc_build(*P)))
     return rc;

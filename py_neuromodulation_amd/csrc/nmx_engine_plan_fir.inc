@@ -541,3 +541,59 @@ int build_notch(Plan& P) {
   P.have_notch = true;
   return 0;
 }
+
+// ---- the band series of the nolds stage (build_nolds, nmx_engine_plan_spectral.inc) ---------------------------------------
+// Zero-padded "same" FIRs over the pre-processed window, series out: the band-pass bank's kernels with the series as their
+// only output.  The taps are the host's: those of the bank the reference's Nolds builds (BandPower(use_kf = False): every
+// band of frequency_ranges_hz, sfreq - 1 taps), picked by the reference's own index (plan_desc._nolds).
+int build_nolds_bands(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  NoldsStage& N = P.nolds;
+  const int nb = d.nolds_n_bands;
+  if (nb == 0) return 0;
+  NMX_REQUIRE(nb <= NMX_MAX_FILTERS_DEV, "nolds: too many band series");
+  FirStage& S = N.fir;
+  NmxBankArgs& A = S.a;
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
+  A.n_channels = d.n_channels;
+  A.W = d.window;
+  A.pad_mode = 0;
+  A.n_sw_filters = nb;
+  N.taps.resize(nb);
+  std::vector<const double*> live;
+  int reach = 0;
+  for (int j = 0; j < nb; ++j) {
+    NMX_REQUIRE(d.nolds_taps[j] && d.nolds_n_taps[j] >= 1 && (d.nolds_n_taps[j] & 1), "nolds: band filter taps must have odd length");
+    N.taps[j].assign(d.nolds_taps[j], d.nolds_taps[j] + d.nolds_n_taps[j]);
+    // only taps within W - 1 of the centre can touch the window (as build_bank)
+    const int half = (d.nolds_n_taps[j] - 1) / 2, uh = std::min(half, d.window - 1);
+    live.push_back(N.taps[j].data() + (half - uh));
+    reach = std::max(reach, uh);
+    NmxFilterDev& F = A.f[j];
+    F.half = uh;
+    F.bp_seglen = 0;
+    F.bp_band = 0;
+    F.burst_index = -1;
+    F.sw_index = j;
+    F.store_raw = 0;
+  }
+  int rc = build_fir_stage(P, live, FirRules{reach, 512, false, false, ST_NOLDS}, &S);
+  if (rc) return rc;
+  S.takes_dc = fir_stage_takes_dc(S);
+  N.have_fir = true;
+  return 0;
+}
+
+// the band series of one chunk into P.nolds.yb, [nw][C][n_band][W]
+static int launch_nolds_bands(Plan& P, const WinView& v, int nw, be_stream_t s, bool& dc_made) {
+  NoldsStage& N = P.nolds;
+  const nmx_plan_desc& d = P.d;
+  int rc;
+  if ((rc = ensure(N.yb, (size_t)nw * d.n_channels * d.nolds_n_bands * d.window * sizeof(float)))) return rc;
+  NmxBankArgs A = N.fir.a;
+  if ((rc = dc_bind(P, A, N.fir.takes_dc, v, nw, s, dc_made))) return rc;
+  A.out = nullptr;
+  A.sw_out = (float*)N.yb.p;
+  launch_fir_stage(P, N.fir, A, nw * d.n_channels, s);
+  return 0;
+}

@@ -537,3 +537,68 @@ static void launch_coh_stage(Plan& P, const WinView& v, int nw, float* d_out, be
   be_launch_coh(A, nw * A.n_pairs, s);
   if (tev) be_timer_stop(P.timers[ST_COH], s);
 }
+
+// ---- nolds: sample entropy of the window and of band series of it (nmx_k_nolds.h) ----------------------------------------
+int build_nolds_bands(Plan& P);   // the band filters: nmx_engine_plan_fir.inc, beside the other FIR stages
+static int launch_nolds_bands(Plan& P, const WinView& v, int nw, be_stream_t s, bool& dc_made);
+
+int build_nolds(Plan& P) {
+  const nmx_plan_desc& d = P.d;
+  if (!(d.features & NMX_F_NOLDS)) return 0;
+  NMX_REQUIRE(d.nolds_n_bands >= 0 && d.nolds_n_bands <= NMX_MAX_BANDS, "nolds: nolds_n_bands out of range");
+  const int n_series = (d.nolds_raw ? 1 : 0) + d.nolds_n_bands;
+  if (n_series == 0 || d.nolds_measures == 0) return 0;   // (nothing to compute: the reference emits no key either)
+  if (d.nolds_measures & ~NMX_NOLDS_SAMPEN)
+    return nmx_fail(NMX_E_UNSUPPORTED, "nolds: only sample_entropy has a kernel (correlation_dimension, lyapunov_exponent, "
+                    "hurst_exponent and detrended_fluctuation_analysis end in the reference's unseeded RANSAC line fit)");
+  NMX_REQUIRE(d.window <= NMX_NOLDS_MAX_N, "nolds: a series holds at most 40 000 samples (it has to fit the CU's LDS)");
+  NMX_REQUIRE(std::isfinite(d.nolds_tol_factor) && d.nolds_tol_factor >= 0.0 && d.nolds_ddof >= 0, "nolds: tol factor / ddof");
+  NmxNoldsArgs& A = P.nolds.a;
+  A = NmxNoldsArgs{};
+  A.n_outputs = d.n_outputs + d.n_extra_cols;   // (the row stride)
+  A.n_channels = d.n_channels;
+  A.W = d.window;
+  A.raw = d.nolds_raw ? 1 : 0;
+  A.n_band = d.nolds_n_bands;
+  A.tol_factor = d.nolds_tol_factor;
+  A.ddof = d.nolds_ddof;
+  A.cols = cv(d.nolds_cols);
+  // every column the stage writes must lie inside the row
+  const long long last = (long long)A.cols.base + (long long)(d.n_channels - 1) * A.cols.ch_stride +
+                         (long long)(n_series - 1) * A.cols.a_stride;
+  NMX_REQUIRE(A.cols.base >= 0 && A.cols.ch_stride >= 0 && A.cols.a_stride >= 0 && last < d.n_outputs,
+              "nolds: output columns outside the row");
+  A.lds_floats = al4(d.window) + 64;
+  int rc = build_nolds_bands(P);
+  if (rc) return rc;
+  P.have_nolds = true;
+  return 0;
+}
+
+// nolds of one chunk from the windows `v`: on the main stream, behind the time / oscillatory kernel
+static int launch_nolds_stage(Plan& P, const WinView& v, int nw, float* d_out, be_stream_t s, bool tev, bool& dc_made) {
+  if (!P.have_nolds) return 0;
+  NmxNoldsArgs A = P.nolds.a;
+  view_into(A, v);
+  A.dcf = dc_table(P);
+  A.out = d_out;
+  if (tev) be_timer_start(P.timers[ST_NOLDS], s);
+  be_stage(ST_NOLDS);
+  int rc = 0;
+  if (P.nolds.have_fir && !(rc = launch_nolds_bands(P, v, nw, s, dc_made))) A.yb = (const float*)P.nolds.yb.p;
+  const int n_items = nw * (A.raw + A.n_band) * A.n_channels;
+  NoldsStage& N = P.nolds;
+  if (!rc && N.h_probe) {   // (nmx_nolds_probe)
+    if (!(rc = ensure(N.d_probe, (size_t)n_items * 4 * sizeof(unsigned)))) A.probe = (unsigned*)N.d_probe.p;
+    if (!rc && N.h_series && !(rc = ensure(N.d_series, (size_t)n_items * A.W * sizeof(float)))) A.series_out = (float*)N.d_series.p;
+  }
+  if (!rc) be_launch_nolds(A, n_items, s);
+  if (!rc && N.h_probe) {
+    const size_t per_hop = (size_t)(A.raw + A.n_band) * A.n_channels;
+    be_d2h_async(N.h_probe + (size_t)N.probe_w0 * per_hop * 4, A.probe, (size_t)n_items * 4 * sizeof(unsigned), s);
+    if (A.series_out)
+      be_d2h_async(N.h_series + (size_t)N.probe_w0 * per_hop * A.W, A.series_out, (size_t)n_items * A.W * sizeof(float), s);
+  }
+  if (tev) be_timer_stop(P.timers[ST_NOLDS], s);
+  return rc;
+}

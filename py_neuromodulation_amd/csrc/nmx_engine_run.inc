@@ -133,6 +133,7 @@ static int run_chunk(Plan& P, const BatchSched& b, const float* d_x, long long l
   be_stage(ST_BURSTS);
   if (P.have_bursts && (rc = launch_burst_stage(P, b, nw, d_out, tev))) return rc;
   if ((rc = launch_timeosc_stage(P, v, nw, d_out, s, tev, dc_made))) return rc;
+  if ((rc = launch_nolds_stage(P, v, nw, d_out, s, tev, dc_made))) return rc;
   launch_coh_stage(P, v, nw, d_out, s, tev);
   if (!sharp_side && (rc = launch_sharp_stage(P, par, nw, d_out, s, tev))) return rc;
   P.sched.end_main(b);
@@ -200,7 +201,7 @@ static ChunkSizes batch_chunk_sizes(const Plan& P, bool host) {
   ChunkSizes z{host, 0, 0, 0};
   // (a plan without a hand-off tensor -- time / oscillatory features straight from the recording -- has nothing a chunk
   // would bound: device-resident batches go out as ONE launch of up to 16 chunks' worth of hops)
-  const bool no_handoff = !P.have_bank && !P.have_notch && !P.front.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
+  const bool no_handoff = !P.have_bank && !(P.have_nolds && P.nolds.have_fir) && !P.have_notch && !P.front.d_R && !P.have_resample && !P.have_rawnorm && P.pre.empty();
   // (an attached normaliser needs a chunk's rows complete, and hop order: it runs on the finalize stream under the NEXT
   // chunk's kernels, so only the last chunk's pass is exposed -- against that, shorter chunks cost the main kernels 0.16 ms
   // per 1024 hops at 256.  Round 6, scans + cells at ~75 us per pass, headline step with / without the z-score:
@@ -220,6 +221,14 @@ static ChunkSizes batch_chunk_sizes(const Plan& P, bool host) {
   // buffer): as many hops as fit NMX_BURST_HANDOFF_MB together, never fewer than one.  Plans up to 16 384 samples keep theirs.
   if (P.have_bursts && P.d.window > 16384) {
     const double per_hop = 3.0 * P.d.n_channels * P.d.n_burst_bands * (double)P.d.window * sizeof(float);
+    const int64_t cap = std::max<int64_t>(1, (int64_t)((double)P.burst_handoff_mb * 1048576.0 / per_hop));
+    z.dev_chunk = std::min(z.dev_chunk, cap);
+    z.host_big = std::min(z.host_big, cap);
+    z.host_first = std::min(z.host_first, cap);
+  }
+  // ... and so do the band series of the nolds stage (one buffer, hops x channels x bands x window floats)
+  if (P.have_nolds && P.nolds.have_fir && P.d.window > 16384) {
+    const double per_hop = (double)P.d.n_channels * P.d.nolds_n_bands * (double)P.d.window * sizeof(float);
     const int64_t cap = std::max<int64_t>(1, (int64_t)((double)P.burst_handoff_mb * 1048576.0 / per_hop));
     z.dev_chunk = std::min(z.dev_chunk, cap);
     z.host_big = std::min(z.host_big, cap);
@@ -364,6 +373,7 @@ static int process_batch_impl(nmx_plan* plan, const float* x, int64_t ldx, int64
       }
     }
     bool freed = false;
+    P.nolds.probe_w0 = w0;
     rc = run_chunk(P, b, d_xk, ldxk, lo, hi, (const long long*)P.starts.p + w0, nw, d_outk, w0 == 0, d_prek, starts + w0,
                    host ? P.sched.input_consumed_event(b, k) : nullptr, &freed);
     if (rc) return bail(rc);
@@ -512,7 +522,7 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
 
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms) {
   Plan* P = (Plan*)plan;
-  if (!P || !ms || which < ST_BATCH || which >= ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
+  if (!P || !ms || which < ST_BATCH || which >= ST_COUNT || which == ST_GEOM) return nmx_fail(NMX_E_INVALID, "bad argument");
   be_set_device(P->device);
   *ms = be_timer_elapsed(P->timers[which]);
   return 0;
@@ -638,8 +648,8 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
 
 int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   Plan* P = (Plan*)plan;
-  if (!P || !buf || n < 1 || which < ST_PREP || which > ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
-  std::string k = which == ST_COUNT ? P->pair_geom : P->kernels[which];   // (9: no stage, the pair kernels' launch geometry)
+  if (!P || !buf || n < 1 || which < ST_PREP || which >= ST_COUNT) return nmx_fail(NMX_E_INVALID, "bad argument");
+  std::string k = which == ST_GEOM ? P->pair_geom : P->kernels[which];   // (9: no stage, the pair kernels' launch geometry)
   if (which == ST_BURSTS && P->bursts.sparse_count)   // (count mode: rows stored as their tail / rows, over the plan's life)
     k += (k.empty() ? "" : ",") + std::string("env_tail_rows=") + std::to_string(P->bursts.env_tail_rows) + "/" + std::to_string(P->bursts.env_rows);
   const size_t m = std::min<size_t>(k.size(), (size_t)n - 1);
@@ -648,3 +658,30 @@ int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n) {
   return 0;
 }
 
+
+// ---- nolds: a batch that also hands back what the sample-entropy kernel counted (include/nmx.h) ----------------------------
+int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                    float* out, uint32_t* a, uint32_t* b, float* tol, uint8_t* sum_zero, float* series) {
+  Plan* Pp = (Plan*)plan;
+  if (!Pp) return nmx_fail(NMX_E_INVALID, "null argument");
+  Plan& P = *Pp;
+  NMX_REQUIRE(P.have_nolds, "nmx_nolds_probe: the plan has no nolds stage");
+  NMX_REQUIRE(n_windows >= 1 && n_windows <= (1 << 20), "nmx_nolds_probe: 1 <= n_windows <= 2^20");
+  const size_t per_hop = (size_t)(P.nolds.a.raw + P.nolds.a.n_band) * P.d.n_channels, n = (size_t)n_windows * per_hop;
+  std::vector<unsigned> hp(n * 4);
+  std::vector<float> rows;
+  if (!out) { rows.resize((size_t)n_windows * (P.d.n_outputs + P.d.n_extra_cols)); out = rows.data(); }
+  P.nolds.h_probe = hp.data();
+  P.nolds.h_series = series;
+  const int rc = process_batch_impl(plan, x, ldx, n_samples, starts, n_windows, out, nullptr, 0, nullptr, nullptr);
+  P.nolds.h_probe = nullptr;
+  P.nolds.h_series = nullptr;
+  if (rc) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    if (a) a[i] = hp[4 * i];
+    if (b) b[i] = hp[4 * i + 1];
+    if (tol) memcpy(&tol[i], &hp[4 * i + 2], 4);
+    if (sum_zero) sum_zero[i] = (uint8_t)hp[4 * i + 3];
+  }
+  return 0;
+}

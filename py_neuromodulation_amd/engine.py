@@ -26,7 +26,7 @@ from .host_mem import (_TABLES, _ld, _offset_scratch, _pool, _rows_ok, _staging,
 from .plan_desc import COH_MAX_NPERSEG, PlanBuilder  # noqa: F401
 
 MAX_PLAN_WINDOW = 16384   # nmx_plan_create: window in [4, 16384] samples for a plan in general; the stand-alone filter objects cut longer
-                          # recordings into segments of this length (a plan of raw_hjorth, return_raw, linelength, fft, welch and
+                          # recordings into segments of this length (a plan of raw_hjorth, return_raw, linelength, fft, welch, nolds and
                           # sharpwave_analysis, without raw normaliser or resampling, may be built up to 40 000 samples; with
                           # NMX_LONG_BURSTS=1 in the environment bursts too: stft, bandpass_filter, coherence, raw_normalization
                           # and raw_resampling then are what remains limited)
@@ -455,6 +455,28 @@ class HotPathEngine:
                                                      y.ctypes.data))
         return y
 
+    def nolds_probe(self, data: np.ndarray, starts: np.ndarray, want_series: bool = True) -> dict:
+        """``process_batch`` of a plan with nolds that also hands back what the sample-entropy kernel counted
+        (nmx_nolds_probe): ``"out"`` float32[n, row_width]; ``"A"``, ``"B"`` (uint32), ``"tol"`` (float32), ``"sum_zero"``
+        (bool), each [n, n_series, C] with the series raw first, then the bands; ``"series"`` float32[n, n_series, C, W]: the
+        samples the walk read (without the plan's carried offsets, which no difference sees).  For tests that judge the
+        counts, not only their logarithm, on the series the kernel itself read."""
+        data = np.asarray(data)
+        if data.ndim != 2 or data.shape[0] != self.C_in:
+            raise ValueError(f"expected data with {self.C_in} rows, got {data.shape}")
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        dc = self._host_offsets(data)
+        x = np.ascontiguousarray(data if dc is None else np.asarray(data, np.float64) - dc[:, None], dtype=np.float32)
+        n, S = len(starts), int(self.desc.nolds_raw) + int(self.desc.nolds_n_bands)
+        out = np.empty((n, self.row_width), np.float32)
+        a, b = np.zeros((n, S, self.C), np.uint32), np.zeros((n, S, self.C), np.uint32)
+        tol, zero = np.zeros((n, S, self.C), np.float32), np.zeros((n, S, self.C), np.uint8)
+        series = np.zeros((n, S, self.C, self.W), np.float32) if want_series else None
+        self.lib.check(self.lib.lib.nmx_nolds_probe(
+            self._plan, x.ctypes.data, _ld(x), x.shape[1], starts.ctypes.data, n, out.ctypes.data, a.ctypes.data,
+            b.ctypes.data, tol.ctypes.data, zero.ctypes.data, series.ctypes.data if series is not None else None))
+        return {"out": out, "A": a, "B": b, "tol": tol, "sum_zero": zero.astype(bool), "series": series}
+
     def timing_ms(self, which: int = 0) -> float:
         ms = C.c_float()
         self.lib.check(self.lib.lib.nmx_last_timing_ms(self._plan, which, C.byref(ms)))
@@ -463,7 +485,8 @@ class HotPathEngine:
     def kernels(self, which: int) -> str:
         """Kernels the last batch -- or the last ``preprocess_window`` / ``filter_window`` call -- launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
         5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
-        7 coherence, 8 grid projection), named as rocprofv3 prints them.  ``which = 9``: the launch geometry of the
+        7 coherence, 8 grid projection, 10 nolds: its band filters and the sample-entropy kernel), named as rocprofv3
+        prints them.  ``which = 9``: the launch geometry of the
         channel-pair FIR kernels of that launch sequence, ``"<kernel>: <n> pairs, <workgroups> x <waves> waves"``."""
         buf = C.create_string_buffer(512)
         self.lib.check(self.lib.lib.nmx_last_kernels(self._plan, which, buf, 512))

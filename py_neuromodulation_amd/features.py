@@ -22,7 +22,7 @@ from .engine import MAX_PLAN_WINDOW, HotPathEngine, long_segments
 FEATURE_DICT = {  # features/feature_processor.py:10-25 (hot-path subset)
     "raw_hjorth": "Hjorth", "return_raw": "Raw", "bandpass_filter": "BandPower", "stft": "STFT",
     "fft": "FFT", "welch": "Welch", "sharpwave_analysis": "SharpwaveAnalyzer", "bursts": "Bursts",
-    "linelength": "LineLength", "coherence": "Coherence",
+    "linelength": "LineLength", "coherence": "Coherence", "nolds": "Nolds",
 }
 
 
@@ -127,6 +127,12 @@ class SharpwaveAnalyzer(_EngineFeature):
 class Coherence(_EngineFeature):
     """features/coherence.py:151-253: coh / icoh between the channel pairs of ``coherence_settings.channels``"""
     feature_name = "coherence"
+
+
+class Nolds(_EngineFeature):
+    """features/nolds.py:32-100: sample entropy of every channel's window ("raw") and of band-pass series of it.  The
+    four other nolds measures raise ``NotImplementedError`` (the reference fits them with an unseeded RANSAC)."""
+    feature_name = "nolds"
 
 
 class HotPathFeatures(_EngineFeature):

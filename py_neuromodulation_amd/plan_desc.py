@@ -20,8 +20,15 @@ from .settings import validation_error
 _FEATURE_BITS = {"raw_hjorth": _lib.F_HJORTH, "return_raw": _lib.F_RAW,
                  "bandpass_filter": _lib.F_BANDPOWER, "stft": _lib.F_STFT, "fft": _lib.F_FFT,
                  "welch": _lib.F_WELCH, "sharpwave_analysis": _lib.F_SHARPWAVE,
-                 "bursts": _lib.F_BURSTS, "linelength": _lib.F_LINELENGTH, "coherence": _lib.F_COHERENCE}
-_OUT_OF_SCOPE = {"fooof", "nolds", "mne_connectivity", "bispectrum"}
+                 "bursts": _lib.F_BURSTS, "linelength": _lib.F_LINELENGTH, "coherence": _lib.F_COHERENCE,
+                 "nolds": _lib.F_NOLDS}
+_OUT_OF_SCOPE = {"fooof", "mne_connectivity", "bispectrum"}
+# nolds.sampen's default tolerance, as recalled for nolds >= 0.6.1 (it is not installed here: parity unpinned against
+# nolds itself): tol = std(x, ddof = 1) * 0.1164 * (0.5627 * ln(emb_dim) + 1.3334) with emb_dim = 2.  Formed here and
+# passed in the plan description -- the kernel (nmx_k_nolds.h) bakes in neither.
+NOLDS_TOL_FACTOR = 0.1164 * (0.5627 * float(np.log(2.0)) + 1.3334)
+NOLDS_DDOF = 1
+NOLDS_MAX_SAMPLES = 40000   # nmx_k_nolds.h: a series sits in the CU's LDS
 COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel
 _BURST_SLOTS = [("duration", ["duration_mean", "duration_max"]),
                 ("amplitude", ["amplitude_mean", "amplitude_max"]),
@@ -260,6 +267,8 @@ class PlanBuilder:
                 col = self._sharpwave(d, filters, col, sharpwave_taps)
             elif f == "coherence":
                 col = self._coherence(d, col)
+            elif f == "nolds":
+                col = self._nolds(d, col, bands, bank_taps)
         d.features = feats
         d.n_outputs = col
         if len(filters) > _lib.NMX_MAX_FILTERS:
@@ -433,3 +442,61 @@ class PlanBuilder:
         d.coh_cols = _cols(col, 0, len(methods) * slots, slots)
         self.coh_pairs = [(int(index[2 * i]), int(index[2 * i + 1])) for i in range(n_pairs)]
         return col + n_pairs * len(methods) * slots
+
+    def _nolds(self, d: PlanDesc, col: int, bands, bank_taps) -> int:
+        """features/nolds.py: the constructor's checks, the series (the window, then one band series per entry of
+        ``nolds_settings.frequency_bands``) and the keys, raw first, then band by band, channel-major inside each.
+
+        The band-index quirk, reproduced on purpose: the reference filters with the bank over ALL of
+        ``frequency_ranges_hz`` and reads ``data_filt[:, i, :]`` with ``i`` the position in nolds' OWN list
+        (nolds.py:59-65).  Key ``..._<nolds band i>`` therefore holds the entropy of GLOBAL band ``i`` -- with the
+        defaults ``..._low_beta`` is the theta series.  Same numbers under the same keys is the goal."""
+        st, sfreq = self.settings, self.sfreq
+        ns = st.nolds_settings
+        feats = _enabled(ns.features)
+        other = [f for f in feats if f != "sample_entropy"]
+        if other:
+            raise NotImplementedError(
+                f"nolds measures {other} are not implemented: the reference ends them in a line fit that defaults to "
+                "fit='RANSAC' -- scikit-learn's RANSACRegressor without a seed -- so two runs of the reference do not agree "
+                "with each other and no parity can be checked; only sample_entropy runs on the device")
+        names = [str(b).replace(" ", "_") for b in ns.frequency_bands]
+        if names:
+            # BandPower(settings, ch_names, sfreq, use_kf=False): its loop reads segment_lengths_ms[band] for every band
+            # of frequency_ranges_hz (bandpower.py:128-131)
+            seg = st.bandpass_filter_settings.segment_lengths_ms
+            for bname, _ in bands:
+                if bname not in seg:
+                    raise KeyError(bname)
+        for fb in names:
+            assert fb in st.frequency_ranges_hz, (
+                f"{fb} selected in nolds_features, but not defined in s['frequency_ranges_hz']")
+        if len(names) > len(bands):
+            raise IndexError(f"index {len(bands)} is out of bounds for axis 1 with size {len(bands)} (nolds reads band "
+                             "series by the position in nolds_settings.frequency_bands)")
+        if self.W > NOLDS_MAX_SAMPLES:
+            raise ValueError(f"nolds: a window of {self.W} samples exceeds the {NOLDS_MAX_SAMPLES}-sample limit of the "
+                             "sample-entropy kernel (the series has to fit the compute unit's local memory)")
+        raw = bool(ns.raw)
+        series = (["raw"] if raw else []) + names
+        if not feats or not series:
+            return col   # (nothing to compute: the reference emits no key either)
+        d.nolds_raw = int(raw)
+        d.nolds_n_bands = len(names)
+        for j in range(len(names)):
+            if bank_taps is not None:
+                taps = np.asarray(bank_taps)[j]
+            else:
+                taps = fir_design.band_pass_bank([bands[j][1]], sfreq)[0]
+            taps = np.asarray(taps, np.float64)
+            d.nolds_taps[j] = self._dptr(taps)
+            d.nolds_n_taps[j] = len(taps)
+        d.nolds_measures = sum(1 << _lib.NOLDS_MEASURES.index(f) for f in feats)
+        d.nolds_tol_factor = NOLDS_TOL_FACTOR
+        d.nolds_ddof = NOLDS_DDOF
+        C_ = self.C
+        d.nolds_cols = _cols(col, 1, C_, 0)
+        for sname in series:
+            for ch in self.ch_names:
+                self.keys += [f"{ch}_nolds_{f}_{sname}" for f in feats]
+        return col + len(series) * C_ * len(feats)

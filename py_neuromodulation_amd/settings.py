@@ -184,6 +184,10 @@ _SW_FEATURES = ["peak_left", "peak_right", "num_peaks", "trough", "width", "prom
 _SW_ON = {"prominence", "interval", "sharpness"}
 
 
+_NOLDS_FEATURES = ["sample_entropy", "correlation_dimension", "lyapunov_exponent", "hurst_exponent",
+                   "detrended_fluctuation_analysis"]
+
+
 def _osc(window_ms: int) -> dict:
     return {"windowlength_ms": window_ms, "log_transform": True,
             "features": {"mean": True, "median": False, "std": False, "max": False},
@@ -244,11 +248,14 @@ def _default_dict() -> dict:
         "coherence_settings": {"channels": [], "frequency_bands": ["high_beta"],
                                "features": {"mean_fband": True, "max_fband": True, "max_allfbands": True},
                                "method": {"coh": True, "icoh": True}, "nperseg": 128},
+        # features/nolds.py:14-25 (NoldsSettings / NoldsFeatures: the pydantic model's defaults)
+        "nolds_settings": {"raw": True, "frequency_bands": ["low_beta"],
+                           "features": {f: (f == "lyapunov_exponent") for f in _NOLDS_FEATURES}},
     }
 
 
 _SELECTOR_KEYS = {"features", "postprocessing", "preprocessing_filter", "bandpower_features", "burst_features",
-                  "sharpwave_features"}
+                  "sharpwave_features"}   # ("features" covers nolds_settings.features too: NoldsSettings)
 
 
 def _merge(base: dict, over: dict) -> dict:
@@ -277,6 +284,8 @@ def _build(key: str, v: Any) -> Any:
         return BoolSelector(**{k: bool(v.get(k, False)) for k in ("mean", "median", "std", "max")})
     if key == "coherence_settings" and isinstance(v, dict):
         return CoherenceSettings(**v)
+    if key == "nolds_settings" and isinstance(v, dict):
+        return NoldsSettings(**v)
     if isinstance(v, dict):
         cls = FeatureSelector if key == "features" else BoolSelector if key in _SELECTOR_KEYS else _Node
         return cls(**{k: _build(k, x) for k, x in v.items()})
@@ -310,6 +319,30 @@ class CoherenceSettings(_Node):
             out.append(f"coherence_settings.nperseg must be an int >= 1, got {n!r}")
         if len(self.frequency_bands) < 1:
             out.append("coherence_settings.frequency_bands needs at least one band")
+        return out
+
+
+class NoldsSettings(_Node):
+    """features/nolds.py:14-29.  ``features`` is a switch set (``get_enabled()``) also when a plain dict is assigned at run
+    time; band names get underscores for spaces (the reference's field validator)."""
+
+    def __setattr__(self, key, value) -> None:
+        if key == "features" and isinstance(value, dict):
+            value = BoolSelector(**{f: bool(value.get(f, False)) for f in _NOLDS_FEATURES},
+                                 **{k: v for k, v in value.items() if k not in _NOLDS_FEATURES})
+        elif key == "frequency_bands" and isinstance(value, (list, tuple)):
+            value = [str(f).replace(" ", "_") for f in value]
+        super().__setattr__(key, value)
+
+    def errors(self) -> list[str]:
+        out = []
+        if not isinstance(self.raw, (bool, np.bool_)):
+            out.append(f"nolds_settings.raw must be a bool, got {self.raw!r}")
+        if not isinstance(self.frequency_bands, list):
+            out.append(f"nolds_settings.frequency_bands must be a list of band names, got {self.frequency_bands!r}")
+        unknown = [k for k in self.features if k not in _NOLDS_FEATURES]
+        if unknown:
+            out.append(f"nolds_settings.features: unknown measures {unknown}")
         return out
 
 
@@ -412,6 +445,7 @@ class NMSettings(_Node):
         if self.bursts_settings.threshold < 0 or self.bursts_settings.time_duration_s < 0:
             errors.append("bursts_settings threshold / time_duration_s must be >= 0")
         errors += self.coherence_settings.errors()
+        errors += self.nolds_settings.errors()
         for name in ("project_cortex_settings", "project_subcortex_settings"):   # NMField(gt=0.0)
             v = self[name].max_dist_mm
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not v > 0:
