@@ -31,7 +31,10 @@
 // Time domain: the lane that owns 8 consecutive samples of a run also reads a 2-sample halo (left of an ascending run,
 // right of a descending one: the neighbour that is already in LDS) and advances its window's sums of u, u^2, d1^2,
 // d2^2, |d1| (u = x - pivot, the mean of four samples spread over the window) on PACKED arithmetic (two samples per instruction; the unaligned pairs the differences need
-// are one v_pk_mov each) in the shadow of the MFMAs; the four partial sums of a window meet once per tile.
+// are one v_pk_mov each) in the shadow of the MFMAs; the four partial sums of a window meet once per tile.  The
+// single-pass variance (q0 - s0^2 / W) / W cancels q0 / (q0 - s0^2 / W)-fold when the pivot sits off the window's mean (a
+// stimulation pulse on the pivot's samples): a window beyond NMX_SMM_CANCEL is flagged and left, like a window with a NaN,
+// to the wave-level kernel's two-pass form.
 // Conditions (host: nmx_specmm_ok): W = 1000, FFT over the whole window, band means only, bins inside 32 consecutive k
 // with k_lo >= 1, no Welch / STFT.  Device only.
 #pragma once
@@ -62,11 +65,21 @@ static inline bool nmx_specmm_ok(const NmxTimeOscArgs& A) {
   return true;
 }
 
+// Cancellation ratio q0 / (q0 - s0^2 / W) beyond which a window goes to the two-pass redo.  Error model: the relative
+// error of the activity is ratio x 2^-24 x roundings.  Roundings = 2: q0 and s0 are sums of 1000 terms over partial
+// accumulators and a tree, 0.85 x 2^-24 rms each under random rounding; s0^2 / W carries twice s0's and one more, and is
+// (ratio - 1) / ratio of q0 -- together 2.0 for a large ratio (measured on a float32 restatement with the pivot displaced to
+// ratios 1 .. 230: 1.0 - 2.2 rms, 3.4 - 7.1 at worst among 4000 windows).  8 x 2 x 2^-24 = 9.5e-7: a decade under the 1e-5
+// policy.  The pivot of a white-noise window sits half a spread (standard deviation) off its mean: a ratio of 8 is 5.3 of
+// those, one clean window in 8 million -- and such a window is only computed by the other kernel
+// (tests/test_timedomain_probes_cpu.py: white noise with offsets up to +-500 sets no bit).
+#define NMX_SMM_CANCEL 8.0f
+
 #ifdef NMX_HOST_EMU
 // ---- logic emulator (tests/emu, never loaded by the package): the kernel's ARITHMETIC for one (window, channel) -- the
 // twice-folded half-sample-phase contraction against the host's table, band means of log10 |Y| / |Y| over the plan's bin
-// ranges, the single-pass time domain about the window's first sample with telescoped difference sums, the overflow
-// flag for the wave-level redo -- without its machinery (DMA ring, MFMA operand layout, packed arithmetic): what the
+// ranges, the single-pass time domain about the device's pivot with telescoped difference sums, the overflow and
+// cancellation flags for the wave-level redo -- without its machinery (DMA ring, MFMA operand layout, packed arithmetic): what the
 // CPU tier can check is the table, the bin bookkeeping, the formulas and the flag protocol.  fp32 like the device,
 // summation orders differ (the tests hold both to the oracle).  -> true: the window is left to the redo pass.
 NMX_DEV bool nmx_specmm_item_emu(const NmxTimeOscArgs& A, int w, int c) {
@@ -94,7 +107,6 @@ NMX_DEV bool nmx_specmm_item_emu(const NmxTimeOscArgs& A, int w, int c) {
     }
   if (!(chk < INFINITY)) return true;   // a NaN / an infinity among the samples, or a power that overflows
   float* o = A.out + (long long)w * A.n_outputs;
-  for (int b = 0; b < A.n_bands; ++b) o[O.cols.base + c * O.cols.ch_stride + b * O.cols.a_stride] = bs[b] * O.inv_bins[b];
   if (A.features & (NMXD_F_HJORTH | NMXD_F_LINELENGTH | NMXD_F_RAW)) {
     const float p = 0.25f * ((x[0] + x[999]) + (x[499] + x[500]));   // (the device's pivot)
     // (64 partial sums per statistic, like the device's lanes, then a tree: one fp32 accumulator over 1000 terms would
@@ -114,7 +126,9 @@ NMX_DEV bool nmx_specmm_item_emu(const NmxTimeOscArgs& A, int w, int c) {
     const float u0 = x[0] - p, u1 = x[1] - p, u998 = x[998] - p, u999 = x[999] - p;
     const float rW = 1.f / 1000.f, rW1 = 1.f / 999.f, rW2 = 1.f / 998.f;
     const float sd1 = u999 - u0, sd2 = (u999 - u998) - (u1 - u0);   // telescoped sums of the differences
-    const float v0 = (q0 - s0 * s0 * rW) * rW, v1 = (q1 - sd1 * sd1 * rW1) * rW1, v2 = (q2 - sd2 * sd2 * rW2) * rW2;
+    const float cw = q0 - s0 * s0 * rW;
+    if (!(q0 <= NMX_SMM_CANCEL * cw)) return true;   // the pivot sits off the window's mean: the two-pass redo (nothing written)
+    const float v0 = cw * rW, v1 = (q1 - sd1 * sd1 * rW1) * rW1, v2 = (q2 - sd2 * sd2 * rW2) * rW2;
     const float a0 = v0 < 0.f ? 0.f : v0, a1 = v1 < 0.f ? 0.f : v1, a2 = v2 < 0.f ? 0.f : v2;
     const float act = nmx_clean(a0), mob = nmx_clean(sqrtf(a1 / a0)), comp = nmx_clean(sqrtf(a2 / a1) / mob);
     if (A.features & NMXD_F_HJORTH) {
@@ -126,6 +140,7 @@ NMX_DEV bool nmx_specmm_item_emu(const NmxTimeOscArgs& A, int w, int c) {
     if (A.features & NMXD_F_LINELENGTH) o[A.ll_cols.base + c * A.ll_cols.ch_stride] = sa * rW1 * rW1;
     if (A.features & NMXD_F_RAW) o[A.raw_cols.base + c * A.raw_cols.ch_stride] = x[999] + (A.dcf ? A.dcf[c] : 0.f);
   }
+  for (int b = 0; b < A.n_bands; ++b) o[O.cols.base + c * O.cols.ch_stride + b * O.cols.a_stride] = bs[b] * O.inv_bins[b];
   return false;
 }
 #endif
@@ -377,7 +392,9 @@ struct NmxSmmWave {
     if (FIRST) {
       // the pivot of the single-pass sums: the mean of x[0], x[499], x[500], x[999] -- all in step 0's buffer.  (It was x[0]
       // alone: behind a resampler or a notch the first sample of a window can sit several spreads off the rest -- an edge
-      // transient --, and q0 - s0^2 / W then cancels (1 + k^2)-fold: fuzz seed 102790, Hjorth mobility 1.8e-5 off.)
+      // transient --, and q0 - s0^2 / W then cancels (1 + k^2)-fold: fuzz seed 102790, Hjorth mobility 1.8e-5 off.  A pulse
+      // on these four samples still moves it -- activity 6e-5 off at 100 spreads: what cancels is flagged in finish(),
+      // NMX_SMM_CANCEL.)
       auto at = [&](unsigned a) { return cl(*(__attribute__((address_space(3))) const float*)(unsigned long)a); };
       N.pilot = 0.25f * ((at(cur + L.opilot) + at(cur + 6144 + L.opilot7)) + (at(cur + 2048 + L.opilot7) + at(cur + 4096 + L.opilot)));
     }
@@ -672,7 +689,7 @@ struct NmxSmmWave {
     chk += __shfl_xor(chk, 32, 64);
     // (also behind a stage that has cleaned the samples already: a re-referenced window with members of its group on the
     // rail holds +-1e38s -- its sums of squares are inf - inf here, the wave-level kernel's two-pass forms are not)
-    const bool dirty = !CLEAN && !(chk < INFINITY);
+    bool dirty = !CLEAN && !(chk < INFINITY);
     if (TD) {
       float s0 = T.es0 + (T.s0.x + T.s0.y), q0 = T.eq0 + ((T.q0[0].x + T.q0[0].y) + (T.q0[1].x + T.q0[1].y));
       float q1 = T.eq1 + ((T.q1[0].x + T.q1[0].y) + (T.q1[1].x + T.q1[1].y));
@@ -684,7 +701,11 @@ struct NmxSmmWave {
       q2 += __shfl_xor(q2, 32, 64); sa += __shfl_xor(sa, 32, 64);
       const float rW = 1.f / 1000.f, rW1 = 1.f / 999.f, rW2 = 1.f / 998.f;
       const float sd1 = T.u999 - T.u0, sd2 = (T.u999 - T.u998) - (T.u1 - T.u0);   // telescoped sums of the differences
-      const float v0 = (q0 - s0 * s0 * rW) * rW;
+      const float cw = q0 - s0 * s0 * rW;
+      // the pivot sits off the window's mean (a pulse on the pivot's own samples): q0 - s0^2 / W has lost its digits.
+      // (Whatever CLEAN: cleaning on load does not move a pivot back.)
+      if (!(q0 <= NMX_SMM_CANCEL * cw)) dirty = true;
+      const float v0 = cw * rW;
       const float v1 = (q1 - sd1 * sd1 * rW1) * rW1;
       const float v2 = (q2 - sd2 * sd2 * rW2) * rW2;
       float act, mob, comp;

@@ -238,7 +238,8 @@ extern "C" void nmx_wave_launch_timeosc_w1000(const NmxTimeOscArgs* A, int n_ite
 }
 
 // The windows the matrix-pipe kernel (nmx_k_specmm.h) flagged -- a NaN or an infinity among the samples: it does not clean
-// on load -- through the wave-level kernel's item code, which does.  One 16-bit mask per tile of that kernel (16
+// on load; a single-pass variance that cancels beyond NMX_SMM_CANCEL -- through the wave-level kernel's item code, which
+// cleans and sums in two passes.  One 16-bit mask per tile of that kernel (16
 // consecutive windows of a channel, tile = group * n_channels + channel); a wave looks at 64 masks at a time; a clean
 // recording never sets a bit.
 template <int NB>
