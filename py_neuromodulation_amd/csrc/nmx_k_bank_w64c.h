@@ -313,7 +313,7 @@ NMX_DEV void nmx_w64c_lane_setup(NmxW64cLane& Ln, const float* tile, const float
 // v[j] = (y_c, y_{c+1})[l + 64 j], j < 16.  Band-pass activity = variance of the tail [W - seglen, W) of both channels at
 // once (re / im); filtered series to HBM as lane-consecutive 4-byte stores, one row per channel.
 NMX_DEV void nmx_w64c_epilogue(const NmxBankW64Args& AA, const NmxFilterDev& F, const nmx_c2* v, int w, int c, int l, bool two,
-                               float* out_row) {
+                               float* out_row, bool first = true) {   // first = false: channel c is not this pass's (a split pair)
   const NmxBankArgs& A = AA.b;
   const int W = A.W;
   // ---- band-pass activity: variance of the tail [W - seglen, W), both channels at once (re / im) ------------------
@@ -349,7 +349,7 @@ NMX_DEV void nmx_w64c_epilogue(const NmxBankW64Args& AA, const NmxFilterDev& F, 
       t1 = nmx_wave_reduce(a2.x, 0.f, [](float a_, float b_) { return a_ + b_; });
       t2 = nmx_wave_reduce(a2.y, 0.f, [](float a_, float b_) { return a_ + b_; });
     }
-    if (l < 2 && (l == 0 || two)) {
+    if (l < 2 && (l == 0 ? first : two)) {
       const float act = (l == 0 ? t1 : t2) * inv_n;
       const int col = A.bp_cols.base + (c + l) * A.bp_cols.ch_stride + F.bp_band * A.bp_cols.a_stride;
       out_row[col] = nmx_bp_activity(A.bp_log ? log10f(act) : act, (A.bp_kalman_mask >> F.bp_band) & 1u);
@@ -362,7 +362,7 @@ NMX_DEV void nmx_w64c_epilogue(const NmxBankW64Args& AA, const NmxFilterDev& F, 
     float* d = dst ? dyb : dsw;
     if (!d) continue;
     const long long next = (long long)(dst ? A.n_burst_bands : A.n_sw_filters) * W;   // the same band of channel c + 1
-    const nmx_rsrc s1 = nmx_make_rsrc(d, 4 * W);
+    const nmx_rsrc s1 = nmx_make_rsrc(d, first ? 4 * W : 0);
     const nmx_rsrc s2 = nmx_make_rsrc(d + next, two ? 4 * W : 0);
     NMX_UNROLL
     for (int j = 0; j < 16; ++j) {
@@ -379,15 +379,22 @@ NMX_DEV void nmx_bank_w64c_item(const NmxBankW64Args& AA, int w, int c, const Nm
   const NmxBankArgs& A = AA.b;
   const int W = A.W;
   const int l = (int)(threadIdx.x & 63);
-  const bool two = c + 1 < A.n_channels;
+  const bool pair = c + 1 < A.n_channels;
   float* out_row = A.out ? A.out + (long long)w * A.n_outputs : nullptr;
   const float* src = A.x + (long long)c * A.ch_stride + (long long)w * A.win_stride +
                      (A.starts ? nmx_uniform_ll(A.starts[w]) : 0ll);
   nmx_c2 v[24], z[24];
   NMX_PROF_DECL
 
+  // solo 0: the pair.  Two channels whose scales lie more than 2^60 apart (a sample on the rail next to an ordinary
+  // channel) cannot share a transform -- the smaller one would be rounded away, or lost to the larger one's overflow:
+  // such a pair runs as solo 1 and solo 2, each channel beside a missing partner, as the last odd channel does.
+  int solo = 0;
+  do {
+  const bool first = solo != 2, two = pair && solo != 1;
+
   // ---- load: sample l + 64 j of channel c -> re, of channel c + 1 -> im (the row end is the buffer range check) ----
-  const nmx_rsrc r1 = nmx_make_rsrc(src, 4 * W);
+  const nmx_rsrc r1 = nmx_make_rsrc(src, first ? 4 * W : 0);
   const nmx_rsrc r2 = nmx_make_rsrc(src + A.ch_stride, two ? 4 * W : 0);
   NMX_UNROLL
   for (int j = 0; j < 16; ++j) {
@@ -399,7 +406,7 @@ NMX_DEV void nmx_bank_w64c_item(const NmxBankW64Args& AA, int w, int c, const Nm
     for (int j = 0; j < 16; ++j) v[j] = nmx_mk2(nmx_clean_bl(v[j].x), nmx_clean_bl(v[j].y));
   }
   if (A.dcf) {   // the offset the stream was split from (nmx_engine_dc.inc), on the samples that exist (not on the zero padding)
-    const nmx_c2 dd = nmx_mk2(A.dcf[c], two ? A.dcf[c + 1] : 0.f);
+    const nmx_c2 dd = nmx_mk2(first ? A.dcf[c] : 0.f, two ? A.dcf[c + 1] : 0.f);
     NMX_UNROLL
     for (int j = 0; j < 16; ++j) {
       if (64 * j + 63 < W) v[j] += dd;
@@ -415,6 +422,7 @@ NMX_DEV void nmx_bank_w64c_item(const NmxBankW64Args& AA, int w, int c, const Nm
   int e = 0;
   if (m1 > 0.f && m2 > 0.f) {
     e = __builtin_amdgcn_frexp_expf(m1) - __builtin_amdgcn_frexp_expf(m2);
+    if (solo == 0 && (e < -60 || e > 60)) { solo = 1; continue; }   // (wave-uniform: m1, m2 are wave maxima)
     e = e < -60 ? -60 : (e > 60 ? 60 : e);
   }
   NMX_UNROLL
@@ -450,9 +458,11 @@ NMX_DEV void nmx_bank_w64c_item(const NmxBankW64Args& AA, int w, int c, const Nm
     for (int j = 0; j < 16; ++j) v[j] = v[j] * unscale;
     NMX_PROF(3)
 
-    nmx_w64c_epilogue(AA, F, v, w, c, l, two, out_row);
+    nmx_w64c_epilogue(AA, F, v, w, c, l, two, out_row, first);
     NMX_PROF(5)
   }
+  solo = solo == 1 ? 2 : 0;
+  } while (solo);
 #if defined(NMX_BANK_PROFILE)
   if (w == 5 && (c == 2 || c == 40) && l == 0)
     printf("bank c profile w=%d c=%d: load+scale %lld | forward %lld | spectral %lld | inverse %lld | variance %lld | stores %lld "

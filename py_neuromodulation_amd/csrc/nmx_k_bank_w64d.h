@@ -35,7 +35,7 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
   nmx_c2* X = (nmx_c2*)(smem + AA.off_X);
   const int W = A.W;
   const int l = (int)(threadIdx.x & 63);
-  const bool two = c + 1 < A.n_channels;
+  const bool pair = c + 1 < A.n_channels;
   float* out_row = A.out ? A.out + (long long)w * A.n_outputs : nullptr;
   const float* src = A.x + (long long)c * A.ch_stride + (long long)w * A.win_stride +
                      (A.starts ? nmx_uniform_ll(A.starts[w]) : 0ll);
@@ -43,7 +43,13 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
   const nmx_c2* twC = twB + NMX_W64_TWB_N;
   nmx_c2 v[16], z[16];
 
-  const nmx_rsrc r1 = nmx_make_rsrc(src, 4 * W);
+  // solo 0: the pair.  Two channels whose scales lie more than 2^60 apart (a sample on the rail next to an ordinary
+  // channel) cannot share a transform -- the smaller one would be rounded away, or lost to the larger one's overflow:
+  // such a pair runs as solo 1 and solo 2, each channel beside a missing partner, as the last odd channel does.
+  int solo = 0;
+  do {
+  const bool first = solo != 2, two = pair && solo != 1;
+  const nmx_rsrc r1 = nmx_make_rsrc(src, first ? 4 * W : 0);
   const nmx_rsrc r2 = nmx_make_rsrc(src + A.ch_stride, two ? 4 * W : 0);
   NMX_UNROLL
   for (int j = 0; j < 16; ++j) {
@@ -64,6 +70,7 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
   int e = 0;
   if (m1 > 0.f && m2 > 0.f) {
     e = __builtin_amdgcn_frexp_expf(m1) - __builtin_amdgcn_frexp_expf(m2);
+    if (solo == 0 && (e < -60 || e > 60)) { solo = 1; continue; }   // (wave-uniform: m1, m2 are wave maxima)
     e = e < -60 ? -60 : (e > 60 ? 60 : e);
   }
   NMX_UNROLL
@@ -127,7 +134,7 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
         t1 = nmx_wave_reduce(a2.x, 0.f, add);
         t2 = nmx_wave_reduce(a2.y, 0.f, add);
       }
-      if (l < 2 && (l == 0 || two)) {
+      if (l < 2 && (l == 0 ? first : two)) {
         const float act = (l == 0 ? t1 : t2) * inv_n;
         const int col = A.bp_cols.base + (c + l) * A.bp_cols.ch_stride + F.bp_band * A.bp_cols.a_stride;
         out_row[col] = nmx_bp_activity(A.bp_log ? log10f(act) : act, (A.bp_kalman_mask >> F.bp_band) & 1u);
@@ -139,7 +146,7 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
       float* d = dst ? dyb : dsw;
       if (!d) continue;
       const long long next = (long long)(dst ? A.n_burst_bands : A.n_sw_filters) * W;
-      const nmx_rsrc s1 = nmx_make_rsrc(d, 4 * W);
+      const nmx_rsrc s1 = nmx_make_rsrc(d, first ? 4 * W : 0);
       const nmx_rsrc s2 = nmx_make_rsrc(d + next, two ? 4 * W : 0);
       NMX_UNROLL
       for (int i = 0; i < 16; ++i) {
@@ -150,5 +157,7 @@ NMX_DEV void nmx_bank_w64d_item(const NmxBankW64Args& AA, int w, int c, float* s
       }
     }
   }
+  solo = solo == 1 ? 2 : 0;
+  } while (solo);
 }
 #endif
