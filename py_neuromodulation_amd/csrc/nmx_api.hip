@@ -38,7 +38,12 @@ __global__ void __launch_bounds__(256) nmx_kern_timeosc(const NmxTimeOscArgs A) 
 __global__ void __launch_bounds__(256) nmx_kern_bank(const NmxBankArgs A, int n_items) {
   // one item per workgroup; partitioned mode (NmxBankArgs::ups_*): a workgroup walks items with its scratch slot
   for (int item = blockIdx.x; item < n_items; item += gridDim.x)
-    nmx_bank_item(A, item / A.n_channels, item % A.n_channels, nmx_smem, (int)blockIdx.x);
+    nmx_bank_item_t<false>(A, item / A.n_channels, item % A.n_channels, nmx_smem, (int)blockIdx.x);
+}
+// ... partitioned mode with band-pass power from differenced taps (NmxBankArgs::ups_diff_mask: windows above 16 384 samples)
+__global__ void __launch_bounds__(256) nmx_kern_bank_diff(const NmxBankArgs A, int n_items) {
+  for (int item = blockIdx.x; item < n_items; item += gridDim.x)
+    nmx_bank_item_t<true>(A, item / A.n_channels, item % A.n_channels, nmx_smem, (int)blockIdx.x);
 }
 template <int CH>
 __global__ void __launch_bounds__(256) nmx_kern_burst_thr(const NmxBurstThrArgs A) {
@@ -479,7 +484,8 @@ static void be_launch_timeosc_redo(const NmxTimeOscArgs& A, int n_items, be_stre
 }
 static void be_launch_bank(const NmxBankArgs& A, int n_items, int nt, size_t lds, be_stream_t s) {
   const int grid = (A.partitioned && n_items > NMX_UPS_SLOTS) ? NMX_UPS_SLOTS : n_items;
-  NMX_LAUNCH(nmx_kern_bank, dim3(grid), dim3(nt), lds, s, A, n_items);
+  if (A.ups_diff_mask) NMX_LAUNCH(nmx_kern_bank_diff, dim3(grid), dim3(nt), lds, s, A, n_items);
+  else NMX_LAUNCH(nmx_kern_bank, dim3(grid), dim3(nt), lds, s, A, n_items);
 }
 extern "C" void nmx_w64_launch_rd64(const NmxBankW64Args*, int, size_t, int, hipStream_t);
 extern "C" void nmx_w64x2_launch_rd64(const NmxBankW64Args*, int, int, hipStream_t);

@@ -75,19 +75,31 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   // refusal of such a plan is behaviour the suite pins (tests/timeosc_long_cases.py: a 20 000-sample plan with fft and bursts
   // raises): a plan that was refused stays refused until the caller asks.  Making it the default is this one test and the
   // default of this variable.
+  // Band-pass power above 16 384 samples is OPT-IN the same way (NMX_LONG_BANDPOWER=1): the partitioned bank then takes the
+  // derivative series of mobility and complexity from differenced taps (build_bank, nmx_k_bank.h: NmxBankArgs::ups_diff_mask).
   const bool long_bursts = env_int("NMX_LONG_BURSTS", 0) != 0;
+  const bool long_bandpower = env_int("NMX_LONG_BANDPOWER", 0) != 0;
   const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_NOLDS |
-                           (long_bursts ? NMX_F_BURSTS : 0u);
+                           (long_bursts ? NMX_F_BURSTS : 0u) | (long_bandpower ? NMX_F_BANDPOWER : 0u);
   const bool long_fits = desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0);
-  if (long_bursts)
-    NMX_REQUIRE(long_fits,
-                "window must be in [4, 16 384] samples for a plan with stft, bandpass_filter, coherence, raw_normalization or "
-                "raw_resampling; only raw_hjorth, return_raw, linelength, fft, welch, sharpwave_analysis and bursts run up to 40 000 samples, "
-                "behind re-referencing and FIR pre-processing");
-  NMX_REQUIRE(long_fits,
-              "window must be in [4, 16 384] samples for a plan with stft, bandpass_filter, bursts, coherence, raw_normalization or "
-              "raw_resampling; only raw_hjorth, return_raw, linelength, fft, welch and sharpwave_analysis run up to 40 000 samples, behind "
-              "re-referencing and FIR pre-processing (bursts too with NMX_LONG_BURSTS=1 in the environment)");
+  if (!long_fits) {
+    // one message, its two lists of names built from the two opt-ins: what stays limited in front of the ';', what runs up to
+    // 40 000 samples behind it, then the variable of every opt-in that is not set
+    std::string limited = "stft, ", runs = "raw_hjorth, return_raw, linelength, fft, welch", hint;
+    if (!long_bandpower) limited += "bandpass_filter, ";
+    if (!long_bursts) limited += "bursts, ";
+    limited += "coherence, raw_normalization or raw_resampling";
+    if (long_bursts && long_bandpower) runs += ", sharpwave_analysis, bursts and bandpass_filter";
+    else if (long_bursts) runs += ", sharpwave_analysis and bursts";
+    else if (long_bandpower) runs += ", sharpwave_analysis and bandpass_filter";
+    else runs += " and sharpwave_analysis";
+    if (!long_bursts && !long_bandpower)
+      hint = " (bursts too with NMX_LONG_BURSTS=1 in the environment, bandpass_filter with NMX_LONG_BANDPOWER=1)";
+    else if (!long_bursts) hint = " (bursts too with NMX_LONG_BURSTS=1 in the environment)";
+    else if (!long_bandpower) hint = " (bandpass_filter too with NMX_LONG_BANDPOWER=1 in the environment)";
+    return nmx_fail(NMX_E_INVALID, "window must be in [4, 16 384] samples for a plan with " + limited + "; only " + runs +
+                                       " run up to 40 000 samples, behind re-referencing and FIR pre-processing" + hint);
+  }
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");
   NMX_REQUIRE(desc->n_extra_cols >= 0 && (long long)desc->n_outputs + desc->n_extra_cols < (1ll << 30),

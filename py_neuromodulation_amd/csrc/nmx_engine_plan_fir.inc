@@ -307,26 +307,42 @@ int bank_partitioned_setup(Plan& P, NmxBankArgs& A, const std::vector<const doub
   A.off_red = A.off_b + al4(2 * B);
   A.lds_floats = A.off_red + 64;
   NMX_REQUIRE((size_t)A.lds_floats * 4 <= 160 * 1024, "window too long for the partitioned FIR kernel (> 40 384 samples)");
+  // (a filter of ups_diff_mask also runs its differenced taps, one tap longer on each side: NmxBankArgs::ups_diff_mask)
   int hm = 0;
-  for (int i = 0; i < A.n_filters; ++i) hm = std::max(hm, A.f[i].half);
+  for (int i = 0; i < A.n_filters; ++i) hm = std::max(hm, A.f[i].half + (int)((A.ups_diff_mask >> i) & 1u));
   A.ups_B = B;
   A.ups_hm = hm;
   A.ups_frames = (2 * hm + A.W - 1) / B + 1;   // blocks 0 .. (half_f + hm + W - 1) / B
   int rc;
   if ((rc = build_fft(P, B, &A.fft))) return rc;
-  for (int i = 0; i < A.n_filters; ++i) {
-    const int L = 2 * A.f[i].half + 1, np = (L + B - 1) / B;
-    std::vector<float> H((size_t)np * (B + 1) * 2);
-    std::vector<double> re(2 * B), im(2 * B);
-    for (int p = 0; p < np; ++p) {
+  std::vector<double> re(2 * B), im(2 * B);
+  // the partition spectra [ceil(n / B)][B + 1] of the taps t[0, n), appended to H
+  auto partitions = [&](const double* t, int n, std::vector<float>& H) {
+    for (int p = 0; p < (n + B - 1) / B; ++p) {
       std::fill(re.begin(), re.end(), 0.0);
       std::fill(im.begin(), im.end(), 0.0);
-      for (int j = 0; j < B && p * B + j < L; ++j) re[j] = taps[i][p * B + j];
+      for (int j = 0; j < B && p * B + j < n; ++j) re[j] = t[p * B + j];
       host_fft(re, im);
       for (int k = 0; k <= B; ++k) {
-        H[((size_t)p * (B + 1) + k) * 2] = (float)(re[k] / (2.0 * B));
-        H[((size_t)p * (B + 1) + k) * 2 + 1] = (float)(im[k] / (2.0 * B));
+        H.push_back((float)(re[k] / (2.0 * B)));
+        H.push_back((float)(im[k] / (2.0 * B)));
       }
+    }
+  };
+  for (int i = 0; i < A.n_filters; ++i) {
+    const int L = 2 * A.f[i].half + 1;
+    std::vector<float> H;
+    partitions(taps[i], L, H);
+    if ((A.ups_diff_mask >> i) & 1u) {
+      // g1[j] = h[j - 1] - h[j - 2], g2[j] = h[j] - 2 h[j - 1] + h[j - 2], j in [0, L + 2), in float64 from the live taps
+      auto h = [&](int j) { return j >= 0 && j < L ? taps[i][j] : 0.0; };
+      std::vector<double> g1(L + 2), g2(L + 2);
+      for (int j = 0; j < L + 2; ++j) {
+        g1[j] = h(j - 1) - h(j - 2);
+        g2[j] = (h(j) - h(j - 1)) - (h(j - 1) - h(j - 2));
+      }
+      if (A.bp_features & 6u) partitions(g1.data(), L + 2, H);   // (only the series the plan's features read)
+      if (A.bp_features & 4u) partitions(g2.data(), L + 2, H);
     }
     A.f[i].H = (const float*)upload(P, H.data(), H.size() * sizeof(float));
     if (!A.f[i].H) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
@@ -450,9 +466,18 @@ int build_bank(Plan& P) {
   // one-wave M = 2048 from W + reach = 513 on (513 .. 1024: the one-wave 1024-point path still beats the multi-wave LDS
   // Stockham of half the length, measured on BASELINE config 5)
   const bool fits_x2 = (d.window & 3) == 0 && !(d.bp_features & 6u);
+  // Above 16 384 samples (NMX_LONG_BANDPOWER: nmx_plan_create) mobility and complexity come from differenced taps: the
+  // second difference of a stored fp32 band series cancels to rounding noise at those rates (NmxBankArgs::ups_diff_mask).
+  // Below, the outputs are pinned and the epilogue stays as it is.  (Activity alone takes the same form with one series: only
+  // the output blocks that hold the tail are transformed.)
+  A.ups_diff_mask = 0;
+  if (d.window > 16384)
+    for (int i = 0; i < d.n_filters; ++i)
+      if (A.f[i].bp_seglen > 0) A.ups_diff_mask |= 1u << i;
   std::vector<std::vector<float>> H;
   int rc = build_fir_stage(P, live, FirRules{reach, 512, fits_x2, hil, ST_BANK}, &S, &H);
   if (rc) return rc;
+  NMX_REQUIRE(!A.ups_diff_mask || A.partitioned, "internal: band-pass power above 16 384 samples runs on the partitioned bank");
   if (hil && !A.partitioned) {
     A.hil_full = d.window & 1;
     if ((rc = build_fft(P, A.hil_full ? d.window : d.window / 2, &A.hil_r))) return rc;

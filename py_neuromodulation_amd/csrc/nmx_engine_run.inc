@@ -219,6 +219,7 @@ static ChunkSizes batch_chunk_sizes(const Plan& P, bool host) {
   // Long windows: the bursts chain's hand-off buffers -- the band series and the envelope of both chunk parities, hops x
   // channels x bands x window floats each -- bound the chunk (256 channels x 3 bands x 40 000 samples are 123 MB per hop and
   // buffer): as many hops as fit NMX_BURST_HANDOFF_MB together, never fewer than one.  Plans up to 16 384 samples keep theirs.
+  // (Band-pass power on long windows hands nothing off -- its series live and die in LDS -- and bounds no chunk.)
   if (P.have_bursts && P.d.window > 16384) {
     const double per_hop = 3.0 * P.d.n_channels * P.d.n_burst_bands * (double)P.d.window * sizeof(float);
     const int64_t cap = std::max<int64_t>(1, (int64_t)((double)P.burst_handoff_mb * 1048576.0 / per_hop));
@@ -506,6 +507,8 @@ int nmx_filter_window(nmx_plan* plan, const double* x, int64_t ldx, double* y) {
   view_into(A, WinView{(const float*)P.x_in.p, W, 0, nullptr, 0});
   A.out = nullptr;
   A.n_sw_filters = NF; A.sw_out = (float*)P.sharp.swy[0].p;
+  // (bp_seglen = 0 switches every epilogue off, the differenced-taps one of a long plan included -- A.out is null here: the
+  // plan's kernel runs, and every filter goes the whole-series way)
   for (int i = 0; i < NF; ++i) {
     A.f[i].sw_index = i; A.f[i].bp_seglen = 0; A.f[i].burst_index = -1; A.f[i].store_raw = 0;
   }

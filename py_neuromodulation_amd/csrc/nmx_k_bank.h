@@ -82,6 +82,17 @@ struct NmxBankArgs {
   float* yb_out;    // [n_windows][C][n_burst_bands][W]
   int ups_B, ups_frames, ups_hm;
   float2* ups_scratch;          // [gridDim.x][ups_frames][B + 1]
+  // DIFFERENCED-TAPS form of the band-pass power epilogue (bit f: filter f; plan windows above 16 384 samples only).  At
+  // 20 kHz a 13 - 20 Hz series moves by 5e-3 of its amplitude per sample, its second difference is 2.5e-5 of it, and each
+  // stored float32 y[n] carries 6e-8: d2y formed from y in LDS is rounding noise at the 1e-2 level and var(d2y) is biased
+  // upward (complexity 1e-4 off).  Differences of a zero-padded "same" convolution ARE convolutions with differenced taps,
+  //   g1[j] = h[j - 1] - h[j - 2]          (x * g1)[n] = y[n] - y[n - 1]               diff(y)[n]    = (x * g1)[n + 1]
+  //   g2[j] = h[j] - 2 h[j - 1] + h[j - 2]  (x * g2)[n] = y[n + 1] - 2 y[n] + y[n - 1]  diff(y, 2)[n] = (x * g2)[n + 1]
+  // both of length L + 2 (half length half + 1; g1 with a zero tap in front), formed in float64 on the host from the live
+  // taps (bank_partitioned_setup) and stored behind h's partition spectra: F.H = [P][B + 1] of h, [P'][B + 1] of g1,
+  // [P'][B + 1] of g2, P' = ceil((L + 2) / B).  The frame spectra are shared; each series takes the LDS in turn and is
+  // reduced to its two-pass variance over the tail before the next one (nmx_bank_item).
+  unsigned ups_diff_mask;
 };
 
 // partitioned overlap-save (NmxBankArgs::ups_*), step 1: the spectra of all frames of one (window, channel)
@@ -111,14 +122,14 @@ NMX_DEV void nmx_bank_ups_frames(const NmxBankArgs& A, const float* src, float2*
   NMX_SYNC();
 }
 
-// step 2: filter F of the item into y[0..W) (LDS)
-NMX_DEV void nmx_bank_ups_filter(const NmxBankArgs& A, const NmxFilterDev& F, const float2* S, float* y, float2* bufA,
-                                 float2* bufB) {
-  const int W = A.W, B = A.ups_B, Bh = B >> 1;
-  const int L = 2 * F.half + 1, P = (L + B - 1) / B;
-  const int off = F.half + A.ups_hm;   // y[n] = (h * u)[n + off]
-  const float2* NMX_RESTRICT H = (const float2*)F.H;
-  for (int b = off / B; b <= (off + W - 1) / B; ++b) {
+// step 2: the taps of half length `half` with partition spectra H, of the item, into y[n_lo..n_hi) (LDS): only the output
+// blocks that hold a sample of that range are transformed
+NMX_DEV void nmx_bank_ups_series(const NmxBankArgs& A, const float2* NMX_RESTRICT H, int half, const float2* S, float* y,
+                                 float2* bufA, float2* bufB, int n_lo, int n_hi) {
+  const int B = A.ups_B, Bh = B >> 1;
+  const int L = 2 * half + 1, P = (L + B - 1) / B;
+  const int off = half + A.ups_hm;   // y[n] = (h * u)[n + off]
+  for (int b = (off + n_lo) / B; b <= (off + n_hi - 1) / B; ++b) {
     const int pmax = (P - 1 < b) ? P - 1 : b;   // frames below 0 are zero
     for (int k = NMX_TID; k <= Bh; k += NMX_NT) {
       const int k2 = B - k;
@@ -136,13 +147,48 @@ NMX_DEV void nmx_bank_ups_filter(const NmxBankArgs& A, const NmxFilterDev& F, co
     const float* yf = (const float*)nmx_fft<+1>(A.fft, bufB, bufA, bufB);
     for (int i = NMX_TID; i < B; i += NMX_NT) {
       const int n = b * B + i - off;
-      if (n >= 0 && n < W) y[n] = yf[B + i];
+      if (n >= n_lo && n < n_hi) y[n] = yf[B + i];
     }
     NMX_SYNC();
   }
 }
+// ... filter F of the item into y[0..W)
+NMX_DEV void nmx_bank_ups_filter(const NmxBankArgs& A, const NmxFilterDev& F, const float2* S, float* y, float2* bufA,
+                                 float2* bufB) {
+  nmx_bank_ups_series(A, (const float2*)F.H, F.half, S, y, bufA, bufB, 0, A.W);
+}
 
-NMX_DEV void nmx_bank_item(const NmxBankArgs& A, int w, int c, float* smem, int slot = 0) {
+// Band-pass power of filter F from three series (NmxBankArgs::ups_diff_mask): y, then x * g1, then x * g2, each over the
+// tail only -- unless y leaves as a series (dst_a, dst_b) -- and each reduced before the next one takes the LDS.  The tail of y is
+// y[t0, W), t0 = W - seglen; diff(y) over it is (x * g1)[t0 + 1, W), diff(y, 2) is (x * g2)[t0 + 1, W - 1).
+NMX_DEV void nmx_bank_ups_power(const NmxBankArgs& A, const NmxFilterDev& F, const float2* S, float* y, float2* bufA,
+                                float2* bufB, float* red, float* dst_a, float* dst_b, float& act, float& mob, float& comp) {
+  const int W = A.W, B = A.ups_B, n = F.bp_seglen, t0 = W - n;
+  const float2* H = (const float2*)F.H;
+  const float2* H1 = H + (long long)((2 * F.half + B) / B) * (B + 1);          // behind the P partitions of h
+  const float2* H2 = H1 + (long long)((2 * F.half + 2 + B) / B) * (B + 1);     // behind the P' partitions of g1
+  const bool whole = dst_a || dst_b;
+  nmx_bank_ups_series(A, H, F.half, S, y, bufA, bufB, whole ? 0 : t0, W);
+  const float v0 = nmx_var(n, red, [&](int i) { return y[t0 + i]; });
+  act = v0;
+  mob = comp = 0.f;
+  if (dst_a) for (int i = NMX_TID; i < W; i += NMX_NT) dst_a[i] = y[i];
+  if (dst_b) for (int i = NMX_TID; i < W; i += NMX_NT) dst_b[i] = y[i];
+  if (!(A.bp_features & 6u)) return;
+  NMX_SYNC();
+  nmx_bank_ups_series(A, H1, F.half + 1, S, y, bufA, bufB, t0 + 1, W);
+  const float v1 = nmx_var(n - 1, red, [&](int i) { return y[t0 + 1 + i]; });
+  mob = sqrtf(v1 / v0);   // (bandpower.py:191; nan_to_num on the final values only, as nmx_hjorth mode 1)
+  if (!(A.bp_features & 4u)) return;
+  NMX_SYNC();
+  nmx_bank_ups_series(A, H2, F.half + 1, S, y, bufA, bufB, t0 + 1, W - 1);
+  const float v2 = nmx_var(n - 2, red, [&](int i) { return y[t0 + 1 + i]; });
+  comp = sqrtf(v2 / v1) / mob;
+}
+
+// DIFF: the item code of a launch with a differenced-taps filter (NmxBankArgs::ups_diff_mask; nmx_kern_bank_diff)
+template <bool DIFF>
+NMX_DEV void nmx_bank_item_t(const NmxBankArgs& A, int w, int c, float* smem, int slot = 0) {
   float2* X = (float2*)(smem + A.off_X);
   float2* bufA = (float2*)(smem + A.off_a);
   float2* bufB = (float2*)(smem + A.off_b);
@@ -158,6 +204,25 @@ NMX_DEV void nmx_bank_item(const NmxBankArgs& A, int w, int c, float* smem, int 
     nmx_bank_ups_frames(A, src, S, bufA, bufB, A.dcf ? A.dcf[c] : 0.f);
     for (int fi = 0; fi < A.n_filters; ++fi) {
       const NmxFilterDev& F = A.f[fi];
+      // (bp_seglen == 0: a launch without the epilogue and without an output row -- nmx_filter_window -- takes the whole series)
+      if (DIFF && F.bp_seglen > 0 && ((A.ups_diff_mask >> fi) & 1u)) {   // ---- band-pass power from differenced taps: three series in turn ----
+        // (a burst band, or a band the sharp-wave stage reads, still leaves its whole y before the derivatives take the LDS)
+        float* yb = F.burst_index >= 0 ? A.yb_out + (((long long)w * A.n_channels + c) * A.n_burst_bands + F.burst_index) * W : nullptr;
+        float* ys = F.sw_index >= 0 ? A.sw_out + (((long long)w * A.n_channels + c) * A.n_sw_filters + F.sw_index) * W : nullptr;
+        float act, mob, comp;
+        nmx_bank_ups_power(A, F, S, y, bufA, bufB, red, yb, ys, act, mob, comp);
+        if (NMX_TID == 0) {
+          int col = A.bp_cols.base + c * A.bp_cols.ch_stride + F.bp_band * A.bp_cols.a_stride;
+          if (A.bp_features & 1u) {
+            out_row[col] = nmx_bp_activity(A.bp_log ? log10f(act) : act, (A.bp_kalman_mask >> F.bp_band) & 1u);
+            col += A.bp_cols.b_stride;
+          }
+          if (A.bp_features & 2u) { out_row[col] = nmx_nan_to_num(mob); col += A.bp_cols.b_stride; }
+          if (A.bp_features & 4u) out_row[col] = nmx_nan_to_num(comp);
+        }
+        NMX_SYNC();
+        continue;
+      }
       nmx_bank_ups_filter(A, F, S, y, bufA, bufB);
       NMX_SYNC();
       if (F.bp_seglen > 0) {
@@ -313,4 +378,10 @@ NMX_DEV void nmx_bank_item(const NmxBankArgs& A, int w, int c, float* smem, int 
     }
     NMX_SYNC();
   }
+}
+
+// the item of any launch (the emulator's entry; the device kernels instantiate the form their launch needs)
+NMX_DEV void nmx_bank_item(const NmxBankArgs& A, int w, int c, float* smem, int slot = 0) {
+  if (A.ups_diff_mask) nmx_bank_item_t<true>(A, w, c, smem, slot);
+  else nmx_bank_item_t<false>(A, w, c, smem, slot);
 }
