@@ -243,7 +243,10 @@ struct NmxTimeOscArgs {
   // [off_a, off_spec) then holds the transform buffers of one subsequence (NmxOsc::split_d) over it
   int long_mode;
   int long_nb;             // floats per spectrum: max over FFT / Welch of k_hi - k_lo, rounded up to 4
-  int long_spec_slab;      // the accumulators + spectrum (3 long_nb floats) live in the workgroup's slab, not at off_spec
+  int long_spec_slab;      // the accumulators + spectrum (long_sp_floats) live in the workgroup's slab, not at off_spec
+  int long_sp_floats;      // floats of that region: 3 long_nb, or the STFT's accumulators + (k_hi - k_lo) x nseg spectrum if larger
+  int long_stft;           // STFT segment class (NMX_TOL_STFT_*, nmx_k_timeosc_long.h); 0: no STFT in this plan
+  int long_stft_acc;       // floats in front of the STFT spectrum: the accumulators of the split class, else 0
   int slab_floats;         // floats per slab (0: none needed)
   int slab_blocks;         // slabs allocated = resident workgroups of the persistent kernel
   float* slab;             // [slab_blocks][slab_floats] device memory owned by the plan (the emulator runs on slab 0)

@@ -66,8 +66,9 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   // 16 384 samples for a plan in general; up to 40 000 (the partitioned FIR stage's bound) for a plan whose window-sized
   // stages are all sized for it: the FIR stages (notch, preprocessing_filter, the sharp-wave pre-filters), re-referencing,
   // the sharp-wave analysis (long-window mode of build_sharp), the long-window time / oscillatory kernel (build_timeosc:
-  // Hjorth, raw, line length, FFT, Welch) and the bursts chain (partitioned bank, long Hilbert kernel, staged walk, scan
-  // statistics: build_hilbert, build_bursts)
+  // Hjorth, raw, line length, FFT, Welch, and STFT behind its opt-in), the bursts chain (partitioned bank, long Hilbert kernel,
+  // staged walk, scan statistics: build_hilbert, build_bursts) and coherence (nmx_coh_item reads its samples from the window view
+  // and keeps one segment of at most 4096 samples on chip)
   // (a plan of nolds alone takes any window from one sample on: the reference's Nolds does -- NaN below four samples)
   NMX_REQUIRE((desc->window >= 4 || (desc->features == NMX_F_NOLDS && desc->window >= 1)) && desc->window <= 40000,
               "window must be in [4, 40 000 samples]");
@@ -77,28 +78,41 @@ int nmx_plan_create(const nmx_plan_desc* desc, nmx_plan** out) {
   // default of this variable.
   // Band-pass power above 16 384 samples is OPT-IN the same way (NMX_LONG_BANDPOWER=1): the partitioned bank then takes the
   // derivative series of mobility and complexity from differenced taps (build_bank, nmx_k_bank.h: NmxBankArgs::ups_diff_mask).
-  const bool long_bursts = env_int("NMX_LONG_BURSTS", 0) != 0;
-  const bool long_bandpower = env_int("NMX_LONG_BANDPOWER", 0) != 0;
-  const uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_NOLDS |
-                           (long_bursts ? NMX_F_BURSTS : 0u) | (long_bandpower ? NMX_F_BANDPOWER : 0u);
+  // STFT and coherence above 16 384 samples are OPT-IN the same way (NMX_LONG_STFT=1, NMX_LONG_COHERENCE=1): the STFT phase of
+  // the long-window time / oscillatory kernel (nmx_k_timeosc_long.h), and the coherence stage on the long plan's window view.
+  struct LongOptIn { const char* name; const char* var; uint32_t feature; bool on; bool always_hinted; };
+  const LongOptIn opt_ins[] = {   // (in the order the "runs up to 40 000" list and the hint name them)
+      {"bursts", "NMX_LONG_BURSTS", NMX_F_BURSTS, env_int("NMX_LONG_BURSTS", 0) != 0, true},
+      {"bandpass_filter", "NMX_LONG_BANDPOWER", NMX_F_BANDPOWER, env_int("NMX_LONG_BANDPOWER", 0) != 0, true},
+      {"stft", "NMX_LONG_STFT", NMX_F_STFT, env_int("NMX_LONG_STFT", 0) != 0, false},
+      {"coherence", "NMX_LONG_COHERENCE", NMX_F_COHERENCE, env_int("NMX_LONG_COHERENCE", 0) != 0, false},
+  };
+  uint32_t long_ok = NMX_F_SHARPWAVE | NMX_F_HJORTH | NMX_F_RAW | NMX_F_LINELENGTH | NMX_F_FFT | NMX_F_WELCH | NMX_F_NOLDS;
+  for (const LongOptIn& o : opt_ins) if (o.on) long_ok |= o.feature;
   const bool long_fits = desc->window <= 16384 || (!(desc->features & ~long_ok) && desc->raw_norm_method <= 0 && desc->raw_window <= 0);
   if (!long_fits) {
-    // one message, its two lists of names built from the two opt-ins: what stays limited in front of the ';', what runs up to
-    // 40 000 samples behind it, then the variable of every opt-in that is not set
-    std::string limited = "stft, ", runs = "raw_hjorth, return_raw, linelength, fft, welch", hint;
-    if (!long_bandpower) limited += "bandpass_filter, ";
-    if (!long_bursts) limited += "bursts, ";
-    limited += "coherence, raw_normalization or raw_resampling";
-    if (long_bursts && long_bandpower) runs += ", sharpwave_analysis, bursts and bandpass_filter";
-    else if (long_bursts) runs += ", sharpwave_analysis and bursts";
-    else if (long_bandpower) runs += ", sharpwave_analysis and bandpass_filter";
-    else runs += " and sharpwave_analysis";
-    if (!long_bursts && !long_bandpower)
-      hint = " (bursts too with NMX_LONG_BURSTS=1 in the environment, bandpass_filter with NMX_LONG_BANDPOWER=1)";
-    else if (!long_bursts) hint = " (bursts too with NMX_LONG_BURSTS=1 in the environment)";
-    else if (!long_bandpower) hint = " (bandpass_filter too with NMX_LONG_BANDPOWER=1 in the environment)";
-    return nmx_fail(NMX_E_INVALID, "window must be in [4, 16 384] samples for a plan with " + limited + "; only " + runs +
-                                       " run up to 40 000 samples, behind re-referencing and FIR pre-processing" + hint);
+    // one message, its three parts built from the opt-ins: what stays limited in front of the ';', what runs up to 40 000
+    // samples behind it, then the variable of every opt-in that is not set.  (The hint names NMX_LONG_STFT / NMX_LONG_COHERENCE
+    // only to a plan that asks for that feature: the text a plan without them gets is the one it always got.)
+    auto join = [](const std::vector<std::string>& v, const char* last) {
+      std::string t;
+      for (size_t i = 0; i < v.size(); ++i) t += (i == 0 ? "" : i + 1 == v.size() ? last : ", ") + v[i];
+      return t;
+    };
+    std::vector<std::string> limited, runs = {"raw_hjorth", "return_raw", "linelength", "fft", "welch", "sharpwave_analysis"};
+    for (const char* name : {"stft", "bandpass_filter", "bursts", "coherence"})   // (the order the limited list always had)
+      for (const LongOptIn& o : opt_ins) if (!o.on && std::string(name) == o.name) limited.push_back(name);
+    limited.push_back("raw_normalization or raw_resampling");
+    std::string hint;
+    for (const LongOptIn& o : opt_ins) {
+      if (o.on) { runs.push_back(o.name); continue; }
+      if (!o.always_hinted && !(desc->features & o.feature)) continue;
+      hint += hint.empty() ? std::string(" (") + o.name + " too with " + o.var + "=1 in the environment"
+                           : std::string(", ") + o.name + " with " + o.var + "=1";
+    }
+    if (!hint.empty()) hint += ")";
+    return nmx_fail(NMX_E_INVALID, "window must be in [4, 16 384] samples for a plan with " + join(limited, ", ") + "; only " +
+                                       join(runs, " and ") + " run up to 40 000 samples, behind re-referencing and FIR pre-processing" + hint);
   }
   NMX_REQUIRE(desc->sfreq > 0 && desc->feat_hz > 0, "sfreq and feat_hz must be positive");
   NMX_REQUIRE(desc->n_outputs >= 1, "n_outputs must be >= 1");

@@ -145,8 +145,8 @@ int build_osc(Plan& P, const nmx_osc_desc& s, int kind, NmxOsc* o, int* cplx_len
   osc_bin_range(d, s, &o->k_lo, &o->k_hi);
   int nc = o->complex_full ? s.n : s.n / 2;
   if (lng) {
-    const char* fam = kind == 0 ? "fft" : "welch";
-    if (s.return_spectrum)
+    const char* fam = kind == 0 ? "fft" : kind == 1 ? "welch" : "stft";
+    if (s.return_spectrum && kind != 2)   // (the STFT phase has it: new code behind NMX_LONG_STFT)
       return nmx_fail(NMX_E_UNSUPPORTED, std::string(fam) + ": return_spectrum is not implemented in the long-window time/oscillatory "
                       "kernel (windows above 16 384 samples, or segments whose transform buffers do not fit LDS next to the window)");
     const int D = long_split(s.n);
@@ -211,6 +211,30 @@ int build_osc(Plan& P, const nmx_osc_desc& s, int kind, NmxOsc* o, int* cplx_len
       if (nv == s.n && s.n > 4) {   // the closed form (no n x nfreq trigonometric sums at plan time)
         wdc[2 * ((size_t)sel * o->nfreq)] = (float)(0.54 * s.n);
         wdc[2 * ((size_t)sel * o->nfreq + 1)] = (float)(-0.23 * s.n);
+        continue;
+      }
+      if (lng && s.n > 4) {
+        // long-window plans (nperseg up to 20 000: the sums below would be 10^8 sincos pairs): the truncated window's
+        // transform in closed form, float64 -- the hamming window is three exponentials, each a geometric sum over i < nv:
+        //   0.54 G(k) - 0.23 G(k - 1) - 0.23 G(k + 1),  G(m) = (1 - e^(-2 pi i m nv / n)) / (1 - e^(-2 pi i m / n)),  G(0) = nv
+        auto G = [&](int m, double* gr, double* gi) {
+          const long long mm = ((long long)m % s.n + s.n) % s.n;
+          if (mm == 0) { *gr = (double)nv; *gi = 0.0; return; }
+          const double a1 = -2.0 * kPi * (double)mm / s.n, an = -2.0 * kPi * (double)((mm * nv) % s.n) / s.n;
+          const double pr = 1.0 - std::cos(an), pi = -std::sin(an), qr = 1.0 - std::cos(a1), qi = -std::sin(a1);
+          const double q2 = qr * qr + qi * qi;
+          *gr = (pr * qr + pi * qi) / q2;
+          *gi = (pi * qr - pr * qi) / q2;
+        };
+        for (int k = 0; k < o->nfreq; ++k) {
+          double r0, i0, rm, im1, rp, ip;
+          G(k, &r0, &i0); G(k - 1, &rm, &im1); G(k + 1, &rp, &ip);
+          double re = 0.54 * r0 - 0.23 * (rm + rp), im = 0.54 * i0 - 0.23 * (im1 + ip);
+          if (std::fabs(re) < 1e-9 * s.n) re = 0;
+          if (std::fabs(im) < 1e-9 * s.n) im = 0;
+          wdc[2 * ((size_t)sel * o->nfreq + k)] = (float)re;
+          wdc[2 * ((size_t)sel * o->nfreq + k) + 1] = (float)im;
+        }
         continue;
       }
       for (int k = 0; k < o->nfreq; ++k) {
@@ -304,17 +328,25 @@ int build_timeosc(Plan& P) {
   // The long-window kernel (NMX_TO_LONG) takes every plan above 16 384 samples, and below that every plan without STFT whose
   // generic layout -- window + two transform buffers + spectrum -- does not fit LDS (FFT / Welch segments above ~13 650
   // samples).  A plan whose generic layout fits keeps it.
+  // With NMX_LONG_STFT=1 (the opt-in of nmx_plan_create) the same holds for plans with STFT; without it such a plan below
+  // 16 384 samples is laid out generically, and refused where that does not fit.
   bool lng = d.window > 16384;
-  if (!lng && !(d.features & NMX_F_STFT)) {
+  const bool long_stft = env_int("NMX_LONG_STFT", 0) != 0;
+  if (!lng && (!(d.features & NMX_F_STFT) || long_stft)) {
     int gc = 1, gs = 1;
-    for (int kind = 0; kind < 2; ++kind) {
-      const nmx_osc_desc& s = kind ? d.welch : d.fft;
-      if (!(d.features & (kind ? NMX_F_WELCH : NMX_F_FFT)) || s.n < 2 || s.n > d.window) continue;
+    for (int kind = 0; kind < 3; ++kind) {
+      const nmx_osc_desc& s = kind == 0 ? d.fft : kind == 1 ? d.welch : d.stft;
+      if (!(d.features & (kind == 0 ? NMX_F_FFT : kind == 1 ? NMX_F_WELCH : NMX_F_STFT)) || s.n < 2 || s.n > d.window) continue;
       int lo, hi;
       osc_bin_range(d, s, &lo, &hi);
       const int step = s.n - s.n / 2;
+      int nseg = kind ? (d.window - s.n) / step + 1 : 1;
+      if (kind == 2) {   // (build_osc: scipy's even extension and padding)
+        const int lext = d.window + 2 * (s.n / 2), nadd = ((-(lext - s.n)) % step + step) % step % s.n;
+        nseg = (lext + nadd - s.n) / step + 1;
+      }
       gc = std::max(gc, (s.n & 1) ? s.n : s.n / 2);
-      gs = std::max(gs, (hi - lo) * (kind ? (d.window - s.n) / step + 1 : 1));
+      gs = std::max(gs, (hi - lo) * nseg);
     }
     lng = ((long long)al4(d.window) + 2ll * al4(2 * gc) + al4(gs) + 64) * 4 > 160 * 1024;
   }
@@ -332,23 +364,37 @@ int build_timeosc(Plan& P) {
   // per-wave STFT needs room for (threads / 64) transforms of 250 points in each buffer
   A.stft_per_wave = (d.features & NMX_F_STFT) && maxc >= 250 * (S.nt / 64);
   A.long_mode = 0; A.long_nb = 0; A.long_spec_slab = 0; A.slab_floats = 0; A.slab_blocks = 0; A.slab = nullptr;
+  A.long_sp_floats = 0; A.long_stft = 0; A.long_stft_acc = 0;
   if (lng) {
-    NMX_REQUIRE(!(d.features & NMX_F_STFT), "internal: STFT in a long-window plan");
     // the window at [0, W) for the time-domain phase; then two transform buffers of one subsequence over it, the
     // accumulators (long_nb complex) and the spectrum (long_nb floats) behind them -- or in the workgroup's slab
     A.long_mode = 1;
     A.long_nb = 0;
     if (d.features & NMX_F_FFT) A.long_nb = std::max(A.long_nb, al4(A.fft.k_hi - A.fft.k_lo));
     if (d.features & NMX_F_WELCH) A.long_nb = std::max(A.long_nb, al4(A.welch.k_hi - A.welch.k_lo));
-    const bool osc = (d.features & (NMX_F_FFT | NMX_F_WELCH)) != 0;
+    A.long_sp_floats = 3 * A.long_nb;
+    if (d.features & NMX_F_STFT) {
+      // the segment class (nmx_k_timeosc_long.h).  The per-wave class is the device's (as in the generic item) and needs a
+      // slice of 250 complex points per wave in each buffer; the split class keeps accumulators in front of the spectrum
+      A.long_stft = A.stft.n <= 64 ? NMX_TOL_STFT_DIRECT : A.stft.split_d > 1 ? NMX_TOL_STFT_SPLIT : NMX_TOL_STFT_LDS;
+#ifndef NMX_HOST_EMU
+      if (A.stft.n == 500 && env_int("NMX_LONG_STFT_PER_WAVE", 1)) {
+        A.long_stft = NMX_TOL_STFT_WAVE500;
+        maxc = std::max(maxc, 250 * (512 / 64));   // (nmx_timeosc_long.hip: NMX_BLOCK_FIXED = 512)
+      }
+#endif
+      A.long_stft_acc = A.long_stft == NMX_TOL_STFT_SPLIT ? 2 * al4(A.stft.k_hi - A.stft.k_lo) : 0;
+      A.long_sp_floats = std::max(A.long_sp_floats, A.long_stft_acc + al4((A.stft.k_hi - A.stft.k_lo) * A.stft.nseg));
+    }
+    const bool osc = (d.features & (NMX_F_FFT | NMX_F_WELCH | NMX_F_STFT)) != 0;
     A.off_x = 0;
     A.off_a = 0;
     A.off_b = osc ? al4(2 * maxc) : 0;
     A.off_spec = osc ? A.off_b + al4(2 * maxc) : 0;
-    int end = A.off_spec + 3 * A.long_nb;
+    int end = A.off_spec + A.long_sp_floats;
     if ((size_t)(std::max(end, al4(A.W)) + 64) * 4 > 160 * 1024) {
       A.long_spec_slab = 1;
-      A.slab_floats = 3 * A.long_nb;
+      A.slab_floats = A.long_sp_floats;
       end = A.off_spec;
     }
     A.off_red = std::max(end, al4(A.W));

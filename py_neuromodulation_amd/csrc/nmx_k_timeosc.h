@@ -137,13 +137,13 @@ NMX_DEV float2 nmx_osc_bin(const NmxOsc& O, const float2* Z, int k) {
 }
 
 // long-window item (nmx_k_timeosc_long.h, at the end of this file)
-NMX_DEV void nmx_time_osc_long_item(const NmxTimeOscArgs& A, int w, int c, float* smem, float* slab);
+NMX_DEV void nmx_time_osc_long_item(const NmxTimeOscArgs& A, int w, int c, float* smem, float* slab, int stft_cls);
 
 NMX_DEV void nmx_time_osc_item(const NmxTimeOscArgs& A, int w, int c, float* smem) {
 #ifdef NMX_HOST_EMU
   // the emulator's launch interface carries no kernel choice: a long-window plan's items go to their own code, on slab 0
-  // (on the device NMX_TO_LONG launches nmx_kern_timeosc_long, which hands every workgroup its slab)
-  if (A.long_mode) { nmx_time_osc_long_item(A, w, c, smem, A.slab); return; }
+  // (on the device NMX_TO_LONG launches nmx_kern_timeosc_long / _long_stft<class>, which hand every workgroup its slab)
+  if (A.long_mode) { nmx_time_osc_long_item(A, w, c, smem, A.slab, A.long_stft); return; }
 #endif
   float* xs = smem + A.off_x;
   float2* bufA = (float2*)(smem + A.off_a);

@@ -28,8 +28,9 @@ from .plan_desc import COH_MAX_NPERSEG, PlanBuilder  # noqa: F401
 MAX_PLAN_WINDOW = 16384   # nmx_plan_create: window in [4, 16384] samples for a plan in general; the stand-alone filter objects cut longer
                           # recordings into segments of this length (a plan of raw_hjorth, return_raw, linelength, fft, welch, nolds and
                           # sharpwave_analysis, without raw normaliser or resampling, may be built up to 40 000 samples; with
-                          # NMX_LONG_BURSTS=1 in the environment bursts too, with NMX_LONG_BANDPOWER=1 bandpass_filter: stft,
-                          # coherence, raw_normalization and raw_resampling then are what remains limited)
+                          # NMX_LONG_BURSTS=1 in the environment bursts too, with NMX_LONG_BANDPOWER=1 bandpass_filter, with
+                          # NMX_LONG_STFT=1 stft, with NMX_LONG_COHERENCE=1 coherence: raw_normalization and raw_resampling then
+                          # are what remains limited)
 
 
 def long_segments(n_samples: int, halo: int, window: int = MAX_PLAN_WINDOW):

@@ -29,7 +29,7 @@ _OUT_OF_SCOPE = {"fooof", "mne_connectivity", "bispectrum"}
 NOLDS_TOL_FACTOR = 0.1164 * (0.5627 * float(np.log(2.0)) + 1.3334)
 NOLDS_DDOF = 1
 NOLDS_MAX_SAMPLES = 40000   # nmx_k_nolds.h: a series sits in the CU's LDS
-COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel
+COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel, at every window (above 16 384 samples too: NMX_LONG_COHERENCE)
 _BURST_SLOTS = [("duration", ["duration_mean", "duration_max"]),
                 ("amplitude", ["amplitude_mean", "amplitude_max"]),
                 ("burst_rate_per_s", ["burst_rate_per_s"]), ("in_burst", ["in_burst"])]
