@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 14
+#define NMX_ABI_VERSION 15
 
 /* error codes */
 #define NMX_OK 0
@@ -255,6 +255,16 @@ typedef struct {
    * features fill columns [0, n_outputs), the extra columns are left to an attached grid projection (nmx_proj below)
    * and hold NaN without one.  0 = today's layout. */
   int32_t n_extra_cols;
+
+  /* raw_resampling: the padding mode of the resampler (mne.filter.resample's `npad`).
+   *   resample_npad_mode == 0   "auto", the default (a zero-initialised field): pad to the next power of two with at least
+   *                             min(raw_window / 8, 100) samples per side (the default of Raw.resample)
+   *   resample_npad_mode == 1   resample_npad >= 0 samples per side (0 is legal: no padding); 100 is what the function
+   *                             mne.filter.resample itself defaults to, and so what the reference's call -- which passes
+   *                             no npad -- gets.  raw_window + 2 resample_npad <= 65 536.
+   * MNE parity of either mode is unpinned (MNE is absent from the reference tree). */
+  int32_t resample_npad_mode;
+  int32_t resample_npad;
 } nmx_plan_desc;
 
 typedef struct nmx_plan nmx_plan;
@@ -477,14 +487,19 @@ int nmx_reref_f64(int device, const double* ref_matrix, int n_out, int n_in, con
                   int64_t n_samples, double* y, int64_t ldy);
 
 /* The stand-alone Resampler in FLOAT64 (processing/resample.py:42-60: mne.filter.resample(x.astype(float64), up = ratio,
- * down = 1) -- FFT method, boxcar window, npad "auto", reflect_limited padding) for ANY window length (the reference's tests
+ * down = 1) -- FFT method, boxcar window, npad "auto" (nmx_resample_f64_npad: either padding mode), reflect_limited padding)
+ * for ANY window length (the reference's tests
  * resample 10 s at 4 kHz in one call, tests/test_nm_resample.py:8-47): y[n_channels][ldy] <- x[n_channels][ldx], n_out =
  * round(ratio * n_samples) (round-half-even, as Python's) samples per row.  Host pointers; power-of-two Stockham transforms
- * over HBM in float64, Bluestein's chirp convolution for a resampled padded length that is not a power of two
+ * over HBM in float64, Bluestein's chirp convolution for a padded or a resampled padded length that is not a power of two
  * (nmx_k_resample64.h).  NaN / inf samples spread over their row as in the reference.  Inside a plan the resampler runs on
  * fp32 windows in LDS (raw_window / resample_ratio of the plan description). */
 int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, int64_t n_samples, double ratio, double* y,
                      int64_t ldy, int64_t n_out);
+/* The same with the padding mode: npad < 0 is "auto" (nmx_resample_f64 forwards here with -1), npad >= 0 pads that many
+ * samples per side (100: the default of mne.filter.resample itself), n_samples + 2 npad <= 2^25. */
+int nmx_resample_f64_npad(int device, const double* x, int64_t ldx, int n_channels, int64_t n_samples, double ratio, double* y,
+                          int64_t ldy, int64_t n_out, int64_t npad);
 
 /* Host-side staging passes of the boundary (no device work; a few threads of their own, n_threads <= 0: an eighth of the machine, 4 .. 16).  They
  * replace what a NumPy host does at 1 - 3 GB/s around a batch call -- the reference hands float64 rows

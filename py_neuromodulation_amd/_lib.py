@@ -12,7 +12,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-NMX_ABI_VERSION = 14
+NMX_ABI_VERSION = 15
 NMX_MAX_BANDS = 16
 NMX_MAX_FILTERS = 24
 NMX_MAX_SW_COMBOS = 48
@@ -80,6 +80,7 @@ class PlanDesc(C.Structure):
         ("nolds_taps", C.POINTER(C.c_double) * NMX_MAX_BANDS), ("nolds_n_taps", C.c_int32 * NMX_MAX_BANDS),
         ("nolds_measures", C.c_uint32), ("nolds_tol_factor", C.c_double), ("nolds_ddof", C.c_int32), ("nolds_cols", Cols),
         ("n_extra_cols", C.c_int32),
+        ("resample_npad_mode", C.c_int32), ("resample_npad", C.c_int32),
     ]
 
 
@@ -102,6 +103,7 @@ _EXPORTS = [
     "nmx_norm_create", "nmx_norm_destroy", "nmx_norm_process", "nmx_norm_reset",
     "nmx_norm_state_size", "nmx_norm_state_export", "nmx_norm_state_import",
     "nmx_plan_attach_norm", "nmx_host_alloc", "nmx_host_free", "nmx_device_pool_trim", "nmx_reref_f64", "nmx_resample_f64",
+    "nmx_resample_f64_npad",
     "nmx_plan_carries_offsets", "nmx_plan_set_offsets", "nmx_plan_get_offsets", "nmx_plan_set_pipeline",
     "nmx_host_stage_rows", "nmx_host_group_sums", "nmx_host_stage_parts", "nmx_host_widen_rows",
     "nmx_proj_create", "nmx_proj_destroy", "nmx_proj_process", "nmx_plan_attach_proj", "nmx_nolds_probe",
@@ -182,6 +184,8 @@ class NmxLibrary:
         L.nmx_device_pool_trim.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
         L.nmx_resample_f64.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
                                        C.c_int64]
+        L.nmx_resample_f64_npad.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_void_p,
+                                            C.c_int64, C.c_int64, C.c_int64]
         L.nmx_reref_f64.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                     C.c_int64]
         L.nmx_plan_set_pipeline.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

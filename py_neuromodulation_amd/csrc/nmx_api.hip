@@ -88,7 +88,12 @@ __global__ void __launch_bounds__(256) nmx_kern_reref(const NmxRerefArgs A) {
 }
 __global__ void __launch_bounds__(256) nmx_kern_resample(const NmxResampleArgs A) {
   const int item = blockIdx.x;
-  nmx_resample_item(A, item / A.n_channels, item % A.n_channels, nmx_smem);
+  nmx_resample_body<0>(A, item / A.n_channels, item % A.n_channels, nmx_smem);
+}
+// the fixed pad (npad = n samples per side): lengths that are no powers of two (nmx_k_resample.h, GEN)
+__global__ void __launch_bounds__(256) nmx_kern_resample_npad(const NmxResampleArgs A) {
+  const int item = blockIdx.x;
+  nmx_resample_body<1>(A, item / A.n_channels, item % A.n_channels, nmx_smem);
 }
 __global__ void __launch_bounds__(64) nmx_kern_rawnorm_stats(const NmxRawNormArgs A) {
   nmx_rawnorm_stats_item(A, (int)blockIdx.x);
@@ -573,7 +578,8 @@ static void be_launch_reref(const NmxRerefArgs& A, be_stream_t s) {
   NMX_LAUNCH(nmx_kern_reref, grid, dim3(256), 0, s, A);
 }
 static void be_launch_resample(const NmxResampleArgs& A, int n_items, int nt, size_t lds, be_stream_t s) {
-  NMX_LAUNCH(nmx_kern_resample, dim3(n_items), dim3(nt), lds, s, A);
+  if (A.gen) NMX_LAUNCH(nmx_kern_resample_npad, dim3(n_items), dim3(nt), lds, s, A);
+  else NMX_LAUNCH(nmx_kern_resample, dim3(n_items), dim3(nt), lds, s, A);
 }
 static void be_launch_rawnorm(const NmxRawNormArgs& A, be_stream_t s) {
   if (A.method >= NMX_RAWNORM_MEDIAN && A.method != NMX_RAWNORM_POWER) {

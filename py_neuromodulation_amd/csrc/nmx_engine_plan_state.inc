@@ -179,10 +179,22 @@ int build_resample(Plan& P) {
   // Python round() is round-half-even; so is nearbyint in the default rounding mode
   const int final_len = (int)std::nearbyint(ratio * W);
   NMX_REQUIRE(final_len == d.window, "window must equal round(resample_ratio * raw_window)");
-  const int min_add = std::min(W / 8, 100) * 2;
-  int n_pad = 1;
-  while (n_pad < W + min_add) n_pad <<= 1;
-  const int pad_l = (n_pad - W) / 2;
+  // the padding mode (include/nmx.h): "auto" -- the next power of two -- or a fixed count per side
+  NMX_REQUIRE(d.resample_npad_mode == 0 || d.resample_npad_mode == 1, "resample_npad_mode must be 0 (\"auto\") or 1 (fixed)");
+  const bool fixed = d.resample_npad_mode == 1;
+  int n_pad = 1, pad_l;
+  if (fixed) {
+    NMX_REQUIRE(d.resample_npad >= 0, "resample_npad must be >= 0 samples per side");
+    NMX_REQUIRE((long long)W + 2ll * d.resample_npad <= 65536,
+                "raw_resampling: raw window " + spaced(W) + " + 2 x npad " + spaced(d.resample_npad) + " = " +
+                std::to_string((long long)W + 2ll * d.resample_npad) + " samples exceeds the padded limit of 65 536");
+    n_pad = W + 2 * d.resample_npad;
+    pad_l = d.resample_npad;
+  } else {
+    const int min_add = std::min(W / 8, 100) * 2;
+    while (n_pad < W + min_add) n_pad <<= 1;
+    pad_l = (n_pad - W) / 2;
+  }
   const int n_new = std::max((int)std::nearbyint(ratio * n_pad), 1);
   const int crop_l = (int)std::nearbyint(ratio * pad_l);
   NMX_REQUIRE(crop_l + final_len <= n_new, "internal: resample crop outside the output");
@@ -207,6 +219,46 @@ int build_resample(Plan& P) {
   };
   A.poly_q = A.poly_m = 0;
   A.tab_n = nullptr;
+  A.gen = fixed ? 1 : 0;
+  A.fwd_full = 0;
+  auto roots_of_n_pad = [&]() {
+    std::vector<float> tab(2 * (size_t)n_pad);
+    for (int j = 0; j < n_pad; ++j) {
+      const double a = -2.0 * kPi * (double)j / (double)n_pad;
+      tab[2 * j] = (float)std::cos(a);
+      tab[2 * j + 1] = (float)std::sin(a);
+    }
+    A.tab_n = (const float2*)upload(P, tab.data(), tab.size() * sizeof(float));
+    return A.tab_n ? 0 : nmx_fail(NMX_E_NOMEM, "table allocation failed");
+  };
+  auto max_prime = [](int n) {
+    int big = 1;
+    for (int p = 2; (long long)p * p <= n; ++p) while (n % p == 0) { big = std::max(big, p); n /= p; }
+    return std::max(big, n);
+  };
+  const std::string lens = "raw window " + spaced(W) + ", n_pad " + spaced(n_pad) + ", n_new " + spaced(n_new);
+  if (fixed) {
+    // fixed pad: n_pad = W + 2 npad is any length.  The one-transform form wherever its LDS layout fits (the 8192 gate
+    // below belongs to "auto"); n_pad odd: a full-length complex forward transform
+    NMX_REQUIRE(max_prime(n_new) <= 4096, "raw_resampling: the resampled padded length has a prime factor > 4096 (" + lens + ")");
+    const int n_fwd = (n_pad & 1) ? n_pad : n_pad / 2;
+    if (n_fwd >= 1 && n_fwd <= 32768 && layout(n_fwd, 1) && max_prime(n_fwd) <= 4096 && !env_int("NMX_RESAMPLE_POLY", 0)) {
+      A.fwd_full = n_pad & 1;
+      if ((rc = build_fft(P, n_fwd, &A.fwd))) return rc;
+    } else {
+      // long form: the smallest q in [2, 256] that divides n_pad and leaves m = n_pad / q <= 2048 points per component
+      // (every prime factor of m is then below 4096); an odd q leaves its last component unpaired
+      int q = 0;
+      for (int t = 2; t <= 256 && t < n_pad && !q; ++t)
+        if (n_pad % t == 0 && n_pad / t <= 2048 && layout(n_pad / t, 0)) q = t;
+      NMX_REQUIRE(q > 0, "raw_resampling: no polyphase split of the padded window (" + lens + "): n_pad needs a divisor q "
+                  "in [2, 256] with n_pad / q <= 2048 whose transforms and the resampled padded window fit the LDS");
+      A.poly_q = q;
+      A.poly_m = n_pad / q;
+      if ((rc = build_fft(P, A.poly_m, &A.fwd))) return rc;
+      if ((rc = roots_of_n_pad())) return rc;
+    }
+  } else
   if (n_pad <= 8192 && layout(n_pad / 2, 1) && !env_int("NMX_RESAMPLE_POLY", 0)) {
     if ((rc = build_fft(P, n_pad / 2, &A.fwd))) return rc;
   } else {
@@ -217,14 +269,7 @@ int build_resample(Plan& P) {
     A.poly_m = m;
     A.poly_q = n_pad / m;
     if ((rc = build_fft(P, m, &A.fwd))) return rc;
-    std::vector<float> tab(2 * (size_t)n_pad);
-    for (int j = 0; j < n_pad; ++j) {
-      const double a = -2.0 * kPi * (double)j / (double)n_pad;
-      tab[2 * j] = (float)std::cos(a);
-      tab[2 * j + 1] = (float)std::sin(a);
-    }
-    A.tab_n = (const float2*)upload(P, tab.data(), tab.size() * sizeof(float));
-    if (!A.tab_n) return nmx_fail(NMX_E_NOMEM, "table allocation failed");
+    if ((rc = roots_of_n_pad())) return rc;
   }
   if ((rc = build_fft(P, n_inv, &A.inv))) return rc;
   P.w_in = W;

@@ -580,6 +580,11 @@ int nmx_reref_f64(int device, const double* ref_matrix, int n_out, int n_in, con
 
 int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, int64_t n_samples, double ratio, double* y,
                      int64_t ldy, int64_t n_out) {
+  return nmx_resample_f64_npad(device, x, ldx, n_channels, n_samples, ratio, y, ldy, n_out, -1);
+}
+
+int nmx_resample_f64_npad(int device, const double* x, int64_t ldx, int n_channels, int64_t n_samples, double ratio, double* y,
+                          int64_t ldy, int64_t n_out, int64_t npad) {
   if (!x || !y) return nmx_fail(NMX_E_INVALID, "null argument");
   NMX_REQUIRE(n_channels >= 1 && n_samples >= 1 && n_samples <= (1ll << 24) && ldx >= n_samples,
               "nmx_resample_f64: n_channels >= 1, 1 <= n_samples <= 2^24, ldx >= n_samples");
@@ -588,34 +593,41 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
   const long long W = n_samples, final_len = (long long)std::nearbyint(ratio * (double)W);
   NMX_REQUIRE(final_len == n_out && ldy >= n_out, "nmx_resample_f64: n_out must equal round(ratio * n_samples) and ldy >= n_out");
   if (final_len == 0) return 0;
-  const long long min_add = std::min<long long>(W / 8, 100) * 2;
-  long long n_pad = 1;
-  while (n_pad < W + min_add) n_pad <<= 1;
-  const long long pad_l = (n_pad - W) / 2;
+  long long n_pad = 1, pad_l;
+  if (npad >= 0) {   // fixed pad: that many samples per side
+    NMX_REQUIRE(W + 2 * (long long)npad <= (1ll << 25), "nmx_resample_f64_npad: n_samples + 2 npad beyond 2^25 samples");
+    n_pad = W + 2 * (long long)npad;
+    pad_l = (long long)npad;
+  } else {
+    const long long min_add = std::min<long long>(W / 8, 100) * 2;
+    while (n_pad < W + min_add) n_pad <<= 1;
+    pad_l = (n_pad - W) / 2;
+  }
   const long long n_new = std::max<long long>((long long)std::nearbyint(ratio * (double)n_pad), 1);
   const long long crop_l = (long long)std::nearbyint(ratio * (double)pad_l);
   NMX_REQUIRE(crop_l + final_len <= n_new, "internal: resample crop outside the output");
   NMX_REQUIRE(n_new <= (1ll << 28), "nmx_resample_f64: resampled padded length beyond 2^28 samples");
-  long long L = 0;
+  long long L = 0, Lf = 0;
   if (n_new & (n_new - 1)) { L = 1; while (L < 2 * n_new - 1) L <<= 1; }
+  if (n_pad & (n_pad - 1)) { Lf = 1; while (Lf < 2 * n_pad - 1) Lf <<= 1; }
   if (be_device_count() <= 0) return nmx_fail(NMX_E_NODEVICE, "no HIP device");
   int rc = be_set_device(device);
   if (rc) return rc;
   const int C = n_channels;
-  const long long ld = std::max(std::max(n_pad, n_new), L);
+  const long long ld = std::max(std::max(n_pad, n_new), std::max(L, Lf));
   const size_t nx = (size_t)C * W * sizeof(double), ny = (size_t)C * final_len * sizeof(double);
-  const size_t nw = (size_t)C * ld * sizeof(NmxCplx64), nc = (size_t)L * sizeof(NmxCplx64);
+  const size_t nw = (size_t)C * ld * sizeof(NmxCplx64), nc = (size_t)std::max(L, Lf) * sizeof(NmxCplx64);
   char* d = (char*)be_alloc(nx + ny + 2 * nw + 2 * nc);
   if (!d) return nmx_fail(NMX_E_NOMEM, "nmx_resample_f64: device allocation of " + std::to_string(nx + ny + 2 * nw + 2 * nc) + " bytes failed");
   be_stream_t s = be_stream_create();
   NmxResample64Args A{};
   A.x = (const double*)d; A.ldx = W; A.y = (double*)(d + nx); A.ldy = final_len;
   A.a = (NmxCplx64*)(d + nx + ny); A.b = (NmxCplx64*)(d + nx + ny + nw); A.ld = ld; A.C = C;
-  A.W = W; A.W_new = final_len; A.n_pad = n_pad; A.pad_l = pad_l; A.n_new = n_new; A.crop_l = crop_l; A.L = L;
+  A.W = W; A.W_new = final_len; A.n_pad = n_pad; A.pad_l = pad_l; A.n_new = n_new; A.crop_l = crop_l; A.L = L; A.Lf = Lf;
   const long long use_len = std::min(n_new, n_pad);
   A.nyq_bin = (use_len % 2 == 0) ? use_len / 2 : -1;
   A.nyq_scale = n_new < n_pad ? 2.0 : 0.5;
-  A.scale = ratio / (double)n_new / (L ? (double)L : 1.0);
+  A.scale = ratio / (double)n_new / (L ? (double)L : 1.0) / (Lf ? (double)Lf : 1.0);
   be_h2d_2d_async(d, (size_t)W * sizeof(double), x, (size_t)ldx * sizeof(double), (size_t)W * sizeof(double), (size_t)C, s);
   // a power-of-two transform of `rows` rows: log2(n) Stockham stages between `cur` and `oth`; the result is in `cur`
   auto fft = [&](NmxCplx64*& cur, NmxCplx64*& oth, long long ldr, long long n, int sign, int rows) {
@@ -624,22 +636,27 @@ int nmx_resample_f64(int device, const double* x, int64_t ldx, int n_channels, i
       std::swap(cur, oth);
     }
   };
+  // Bluestein's chirp convolution, either side: `cur` holds the rows times exp(+i pi j^2 / M), zero-extended to Lb points; it
+  // leaves Lb x their circular convolution with exp(-i pi j^2 / M) in `cur` -- the unnormalised INVERSE transform of length M
+  // once bin j is multiplied by exp(+i pi j^2 / M) (OUT on the inverse side, MAP -- with the conjugate -- on the forward one)
+  auto chirp_conv = [&](NmxCplx64*& cur, NmxCplx64*& oth, long long M, long long Lb) {
+    NmxCplx64 *cc = (NmxCplx64*)(d + nx + ny + 2 * nw), *co = cc + std::max(L, Lf);
+    A.bM = M; A.bL = Lb;
+    be_launch_rs64_elem(A, NMX_RS64_CHIRP, nullptr, cc, Lb, 1, s);
+    fft(cc, co, Lb, Lb, -1, 1);
+    A.chirp = cc;
+    fft(cur, oth, ld, Lb, -1, C);
+    be_launch_rs64_elem(A, NMX_RS64_MUL, nullptr, cur, Lb, C, s);
+    fft(cur, oth, ld, Lb, +1, C);
+  };
   NmxCplx64 *cur = A.a, *oth = A.b;
-  be_launch_rs64_elem(A, NMX_RS64_PAD, nullptr, cur, n_pad, C, s);
-  fft(cur, oth, ld, n_pad, -1, C);
+  be_launch_rs64_elem(A, NMX_RS64_PAD, nullptr, cur, Lf ? Lf : n_pad, C, s);
+  if (!Lf) fft(cur, oth, ld, n_pad, -1, C);
+  else chirp_conv(cur, oth, n_pad, Lf);
   be_launch_rs64_elem(A, NMX_RS64_MAP, cur, oth, L ? L : n_new, C, s);
   std::swap(cur, oth);
-  if (!L) {
-    fft(cur, oth, ld, n_new, +1, C);
-  } else {
-    NmxCplx64 *cc = (NmxCplx64*)(d + nx + ny + 2 * nw), *co = cc + L;
-    be_launch_rs64_elem(A, NMX_RS64_CHIRP, nullptr, cc, L, 1, s);
-    fft(cc, co, L, L, -1, 1);
-    A.chirp = cc;
-    fft(cur, oth, ld, L, -1, C);
-    be_launch_rs64_elem(A, NMX_RS64_MUL, nullptr, cur, L, C, s);
-    fft(cur, oth, ld, L, +1, C);
-  }
+  if (!L) fft(cur, oth, ld, n_new, +1, C);
+  else chirp_conv(cur, oth, n_new, L);
   be_launch_rs64_elem(A, NMX_RS64_OUT, cur, nullptr, final_len, C, s);
   be_d2h_2d_async(y, (size_t)ldy * sizeof(double), d + nx, (size_t)final_len * sizeof(double), (size_t)final_len * sizeof(double),
                   (size_t)C, s);

@@ -315,8 +315,11 @@ class DataProcessor(UserViews):
                  device: int = 0, window: int | None = None, lib=None,
                  channel_subset=None, dry_run: bool = False,
                  resample_features_at_new_rate: bool = False, local_inputs: bool = False,
-                 staging_slot: int = 0, _family: tuple | None = None) -> None:
-        """``_family``: (PrepPlan, PostChain, LengthTable) of the processor this one is the twin of for another window
+                 staging_slot: int = 0, _family: tuple | None = None, resample_npad=None) -> None:
+        """``resample_npad``: the padding of raw_resampling, ``"auto"`` (the default) or an int >= 0 samples per side; 100 is
+        what the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
+
+        ``_family``: (PrepPlan, PostChain, LengthTable) of the processor this one is the twin of for another window
         length (`_twin`): the twin takes them instead of building its own.
 
         ``coord_names`` / ``coord_list`` / ``path_grids``: the contacts' coordinates and the directory of grid_cortex.tsv /
@@ -328,7 +331,8 @@ class DataProcessor(UserViews):
         self.channels = chmod.load_channels(channels)
         # (what a twin for another window length is built from: `process` under the reference's own loop, below)
         self._ctor = dict(sfreq=sfreq, line_noise=line_noise, verbose=verbose, device=device, lib=lib,
-                          resample_features_at_new_rate=resample_features_at_new_rate, staging_slot=staging_slot)
+                          resample_features_at_new_rate=resample_features_at_new_rate, staging_slot=staging_slot,
+                          resample_npad=resample_npad)
         self._twin_ok = channel_subset is None and not dry_run and not local_inputs
         self.sfreq_features, self._sfreq_raw_orig = st.sampling_rate_features_hz, sfreq
         self.line_noise, self.verbose = line_noise, verbose
@@ -337,7 +341,7 @@ class DataProcessor(UserViews):
             no_sharded_projection(st)
         if _family is None:
             proj = GridProjection(st, self.channels, coord_names, coord_list, path_grids) if projecting else None
-            prep = PrepPlan(st, self.channels, sfreq, line_noise, resample_features_at_new_rate)
+            prep = PrepPlan(st, self.channels, sfreq, line_noise, resample_features_at_new_rate, resample_npad)
             # (a channel shard leaves the user features to its coordinator, sharding.MultiDeviceProcessor: they see ALL channels)
             plugins = bool(_registered and not dry_run and channel_subset is None)
             _family = (prep, PostChain(st, prep.ch_names_used, proj, plugins, device, lib), None)

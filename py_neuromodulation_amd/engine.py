@@ -63,7 +63,7 @@ class HotPathEngine:
                  resample_from: float | None = None, raw_window: int | None = None,
                  pre_taps: Sequence[np.ndarray] | None = None,
                  raw_norm: tuple | None = None, resample_to: float | None = None, staging_slot: int = 0,
-                 extra_cols=0) -> None:
+                 extra_cols=0, resample_npad=None) -> None:
         """``sfreq`` is the rate every feature and filter is DESIGNED with (what the reference passes to the
         feature constructors).  ``resample_from`` = sampling rate of the incoming windows when they are
         resampled (raw_resampling, processing/resample.py:19-60): incoming windows then hold ``raw_window``
@@ -76,6 +76,9 @@ class HotPathEngine:
         to it as NumPy slicing / scipy.signal.welch do, band-pass tails are clamped, bursts keep
         seg_s = segment_length_features_ms / 1000).
 
+        ``resample_npad``: the resampler's padding, ``"auto"`` (the default) or an int >= 0 samples per side -- 100 is what
+        the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
+
         ``dry_run=True`` only derives the plan description and the key list (no library, no
         GPU) -- used to lay out the global column order when channels are sharded over GPUs.
 
@@ -84,7 +87,8 @@ class HotPathEngine:
         n_outputs + n_extra floats; 0 keeps the plain layout."""
         self.lib = None if dry_run else (lib if lib is not None else _lib.get_library())
         b = PlanBuilder(settings, ch_names, sfreq, features, window, resample_from, raw_window, resample_to, pre_taps,
-                        raw_norm)
+                        raw_norm, resample_npad)
+        self.resample_npad = b.resample_npad
         self.settings, self.ch_names, self.sfreq, self.C, self.enabled = b.settings, b.ch_names, b.sfreq, b.C, b.enabled
         self.W, self.W_in, self.resample_ratio = b.W, b.W_in, b.resample_ratio
         # (`_keep`: the arrays the C struct points into)

@@ -10,6 +10,8 @@ sharpwaves.py:169-197,302-326, bursts.py:119-125,262-298, linelength.py:17-19).
 from __future__ import annotations
 
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
@@ -43,13 +45,35 @@ def _cols(base=0, ch=0, a=0, b=0) -> Cols:
     return Cols(int(base), int(ch), int(a), int(b))
 
 
+def resample_npad_arg(value=None):
+    """The resampler's padding mode as the keyword ``resample_npad`` (``npad`` of ``processing.Resampler``) states it:
+    ``"auto"`` (the default: the next power of two, what ``Raw.resample`` defaults to) or an ``int >= 0``, that many samples
+    per side (100: the default of ``mne.filter.resample`` itself, which the reference's call gets).  ``None``: the
+    environment variable NMX_RESAMPLE_NPAD (``auto`` or an integer), ``"auto"`` without it.  Anything else: ValueError."""
+    if value is None:
+        text = os.environ.get("NMX_RESAMPLE_NPAD", "").strip()
+        if text == "" or text == "auto":
+            return "auto"
+        if not re.fullmatch(r"\+?[0-9]+", text):
+            raise ValueError(f"NMX_RESAMPLE_NPAD must be 'auto' or an integer >= 0, not {text!r}")
+        value = int(text)
+    if isinstance(value, str):
+        if value == "auto":
+            return "auto"
+        raise ValueError(f"resample_npad must be 'auto' or an int >= 0, not {value!r}")
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < 0:
+        raise ValueError(f"resample_npad must be 'auto' or an int >= 0, not {value!r}")
+    return int(value)
+
+
 class PlanBuilder:
     """The window geometry of one plan (``W`` samples the features see, ``W_in`` incoming, ``resample_ratio``), then
     ``build`` -> (PlanDesc, keys, coh_pairs, filter_taps, the arrays the struct points into).  HotPathEngine's arguments."""
 
     def __init__(self, settings, ch_names, sfreq, features=None, window=None, resample_from=None, raw_window=None,
-                 resample_to=None, pre_taps=None, raw_norm=None) -> None:
+                 resample_to=None, pre_taps=None, raw_norm=None, resample_npad=None) -> None:
         self.settings = settings
+        self.resample_npad = resample_npad_arg(resample_npad)
         self.ch_names = list(ch_names)
         self.sfreq = float(sfreq)
         self.C = len(self.ch_names)
@@ -141,6 +165,11 @@ class PlanBuilder:
         if self.resample_ratio:
             d.raw_window = int(self.W_in)
             d.resample_ratio = float(self.resample_ratio)
+            if self.resample_npad != "auto":
+                if self.W_in + 2 * self.resample_npad > 65536:
+                    raise ValueError(f"raw_resampling: raw window {self.W_in} + 2 x resample_npad {self.resample_npad} = "
+                                     f"{self.W_in + 2 * self.resample_npad} samples exceeds the padded limit of 65 536")
+                d.resample_npad_mode, d.resample_npad = 1, int(self.resample_npad)
         if self._raw_norm is not None:              # raw_normalization, last pre-processor
             method, clip, n_hist, add = self._raw_norm
             # "quantile": scikit-learn's QuantileTransformer subsamples histories of more than 10 000 samples at random

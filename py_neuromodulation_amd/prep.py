@@ -21,8 +21,12 @@ class PrepPlan:
     add samples), ``resample_to`` (None: no resampler), ``sfreq_design`` (the rate the features are designed with) and
     ``matrix`` (the folded [C, C_all] channel pick x re-reference, None: the identity)."""
 
-    def __init__(self, settings, channels, sfreq, line_noise=None, resample_features_at_new_rate: bool = False) -> None:
+    def __init__(self, settings, channels, sfreq, line_noise=None, resample_features_at_new_rate: bool = False,
+                 resample_npad=None) -> None:
+        from .plan_desc import resample_npad_arg
+
         st = settings
+        self.resample_npad = resample_npad_arg(resample_npad)   # "auto" or samples per side (keyword, else NMX_RESAMPLE_NPAD)
         self.sfreq_raw = sfreq // 1
         self.ch_names_used, self.feature_idx, self.target_idx = chmod.channel_info(channels)
         self.notch_taps = self.pre_taps = self.raw_norm = self.resample_to = self.ref_matrix = None
@@ -80,7 +84,8 @@ class PrepPlan:
                   raw_norm=self.raw_norm)
         if self.resample_to is None:
             return dict(kw, window=window)
-        return dict(kw, resample_from=self.sfreq_raw, resample_to=self.resample_to, raw_window=window)
+        return dict(kw, resample_from=self.sfreq_raw, resample_to=self.resample_to, raw_window=window,
+                    resample_npad=self.resample_npad)
 
 
 class LocalInput:

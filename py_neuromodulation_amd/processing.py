@@ -151,9 +151,14 @@ class Resampler:
     """processing/resample.py:19-60 as a stand-alone object: ``mne.filter.resample(data.astype(float64), up = new / old,
     down = 1)`` along the last axis (FFT method, reflect_limited padding) in FLOAT64 on the device, for any window length
     (nmx_resample_f64; the reference's tests resample 10 s of data in one call); identity at ratio 1 like the reference.
-    Inside ``DataProcessor`` / ``Stream`` the resampler is a stage of the plan on its fp32 windows."""
+    Inside ``DataProcessor`` / ``Stream`` the resampler is a stage of the plan on its fp32 windows.  ``npad``: ``"auto"``
+    (the default) or an int >= 0 samples per side -- 100 is what the reference's call gets, ``mne.filter.resample``'s own
+    default (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD)."""
 
-    def __init__(self, sfreq: float, resample_freq_hz: float, device: int = 0, **kwargs) -> None:
+    def __init__(self, sfreq: float, resample_freq_hz: float, device: int = 0, npad=None, **kwargs) -> None:
+        from .plan_desc import resample_npad_arg
+
+        self.npad = resample_npad_arg(npad)
         self.sfreq = float(sfreq)
         self.resample_freq_hz = float(resample_freq_hz)
         ratio = float(resample_freq_hz / sfreq)
@@ -171,8 +176,9 @@ class Resampler:
         n_out = int(round(self.up * x.shape[1]))
         y = np.empty((x.shape[0], n_out), np.float64)
         if x.shape[0] and x.shape[1]:
-            lib.check(lib.lib.nmx_resample_f64(self.device, x.ctypes.data, x.shape[1], x.shape[0], x.shape[1], self.up,
-                                               y.ctypes.data, max(n_out, 1), n_out))
+            lib.check(lib.lib.nmx_resample_f64_npad(self.device, x.ctypes.data, x.shape[1], x.shape[0], x.shape[1], self.up,
+                                                    y.ctypes.data, max(n_out, 1), n_out,
+                                                    -1 if self.npad == "auto" else self.npad))
         return y.reshape(data.shape[:-1] + (n_out,))
 
 

@@ -54,8 +54,10 @@ class ShardedStream:
     """One rank of a channel-sharded offline stream."""
 
     def __init__(self, sfreq, channels, settings=None, line_noise=50, rank: int = 0,
-                 world_size: int = 1, device: int | None = None, lib=None, local_input: bool = False) -> None:
+                 world_size: int = 1, device: int | None = None, lib=None, local_input: bool = False,
+                 resample_npad=None) -> None:
         self.sfreq = sfreq
+        self.resample_npad = resample_npad   # raw_resampling's padding: "auto" or samples per side (DataProcessor)
         self.settings = NMSettings.load(settings)
         no_sharded_projection(self.settings)
         self.channels = chmod.load_channels(channels)
@@ -83,7 +85,7 @@ class ShardedStream:
                 "Stream(devices=[...]) (sharding.MultiDeviceProcessor) instead of one rank per GPU")
         return DataProcessor(self.sfreq, self.settings, self.channels, line_noise=self.line_noise, verbose=False,
                              device=self.device, window=window, lib=self._lib, channel_subset=self.shard,
-                             local_inputs=self.local_input, dry_run=dry_run)
+                             local_inputs=self.local_input, dry_run=dry_run, resample_npad=self.resample_npad)
 
     def _comm_device(self, group=None):
         """Where the tensors of a collective must live: this rank's GPU under the "nccl" backend (= RCCL, which
@@ -201,7 +203,8 @@ class MultiDeviceProcessor(UserViews):
     ``local_input=False`` hands every device the whole recording and its rows of the folded matrix."""
 
     def __init__(self, sfreq, settings, channels, line_noise=None, devices=(0,), window=None, lib=None,
-                 verbose: bool = False, resample_features_at_new_rate: bool = False, local_input: bool = True) -> None:
+                 verbose: bool = False, resample_features_at_new_rate: bool = False, local_input: bool = True,
+                 resample_npad=None) -> None:
         from concurrent.futures import ThreadPoolExecutor
 
         self.settings = NMSettings.load(settings)
@@ -212,7 +215,7 @@ class MultiDeviceProcessor(UserViews):
             raise ValueError("devices must name at least one GPU")
         names, _, _ = chmod.channel_info(self.channels)
         kw = dict(line_noise=line_noise, verbose=False, window=window, lib=lib,
-                  resample_features_at_new_rate=resample_features_at_new_rate)
+                  resample_features_at_new_rate=resample_features_at_new_rate, resample_npad=resample_npad)
         layout = DataProcessor(sfreq, self.settings, self.channels, dry_run=True, **kw)
         self.sfreq_raw = layout.sfreq_raw
         self.ch_names_used = layout.ch_names_used
