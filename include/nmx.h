@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 15
+#define NMX_ABI_VERSION 16
 
 /* error codes */
 #define NMX_OK 0
@@ -58,7 +58,8 @@ extern "C" {
 #define NMX_F_COHERENCE (1u << 9)  /* features/coherence.py (pairs of channels) */
 #define NMX_F_NOLDS (1u << 10)     /* features/nolds.py (sample entropy)        */
 
-/* measures of the nolds family, NoldsFeatures field order (features/nolds.py:14-19); only NMX_NOLDS_SAMPEN has a kernel */
+/* measures of the nolds family, NoldsFeatures field order (features/nolds.py:14-19); NMX_NOLDS_SAMPEN has a kernel, and
+ * NMX_NOLDS_DFA one for the final fit "poly" (nolds_dfa_fit below) */
 #define NMX_NOLDS_SAMPEN 1u
 #define NMX_NOLDS_CORR_DIM 2u
 #define NMX_NOLDS_LYAP 4u
@@ -239,9 +240,10 @@ typedef struct {
    *                     -- the reference reads data_filt[:, j, :] of the bank over ALL frequency_ranges_hz with j the position
    *                     in ITS OWN band list, so series j is global band j under the key of nolds band j: the host resolves
    *                     that and hands over the taps it means
-   *   nolds_measures    NMX_NOLDS_* bit mask; anything but NMX_NOLDS_SAMPEN -> NMX_E_UNSUPPORTED
+   *   nolds_measures    NMX_NOLDS_* bit mask; anything but NMX_NOLDS_SAMPEN, and NMX_NOLDS_DFA with nolds_dfa_fit = 1 (below),
+   *                     -> NMX_E_UNSUPPORTED
    *   nolds_tol_factor  tol = nolds_tol_factor * std(x, ddof = nolds_ddof), both formed on the host
-   *   nolds_cols        a = series (raw first, then the bands in list order) */
+   *   nolds_cols        sample entropy: a = series (raw first, then the bands in list order) */
   int32_t nolds_raw;
   int32_t nolds_n_bands;
   const double* nolds_taps[NMX_MAX_BANDS];
@@ -265,6 +267,26 @@ typedef struct {
    * MNE parity of either mode is unpinned (MNE is absent from the reference tree). */
   int32_t resample_npad_mode;
   int32_t resample_npad;
+
+  /* nolds: detrended fluctuation analysis (NMX_NOLDS_DFA of nolds_measures) of the stage's series -- nolds.dfa(x) with its
+   * defaults (order 1, overlapping chunks, fit_trend "poly") but the final log-log line fit "poly" instead of nolds' default
+   * "RANSAC" (scikit-learn's unseeded RANSACRegressor: two runs of the reference disagree).  All zero = off.
+   *   nolds_dfa_fit       0: no DFA (NMX_NOLDS_DFA in nolds_measures -> NMX_E_UNSUPPORTED); 1: "poly", least squares
+   *   nolds_dfa_scales    [nolds_dfa_n_scales] chunk lengths n, ascending, 2 <= n < window, 2 .. 64 of them (copied at plan
+   *                       creation): FORMED ON THE HOST (nolds: logarithmic_n(4, 0.1 N, 1.2) above 70 samples) -- the kernel
+   *                       bakes in neither the table nor its rule.  walk = cumsum(x - mean); per scale the chunks
+   *                       walk[i : i + n], i = 0, n / 2, ... < window - n; F(n) = mean over the chunks of
+   *                       sqrt(mean squared residual of the chunk's least-squares line)
+   *   value               slope of ln F on ln n over the scales with F(n) != 0; NaN when fewer than TWO are left (nolds: NaN
+   *                       for none, the minimum-norm solution of the under-determined fit for one); 0 when the series' float64
+   *                       sum is exactly 0 (the reference's wrapper)
+   *   nolds_dfa_cols      a = series, as nolds_cols.  With both measures on, sample_entropy comes first inside a series and
+   *                       a channel (the reference's get_enabled() order): the two column sets interleave.
+   * Parity with nolds itself is unpinned (it is not installed where the tests run), as for the sample entropy. */
+  int32_t nolds_dfa_fit;
+  int32_t nolds_dfa_n_scales;
+  const int32_t* nolds_dfa_scales;
+  nmx_cols nolds_dfa_cols;
 } nmx_plan_desc;
 
 typedef struct nmx_plan nmx_plan;
@@ -357,7 +379,7 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
  * which = 0 whole batch, 1 pre-processing, 2 time/oscillatory kernel, 3 FIR-bank kernel,
  * 4 bursts kernels, 5 sharp-wave kernel, 6 second FIR-bank launch (the filters whose taps are too long for the
  * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel, 8 grid-projection kernel (attached nmx_proj),
- * 10 the nolds stage (its band filters and the sample-entropy kernel; 9 is no timer: see nmx_last_kernels).
+ * 10 the nolds stage (its band filters, the sample-entropy kernel and the DFA kernel; 9 is no timer: see nmx_last_kernels).
  * Stages 1..10 are those of the first chunk of the batch.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
@@ -382,6 +404,16 @@ int nmx_last_kernels(nmx_plan* plan, int which, char* buf, int64_t n);
  * logarithm, on the series the kernel itself read.  NMX_E_INVALID for a plan without a nolds stage. */
 int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
                     float* out, uint32_t* a, uint32_t* b, float* tol, uint8_t* sum_zero, float* series);
+
+/* The same for the DFA kernel of a plan with NMX_NOLDS_DFA, item by item ([n_windows][n_series][n_channels]):
+ *   fluct     [...][nolds_dfa_n_scales] float64: F(n) of every scale of the table (0 where the kernel dropped the scale)
+ *   alpha     float64 slope of the kept scales (NaN with fewer than two), BEFORE the sum rule
+ *   sum_zero  1 when the float64 sum of the series is exactly 0 (the row then holds 0)
+ *   n_kept    scales with F(n) != 0
+ *   series    [...][window] float32: the samples the kernel read
+ * out and every array may be NULL.  NMX_E_INVALID for a plan without a DFA kernel. */
+int nmx_nolds_dfa_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                        float* out, double* fluct, double* alpha, uint8_t* sum_zero, int32_t* n_kept, float* series);
 
 /* ---- Feature normalisation over a batch of hops (processing/normalization.py:31-111,150-163) ----
  * The reference post-processes every feature vector with a rolling normaliser (on by default,

@@ -26,7 +26,7 @@
 #include "../../include/nmx.h"
 #include "nmx_k_coh.h"   // coherence kernel + its be_launch_coh (HIP launcher, or the emulator's loop)
 #include "nmx_k_proj.h"  // grid-projection kernel + its be_launch_proj (likewise)
-#include "nmx_k_nolds.h" // sample-entropy kernel of the nolds feature + its be_launch_nolds (likewise)
+#include "nmx_k_nolds.h" // sample-entropy and DFA kernels of the nolds feature + be_launch_nolds / _nolds_dfa (likewise)
 
 static thread_local std::string g_nmx_err;
 static int nmx_fail(int code, const std::string& msg) {
@@ -92,7 +92,7 @@ enum Stage {
   ST_COH = 7,
   ST_PROJ = 8,       // grid projection: launched by chunk_finalize, behind the stages of run_chunk
   ST_GEOM = 9,       // no stage: nmx_last_kernels(9) is the launch geometry of the channel-pair FIR kernels
-  ST_NOLDS = 10,     // nolds: its band filters and the sample-entropy kernel
+  ST_NOLDS = 10,     // nolds: its band filters, the sample-entropy kernel and the DFA kernel
   ST_COUNT
 };
 
@@ -181,6 +181,11 @@ struct NoldsStage {
   float* h_series = nullptr;
   long long probe_w0 = 0;
   Buf d_probe, d_series;
+  // detrended fluctuation analysis (NMX_NOLDS_DFA): its own kernel behind the sample entropy's, on the same series
+  bool have_sampen = false, have_dfa = false;
+  NmxNoldsDfaArgs dfa{};      // argument template (scales: a plan table)
+  double* h_dfa = nullptr;    // nmx_nolds_dfa_probe: [item][n_scales + 3] of the caller, as h_probe
+  Buf d_dfa;
 };
 
 // The bursts chain -- Hilbert envelope (where the bank leaves band series), threshold walk, run statistics -- with its kernels

@@ -584,7 +584,7 @@ static void launch_coh_stage(Plan& P, const WinView& v, int nw, float* d_out, be
   if (tev) be_timer_stop(P.timers[ST_COH], s);
 }
 
-// ---- nolds: sample entropy of the window and of band series of it (nmx_k_nolds.h) ----------------------------------------
+// ---- nolds: sample entropy and DFA of the window and of band series of it (nmx_k_nolds.h) ----------------------------------------
 int build_nolds_bands(Plan& P);   // the band filters: nmx_engine_plan_fir.inc, beside the other FIR stages
 static int launch_nolds_bands(Plan& P, const WinView& v, int nw, be_stream_t s, bool& dc_made);
 
@@ -594,7 +594,9 @@ int build_nolds(Plan& P) {
   NMX_REQUIRE(d.nolds_n_bands >= 0 && d.nolds_n_bands <= NMX_MAX_BANDS, "nolds: nolds_n_bands out of range");
   const int n_series = (d.nolds_raw ? 1 : 0) + d.nolds_n_bands;
   if (n_series == 0 || d.nolds_measures == 0) return 0;   // (nothing to compute: the reference emits no key either)
-  if (d.nolds_measures & ~NMX_NOLDS_SAMPEN)
+  const bool dfa = (d.nolds_measures & NMX_NOLDS_DFA) && d.nolds_dfa_fit == 1;
+  NMX_REQUIRE(d.nolds_dfa_fit == 0 || d.nolds_dfa_fit == 1, "nolds: nolds_dfa_fit must be 0 (off) or 1 (\"poly\")");
+  if (d.nolds_measures & ~(NMX_NOLDS_SAMPEN | (dfa ? NMX_NOLDS_DFA : 0u)))
     return nmx_fail(NMX_E_UNSUPPORTED, "nolds: only sample_entropy has a kernel (correlation_dimension, lyapunov_exponent, "
                     "hurst_exponent and detrended_fluctuation_analysis end in the reference's unseeded RANSAC line fit)");
   NMX_REQUIRE(d.window <= NMX_NOLDS_MAX_N, "nolds: a series holds at most 40 000 samples (it has to fit the CU's LDS)");
@@ -615,6 +617,28 @@ int build_nolds(Plan& P) {
   NMX_REQUIRE(A.cols.base >= 0 && A.cols.ch_stride >= 0 && A.cols.a_stride >= 0 && last < d.n_outputs,
               "nolds: output columns outside the row");
   A.lds_floats = al4(d.window) + 64;
+  P.nolds.have_sampen = (d.nolds_measures & NMX_NOLDS_SAMPEN) != 0;
+  if (dfa) {
+    const int S = d.nolds_dfa_n_scales;
+    NMX_REQUIRE(d.nolds_dfa_scales && S >= 2 && S <= NMX_NOLDS_DFA_MAX_SCALES, "nolds: DFA needs a table of 2 .. 64 scales");
+    for (int k = 0; k < S; ++k)
+      NMX_REQUIRE(d.nolds_dfa_scales[k] >= 2 && d.nolds_dfa_scales[k] < d.window && (k == 0 || d.nolds_dfa_scales[k] > d.nolds_dfa_scales[k - 1]),
+                  "nolds: DFA scales must ascend within [2, window - 1]");
+    NmxNoldsDfaArgs& D = P.nolds.dfa;
+    D = NmxNoldsDfaArgs{};
+    D.s = A;
+    D.s.cols = cv(d.nolds_dfa_cols);
+    const long long dlast = (long long)D.s.cols.base + (long long)(d.n_channels - 1) * D.s.cols.ch_stride +
+                            (long long)(n_series - 1) * D.s.cols.a_stride;
+    NMX_REQUIRE(D.s.cols.base >= 0 && D.s.cols.ch_stride >= 0 && D.s.cols.a_stride >= 0 && dlast < d.n_outputs,
+                "nolds: DFA output columns outside the row");
+    D.n_scales = S;
+    D.scales = (const int*)upload(P, d.nolds_dfa_scales, (size_t)S * sizeof(int));
+    if (!D.scales) return nmx_fail(NMX_E_NOMEM, "nolds: DFA scale table");
+    D.lds_floats = al4(d.window) + 64 + 2 * S;
+    P.d.nolds_dfa_scales = nullptr;   // (copied: the caller's array may go)
+    P.nolds.have_dfa = true;
+  }
   int rc = build_nolds_bands(P);
   if (rc) return rc;
   P.have_nolds = true;
@@ -638,12 +662,31 @@ static int launch_nolds_stage(Plan& P, const WinView& v, int nw, float* d_out, b
     if (!(rc = ensure(N.d_probe, (size_t)n_items * 4 * sizeof(unsigned)))) A.probe = (unsigned*)N.d_probe.p;
     if (!rc && N.h_series && !(rc = ensure(N.d_series, (size_t)n_items * A.W * sizeof(float)))) A.series_out = (float*)N.d_series.p;
   }
-  if (!rc) be_launch_nolds(A, n_items, s);
+  if (!rc && N.have_sampen) be_launch_nolds(A, n_items, s);
   if (!rc && N.h_probe) {
     const size_t per_hop = (size_t)(A.raw + A.n_band) * A.n_channels;
     be_d2h_async(N.h_probe + (size_t)N.probe_w0 * per_hop * 4, A.probe, (size_t)n_items * 4 * sizeof(unsigned), s);
     if (A.series_out)
       be_d2h_async(N.h_series + (size_t)N.probe_w0 * per_hop * A.W, A.series_out, (size_t)n_items * A.W * sizeof(float), s);
+  }
+  if (!rc && N.have_dfa) {   // the same series, the DFA columns
+    NmxNoldsDfaArgs D = N.dfa;
+    const NmxCols dcols = D.s.cols;
+    D.s = A;
+    D.s.cols = dcols;
+    D.s.probe = nullptr;
+    D.s.series_out = nullptr;
+    const size_t per_item = (size_t)D.n_scales + 3, per_hop = (size_t)(A.raw + A.n_band) * A.n_channels;
+    if (N.h_dfa) {   // (nmx_nolds_dfa_probe)
+      if (!(rc = ensure(N.d_dfa, (size_t)n_items * per_item * sizeof(double)))) D.probe = (double*)N.d_dfa.p;
+      if (!rc && N.h_series && !(rc = ensure(N.d_series, (size_t)n_items * A.W * sizeof(float)))) D.s.series_out = (float*)N.d_series.p;
+    }
+    if (!rc) be_launch_nolds_dfa(D, n_items, s);
+    if (!rc && N.h_dfa) {
+      be_d2h_async(N.h_dfa + (size_t)N.probe_w0 * per_hop * per_item, D.probe, (size_t)n_items * per_item * sizeof(double), s);
+      if (D.s.series_out)
+        be_d2h_async(N.h_series + (size_t)N.probe_w0 * per_hop * A.W, D.s.series_out, (size_t)n_items * A.W * sizeof(float), s);
+    }
   }
   if (tev) be_timer_stop(P.timers[ST_NOLDS], s);
   return rc;

@@ -685,7 +685,7 @@ int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_sampl
   Plan* Pp = (Plan*)plan;
   if (!Pp) return nmx_fail(NMX_E_INVALID, "null argument");
   Plan& P = *Pp;
-  NMX_REQUIRE(P.have_nolds, "nmx_nolds_probe: the plan has no nolds stage");
+  NMX_REQUIRE(P.have_nolds && P.nolds.have_sampen, "nmx_nolds_probe: the plan has no nolds stage with a sample-entropy kernel");
   NMX_REQUIRE(n_windows >= 1 && n_windows <= (1 << 20), "nmx_nolds_probe: 1 <= n_windows <= 2^20");
   const size_t per_hop = (size_t)(P.nolds.a.raw + P.nolds.a.n_band) * P.d.n_channels, n = (size_t)n_windows * per_hop;
   std::vector<unsigned> hp(n * 4);
@@ -702,6 +702,35 @@ int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_sampl
     if (b) b[i] = hp[4 * i + 1];
     if (tol) memcpy(&tol[i], &hp[4 * i + 2], 4);
     if (sum_zero) sum_zero[i] = (uint8_t)hp[4 * i + 3];
+  }
+  return 0;
+}
+
+// ---- nolds: the same for the DFA kernel (include/nmx.h) --------------------------------------------------------------------
+int nmx_nolds_dfa_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                        float* out, double* fluct, double* alpha, uint8_t* sum_zero, int32_t* n_kept, float* series) {
+  Plan* Pp = (Plan*)plan;
+  if (!Pp) return nmx_fail(NMX_E_INVALID, "null argument");
+  Plan& P = *Pp;
+  NMX_REQUIRE(P.have_nolds && P.nolds.have_dfa, "nmx_nolds_dfa_probe: the plan has no DFA kernel");
+  NMX_REQUIRE(n_windows >= 1 && n_windows <= (1 << 20), "nmx_nolds_dfa_probe: 1 <= n_windows <= 2^20");
+  const size_t S = (size_t)P.nolds.dfa.n_scales, per_item = S + 3;
+  const size_t n = (size_t)n_windows * (size_t)(P.nolds.a.raw + P.nolds.a.n_band) * P.d.n_channels;
+  std::vector<double> hp(n * per_item);
+  std::vector<float> rows;
+  if (!out) { rows.resize((size_t)n_windows * (P.d.n_outputs + P.d.n_extra_cols)); out = rows.data(); }
+  P.nolds.h_dfa = hp.data();
+  P.nolds.h_series = series;
+  const int rc = process_batch_impl(plan, x, ldx, n_samples, starts, n_windows, out, nullptr, 0, nullptr, nullptr);
+  P.nolds.h_dfa = nullptr;
+  P.nolds.h_series = nullptr;
+  if (rc) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    const double* p = hp.data() + i * per_item;
+    if (fluct) memcpy(fluct + i * S, p, S * sizeof(double));
+    if (alpha) alpha[i] = p[S];
+    if (sum_zero) sum_zero[i] = (uint8_t)(p[S + 1] != 0.0);
+    if (n_kept) n_kept[i] = (int32_t)p[S + 2];
   }
   return 0;
 }

@@ -1,4 +1,5 @@
-// nmx_k_nolds.h -- sample entropy of the nolds feature (features/nolds.py): one workgroup per (window, series, channel).
+// nmx_k_nolds.h -- sample entropy and detrended fluctuation analysis (below: nmx_nolds_dfa_item) of the nolds feature
+// (features/nolds.py): one workgroup per (window, series, channel).
 //
 // Reference arithmetic (Nolds.calc_nolds -> nolds.sampen with its defaults: emb_dim = 2, lag = 1, Chebyshev distance, open
 // comparison), for a series x of N samples:
@@ -21,8 +22,8 @@
 // reduction and one LDS pass.  A constant offset the engine carries next to the window (dcf, nmx_engine_dc.inc) changes
 // neither a difference nor the variance; the sum takes it in float64.
 //
-// Included by nmx_engine.inc: the HIP build gets the kernel and its launcher, the host emulator (NMX_HOST_EMU) a launcher
-// that loops the same item code.
+// Included by nmx_engine.inc: the HIP build gets the kernels and their launchers, the host emulator (NMX_HOST_EMU) launchers
+// that loop the same item code.
 #pragma once
 
 #include "nmx_device.h"
@@ -90,12 +91,10 @@ NMX_DEV void nmx_nolds_diag(const float* xs, int T, int k, float tol, unsigned& 
   }
 }
 
-// item = (w * n_series + s) * n_channels + c
-NMX_DEV void nmx_nolds_item(const NmxNoldsArgs& A, int item, float* smem) {
+// The series of item = (w * n_series + s) * n_channels + c into xs (and into A.series_out); -> the constant carried next to it
+NMX_DEV double nmx_nolds_load(const NmxNoldsArgs& A, int item, float* xs) {
   const int n_series = A.raw + A.n_band, C = A.n_channels, N = A.W;
   const int c = item % C, s = (item / C) % n_series, w = item / (C * n_series);
-  float* xs = smem;
-  float* red = smem + ((N + 3) & ~3);
   const bool is_raw = A.raw && s == 0;
   double dc = 0.0;
   if (is_raw) {
@@ -112,6 +111,16 @@ NMX_DEV void nmx_nolds_item(const NmxNoldsArgs& A, int item, float* smem) {
     float* dst = A.series_out + (long long)item * N;
     for (int i = NMX_TID; i < N; i += NMX_NT) dst[i] = xs[i];
   }
+  return dc;
+}
+
+// item = (w * n_series + s) * n_channels + c
+NMX_DEV void nmx_nolds_item(const NmxNoldsArgs& A, int item, float* smem) {
+  const int n_series = A.raw + A.n_band, C = A.n_channels, N = A.W;
+  const int c = item % C, s = (item / C) % n_series, w = item / (C * n_series);
+  float* xs = smem;
+  float* red = smem + ((N + 3) & ~3);
+  const double dc = nmx_nolds_load(A, item, xs);
 
   // ---- sum, mean, variance (float64, two passes), tol ------------------------------------------------------------------
   double sum = 0.0;
@@ -154,6 +163,118 @@ NMX_DEV void nmx_nolds_item(const NmxNoldsArgs& A, int item, float* smem) {
 // threads per workgroup: one wave up to 256 samples, four up to 8192, sixteen beyond
 static inline int nmx_nolds_threads(int n) { return n <= 256 ? 64 : (n <= 8192 ? 256 : 1024); }
 
+// ---- detrended fluctuation analysis (nolds.dfa with fit_trend = "poly", order 1, overlap, fit_exp = "poly") -----------------
+// For a series x of N samples and the plan's scale table n_0 .. n_{S-1} (formed on the host: plan_desc.dfa_scales):
+//   walk = cumsum(x - mean(x)); for every scale n the chunks walk[i : i + n], i = 0, n / 2, 2 (n / 2), ... < N - n;
+//   fluc = sqrt(sum of squared residuals of the chunk's least-squares line / n); F(n) = mean of fluc over the chunks;
+//   alpha = least-squares slope of ln F on ln n over the scales with F(n) != 0 -- NaN with fewer than two of them (nolds
+//   would hand back the minimum-norm solution of the under-determined fit for exactly one); 0 when x.sum() is exactly zero.
+// One workgroup per (window, series, channel), the series in LDS as for the sample entropy.  A WAVE owns a scale (every scale
+// visits about 2 N samples, whatever n), a lane a chunk: the chunk's walk is accumulated in float64 from x - mean starting
+// at 0 -- a line fit does not see a constant, so the profile itself (sigma sqrt(N)) is never formed -- in two passes over
+// the chunk: the sums of the fit, then the residuals themselves (the closed form sum y^2 - n ybar^2 - Sty^2 / Stt cancels
+// to the square root of float64's rounding on chunks that are nearly straight).  The lanes' sums meet in the wave butterfly
+// and F(n) lands in LDS: every sum has one fixed order, a result does not depend on the batch around it.  Thread 0 fits
+// the S points in float64.
+#define NMX_NOLDS_DFA_MAX_SCALES 64
+
+struct NmxNoldsDfaArgs {
+  NmxNoldsArgs s;           // the series and the row as for the sample entropy; cols: the DFA columns; probe unused
+  const int* scales;        // [n_scales] chunk lengths, 2 <= n < W
+  int n_scales;
+  double* probe;            // [item][n_scales + 3]: F(n) of every scale, alpha, sum == 0, scales kept -- or NULL
+  int lds_floats;           // series + 64 floats of reduction scratch + n_scales doubles
+};
+
+#ifdef NMX_HOST_EMU
+#define NMX_DFA_LANE 0
+#define NMX_DFA_LANES 1
+#define NMX_DFA_WAVE 0
+#define NMX_DFA_WAVES 1
+NMX_DEV double nmx_nolds_wave_sum_d(double v) { return v; }
+#else
+#define NMX_DFA_LANE ((int)(threadIdx.x & 63))
+#define NMX_DFA_LANES 64
+#define NMX_DFA_WAVE nmx_uniform_i((int)(threadIdx.x >> 6))
+#define NMX_DFA_WAVES ((int)(blockDim.x >> 6))
+NMX_DEV double nmx_nolds_wave_sum_d(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+#endif
+
+// fluc of the chunk p[0 .. n): the walk y_0 = 0, y_j = y_{j-1} + (p[j] - mean)
+NMX_DEV double nmx_nolds_dfa_chunk(const float* p, int n, double mean, double tm, double inv_n, double inv_stt) {
+  double y = 0.0, sy = 0.0, sty = 0.0;
+  for (int j = 1; j < n; ++j) {
+    y += (double)p[j] - mean;
+    sy += y;
+    sty += (double)j * y;
+  }
+  const double slope = (sty - tm * sy) * inv_stt, icpt = sy * inv_n - slope * tm;
+  double r = icpt * icpt;   // (j = 0: y = 0)
+  y = 0.0;
+  for (int j = 1; j < n; ++j) {
+    y += (double)p[j] - mean;
+    const double e = y - (icpt + slope * (double)j);
+    r += e * e;
+  }
+  return sqrt(r * inv_n);
+}
+
+NMX_DEV void nmx_nolds_dfa_item(const NmxNoldsDfaArgs& D, int item, float* smem) {
+  const NmxNoldsArgs& A = D.s;
+  const int n_series = A.raw + A.n_band, C = A.n_channels, N = A.W, S = D.n_scales;
+  const int c = item % C, s = (item / C) % n_series, w = item / (C * n_series);
+  float* xs = smem;
+  float* red = smem + ((N + 3) & ~3);
+  double* F = (double*)(red + 64);
+  const double dc = nmx_nolds_load(A, item, xs);
+
+  double sum = 0.0;
+  for (int i = NMX_TID; i < N; i += NMX_NT) sum += (double)xs[i];
+  sum = nmx_nolds_sum_d(sum, red);
+  const double mean = sum / (double)N;
+  const bool zero = sum + (double)N * dc == 0.0;
+
+  for (int k = NMX_DFA_WAVE; k < S; k += NMX_DFA_WAVES) {
+    const int n = nmx_uniform_i(D.scales[k]), step = n >> 1;
+    const int n_chunks = (N - n + step - 1) / step;   // starts 0, step, 2 step, ... < N - n: the last sample read is < N - 1
+    const double tm = 0.5 * (double)(n - 1), inv_n = 1.0 / (double)n;
+    const double inv_stt = 12.0 / ((double)n * ((double)n * (double)n - 1.0));
+    double acc = 0.0;
+    for (int q = NMX_DFA_LANE; q < n_chunks; q += NMX_DFA_LANES) acc += nmx_nolds_dfa_chunk(xs + q * step, n, mean, tm, inv_n, inv_stt);
+    acc = nmx_nolds_wave_sum_d(acc);
+    if (NMX_DFA_LANE == 0) F[k] = acc / (double)n_chunks;
+  }
+  NMX_SYNC();
+
+  if (NMX_TID == 0) {
+    int kept = 0;
+    double mx = 0.0, my = 0.0;
+    for (int k = 0; k < S; ++k)
+      if (F[k] > 0.0) { ++kept; mx += log((double)D.scales[k]); my += log(F[k]); }
+    double alpha = NAN;
+    if (kept >= 2) {
+      mx /= (double)kept;
+      my /= (double)kept;
+      double sxx = 0.0, sxy = 0.0;
+      for (int k = 0; k < S; ++k)
+        if (F[k] > 0.0) { const double dx = log((double)D.scales[k]) - mx; sxx += dx * dx; sxy += dx * (log(F[k]) - my); }
+      alpha = sxy / sxx;
+    }
+    A.out[(long long)w * A.n_outputs + A.cols.base + c * A.cols.ch_stride + s * A.cols.a_stride] = zero ? 0.f : (float)alpha;
+    if (D.probe) {
+      double* p = D.probe + (long long)item * (S + 3);
+      for (int k = 0; k < S; ++k) p[k] = F[k];
+      p[S] = alpha; p[S + 1] = zero ? 1.0 : 0.0; p[S + 2] = (double)kept;
+    }
+  }
+}
+
+// a wave per scale: no more waves than scales
+static inline int nmx_nolds_dfa_threads(int n, int n_scales) { return std::min(nmx_nolds_threads(n), 64 * std::max(n_scales, 1)); }
+
 #ifdef NMX_HOST_EMU
 static void be_launch_nolds(const NmxNoldsArgs& A, int n_items, be_stream_t st) {
 #ifdef NMX_TR
@@ -163,6 +284,14 @@ static void be_launch_nolds(const NmxNoldsArgs& A, int n_items, be_stream_t st) 
   std::vector<float> sm((size_t)A.lds_floats + 16);
   for (int it = 0; it < n_items; ++it) nmx_nolds_item(A, it, sm.data());
 }
+static void be_launch_nolds_dfa(const NmxNoldsDfaArgs& D, int n_items, be_stream_t st) {
+#ifdef NMX_TR
+  NMX_TR(st);
+#endif
+  (void)st;
+  std::vector<float> sm((size_t)D.lds_floats + 16);
+  for (int it = 0; it < n_items; ++it) nmx_nolds_dfa_item(D, it, sm.data());
+}
 #else
 extern __shared__ __attribute__((aligned(16))) float nmx_smem[];
 __global__ void __launch_bounds__(1024) nmx_kern_nolds_sampen(const NmxNoldsArgs A) {
@@ -170,5 +299,11 @@ __global__ void __launch_bounds__(1024) nmx_kern_nolds_sampen(const NmxNoldsArgs
 }
 static void be_launch_nolds(const NmxNoldsArgs& A, int n_items, be_stream_t s) {
   NMX_LAUNCH(nmx_kern_nolds_sampen, dim3(n_items), dim3(nmx_nolds_threads(A.W)), (size_t)A.lds_floats * 4, s, A);
+}
+__global__ void __launch_bounds__(1024) nmx_kern_nolds_dfa(const NmxNoldsDfaArgs D) {
+  nmx_nolds_dfa_item(D, (int)blockIdx.x, nmx_smem);
+}
+static void be_launch_nolds_dfa(const NmxNoldsDfaArgs& D, int n_items, be_stream_t s) {
+  NMX_LAUNCH(nmx_kern_nolds_dfa, dim3(n_items), dim3(nmx_nolds_dfa_threads(D.s.W, D.n_scales)), (size_t)D.lds_floats * 4, s, D);
 }
 #endif

@@ -315,9 +315,12 @@ class DataProcessor(UserViews):
                  device: int = 0, window: int | None = None, lib=None,
                  channel_subset=None, dry_run: bool = False,
                  resample_features_at_new_rate: bool = False, local_inputs: bool = False,
-                 staging_slot: int = 0, _family: tuple | None = None, resample_npad=None) -> None:
+                 staging_slot: int = 0, _family: tuple | None = None, resample_npad=None, nolds_fit=None) -> None:
         """``resample_npad``: the padding of raw_resampling, ``"auto"`` (the default) or an int >= 0 samples per side; 100 is
         what the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
+
+        ``nolds_fit``: ``"poly"`` lets nolds' detrended_fluctuation_analysis run, its final line fitted by least squares
+        (plan_desc.nolds_fit_arg; None: NMX_NOLDS_FIT, and without it the measure raises as the unseeded RANSAC fit has it).
 
         ``_family``: (PrepPlan, PostChain, LengthTable) of the processor this one is the twin of for another window
         length (`_twin`): the twin takes them instead of building its own.
@@ -332,7 +335,7 @@ class DataProcessor(UserViews):
         # (what a twin for another window length is built from: `process` under the reference's own loop, below)
         self._ctor = dict(sfreq=sfreq, line_noise=line_noise, verbose=verbose, device=device, lib=lib,
                           resample_features_at_new_rate=resample_features_at_new_rate, staging_slot=staging_slot,
-                          resample_npad=resample_npad)
+                          resample_npad=resample_npad, nolds_fit=nolds_fit)
         self._twin_ok = channel_subset is None and not dry_run and not local_inputs
         self.sfreq_features, self._sfreq_raw_orig = st.sampling_rate_features_hz, sfreq
         self.line_noise, self.verbose = line_noise, verbose
@@ -368,7 +371,7 @@ class DataProcessor(UserViews):
                 full, self.local_rows, self.local_groups = self.local.matrix, self.local.rows, self.local.groups
             kw["ref_matrix"] = full
         self.engine = HotPathEngine(st, names, device=device, lib=lib, dry_run=dry_run, staging_slot=staging_slot,
-                                    extra_cols=chain.extra_cols, **kw)
+                                    extra_cols=chain.extra_cols, nolds_fit=nolds_fit, **kw)
         if chain.keys is None:
             chain.start(self.engine.keys, names, self.sfreq_raw, dry_run)
         if not dry_run:

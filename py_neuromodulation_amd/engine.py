@@ -63,7 +63,7 @@ class HotPathEngine:
                  resample_from: float | None = None, raw_window: int | None = None,
                  pre_taps: Sequence[np.ndarray] | None = None,
                  raw_norm: tuple | None = None, resample_to: float | None = None, staging_slot: int = 0,
-                 extra_cols=0, resample_npad=None) -> None:
+                 extra_cols=0, resample_npad=None, nolds_fit=None) -> None:
         """``sfreq`` is the rate every feature and filter is DESIGNED with (what the reference passes to the
         feature constructors).  ``resample_from`` = sampling rate of the incoming windows when they are
         resampled (raw_resampling, processing/resample.py:19-60): incoming windows then hold ``raw_window``
@@ -79,6 +79,11 @@ class HotPathEngine:
         ``resample_npad``: the resampler's padding, ``"auto"`` (the default) or an int >= 0 samples per side -- 100 is what
         the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
 
+        ``nolds_fit``: ``"poly"`` lets ``nolds_settings.features.detrended_fluctuation_analysis`` run -- ``nolds.dfa`` with
+        its final log-log line fitted by least squares instead of nolds' default, an unseeded RANSAC.  ``None`` (the default;
+        NMX_NOLDS_FIT where it is not given) and ``"RANSAC"`` keep the measure's NotImplementedError
+        (plan_desc.nolds_fit_arg).
+
         ``dry_run=True`` only derives the plan description and the key list (no library, no
         GPU) -- used to lay out the global column order when channels are sharded over GPUs.
 
@@ -87,8 +92,9 @@ class HotPathEngine:
         n_outputs + n_extra floats; 0 keeps the plain layout."""
         self.lib = None if dry_run else (lib if lib is not None else _lib.get_library())
         b = PlanBuilder(settings, ch_names, sfreq, features, window, resample_from, raw_window, resample_to, pre_taps,
-                        raw_norm, resample_npad)
+                        raw_norm, resample_npad, nolds_fit)
         self.resample_npad = b.resample_npad
+        self.nolds_fit = b.nolds_fit
         self.settings, self.ch_names, self.sfreq, self.C, self.enabled = b.settings, b.ch_names, b.sfreq, b.C, b.enabled
         self.W, self.W_in, self.resample_ratio = b.W, b.W_in, b.resample_ratio
         # (`_keep`: the arrays the C struct points into)
@@ -482,6 +488,31 @@ class HotPathEngine:
             b.ctypes.data, tol.ctypes.data, zero.ctypes.data, series.ctypes.data if series is not None else None))
         return {"out": out, "A": a, "B": b, "tol": tol, "sum_zero": zero.astype(bool), "series": series}
 
+    def nolds_dfa_probe(self, data: np.ndarray, starts: np.ndarray, want_series: bool = True) -> dict:
+        """``process_batch`` of a plan with detrended fluctuation analysis that also hands back what the DFA kernel formed
+        (nmx_nolds_dfa_probe): ``"out"`` float32[n, row_width]; ``"scales"`` int[S], the plan's table; ``"F"`` float64[n,
+        n_series, C, S], the fluctuation function; ``"alpha"`` float64 (the slope, before the sum rule), ``"sum_zero"`` (bool)
+        and ``"n_kept"`` (scales with F != 0), each [n, n_series, C]; ``"series"`` float32[n, n_series, C, W]: the samples the
+        kernel read."""
+        data = np.asarray(data)
+        if data.ndim != 2 or data.shape[0] != self.C_in:
+            raise ValueError(f"expected data with {self.C_in} rows, got {data.shape}")
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        dc = self._host_offsets(data)
+        x = np.ascontiguousarray(data if dc is None else np.asarray(data, np.float64) - dc[:, None], dtype=np.float32)
+        n, S = len(starts), int(self.desc.nolds_raw) + int(self.desc.nolds_n_bands)
+        K = int(self.desc.nolds_dfa_n_scales)
+        out = np.empty((n, self.row_width), np.float32)
+        fluct, alpha = np.zeros((n, S, self.C, K), np.float64), np.zeros((n, S, self.C), np.float64)
+        zero, kept = np.zeros((n, S, self.C), np.uint8), np.zeros((n, S, self.C), np.int32)
+        series = np.zeros((n, S, self.C, self.W), np.float32) if want_series else None
+        self.lib.check(self.lib.lib.nmx_nolds_dfa_probe(
+            self._plan, x.ctypes.data, _ld(x), x.shape[1], starts.ctypes.data, n, out.ctypes.data, fluct.ctypes.data,
+            alpha.ctypes.data, zero.ctypes.data, kept.ctypes.data, series.ctypes.data if series is not None else None))
+        scales = np.array([self.desc.nolds_dfa_scales[k] for k in range(K)], np.int64)
+        return {"out": out, "scales": scales, "F": fluct, "alpha": alpha, "sum_zero": zero.astype(bool), "n_kept": kept,
+                "series": series}
+
     def timing_ms(self, which: int = 0) -> float:
         ms = C.c_float()
         self.lib.check(self.lib.lib.nmx_last_timing_ms(self._plan, which, C.byref(ms)))
@@ -490,7 +521,7 @@ class HotPathEngine:
     def kernels(self, which: int) -> str:
         """Kernels the last batch -- or the last ``preprocess_window`` / ``filter_window`` call -- launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
         5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
-        7 coherence, 8 grid projection, 10 nolds: its band filters and the sample-entropy kernel), named as rocprofv3
+        7 coherence, 8 grid projection, 10 nolds: its band filters, the sample-entropy kernel and the DFA kernel), named as rocprofv3
         prints them.  ``which = 9``: the launch geometry of the
         channel-pair FIR kernels of that launch sequence, ``"<kernel>: <n> pairs, <workgroups> x <waves> waves"``."""
         buf = C.create_string_buffer(512)

@@ -130,8 +130,10 @@ class Coherence(_EngineFeature):
 
 
 class Nolds(_EngineFeature):
-    """features/nolds.py:32-100: sample entropy of every channel's window ("raw") and of band-pass series of it.  The
-    four other nolds measures raise ``NotImplementedError`` (the reference fits them with an unseeded RANSAC)."""
+    """features/nolds.py:32-100: sample entropy of every channel's window ("raw") and of band-pass series of it, and --
+    with ``Nolds(settings, ch_names, sfreq, nolds_fit="poly")`` or NMX_NOLDS_FIT=poly in the environment -- detrended
+    fluctuation analysis with its final line fitted by least squares.  Without that, and for the three other nolds
+    measures always, ``NotImplementedError`` (the reference fits them with an unseeded RANSAC)."""
     feature_name = "nolds"
 
 

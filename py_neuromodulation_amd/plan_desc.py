@@ -31,6 +31,11 @@ _OUT_OF_SCOPE = {"fooof", "mne_connectivity", "bispectrum"}
 NOLDS_TOL_FACTOR = 0.1164 * (0.5627 * float(np.log(2.0)) + 1.3334)
 NOLDS_DDOF = 1
 NOLDS_MAX_SAMPLES = 40000   # nmx_k_nolds.h: a series sits in the CU's LDS
+# nolds.dfa's default scale rule, as recalled for nolds >= 0.6 (not installed here either: parity with nolds itself is
+# unpinned, as for NOLDS_TOL_FACTOR): logarithmic_n(4, 0.1 N, 1.2) above 70 samples.  `dfa_scales` forms the table here
+# and the plan description carries it -- the kernel bakes in neither the table nor the rule.
+NOLDS_DFA_MIN_SCALE, NOLDS_DFA_MAX_SHARE, NOLDS_DFA_FACTOR = 4, 0.1, 1.2
+NOLDS_DFA_MAX_SCALES = 64   # nmx_k_nolds.h: NMX_NOLDS_DFA_MAX_SCALES
 COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel, at every window (above 16 384 samples too: NMX_LONG_COHERENCE)
 _BURST_SLOTS = [("duration", ["duration_mean", "duration_max"]),
                 ("amplitude", ["amplitude_mean", "amplitude_max"]),
@@ -66,14 +71,56 @@ def resample_npad_arg(value=None):
     return int(value)
 
 
+def nolds_fit_arg(value=None):
+    """The final line fit of the nolds measures as the keyword ``nolds_fit`` states it: ``None`` (the default: the
+    reference's, ``fit="RANSAC"``, which has no kernel -- every measure that ends in it raises), ``"RANSAC"`` (the same,
+    said aloud) or ``"poly"`` (least squares: ``nolds.dfa(x, fit_exp="poly")`` runs on the device).  ``None`` reads the
+    environment variable NMX_NOLDS_FIT (``poly`` or ``RANSAC``).  Anything else: ValueError.  -> None or "poly"."""
+    name = "nolds_fit"
+    if value is None:
+        value = os.environ.get("NMX_NOLDS_FIT", "").strip()
+        name = "NMX_NOLDS_FIT"
+        if value == "":
+            return None
+    if isinstance(value, str) and value == "poly":
+        return "poly"
+    if isinstance(value, str) and value == "RANSAC":
+        return None
+    raise ValueError(f"{name} must be 'poly' or 'RANSAC' (or unset), not {value!r}")
+
+
+def dfa_scales(n_samples: int) -> list[int]:
+    """The chunk lengths ``nolds.dfa`` chooses for a series of ``n_samples`` (its default ``nvals``), and its errors."""
+    N = int(n_samples)
+    if N > 70:
+        lo, hi, f = NOLDS_DFA_MIN_SCALE, NOLDS_DFA_MAX_SHARE * N, NOLDS_DFA_FACTOR
+        nvals = [lo]   # nolds.logarithmic_n
+        for i in range(int(np.floor(np.log(1.0 * hi / lo) / np.log(f))) + 1):
+            n = int(np.floor(lo * (f ** i)))
+            if n > nvals[-1]:
+                nvals.append(n)
+    elif N > 10:
+        nvals = [4, 5, 6, 7, 8, 9]
+    else:
+        nvals = [N - 2, N - 1]
+    if len(nvals) < 2:
+        raise ValueError("at least two nvals are needed")
+    if min(nvals) < 2:
+        raise ValueError(f"nvals must be at least two (detrended_fluctuation_analysis of a {N}-sample series)")
+    if max(nvals) >= N:
+        raise ValueError("nvals cannot be larger than the input size")
+    return nvals
+
+
 class PlanBuilder:
     """The window geometry of one plan (``W`` samples the features see, ``W_in`` incoming, ``resample_ratio``), then
     ``build`` -> (PlanDesc, keys, coh_pairs, filter_taps, the arrays the struct points into).  HotPathEngine's arguments."""
 
     def __init__(self, settings, ch_names, sfreq, features=None, window=None, resample_from=None, raw_window=None,
-                 resample_to=None, pre_taps=None, raw_norm=None, resample_npad=None) -> None:
+                 resample_to=None, pre_taps=None, raw_norm=None, resample_npad=None, nolds_fit=None) -> None:
         self.settings = settings
         self.resample_npad = resample_npad_arg(resample_npad)
+        self.nolds_fit = nolds_fit_arg(nolds_fit)   # None, or "poly": detrended_fluctuation_analysis runs (keyword, else NMX_NOLDS_FIT)
         self.ch_names = list(ch_names)
         self.sfreq = float(sfreq)
         self.C = len(self.ch_names)
@@ -484,6 +531,9 @@ class PlanBuilder:
         ns = st.nolds_settings
         feats = _enabled(ns.features)
         other = [f for f in feats if f != "sample_entropy"]
+        dfa = self.nolds_fit == "poly" and "detrended_fluctuation_analysis" in feats
+        if dfa:   # (nolds_fit="poly": nolds.dfa(x, fit_exp="poly") has a kernel; the other three keep raising)
+            other.remove("detrended_fluctuation_analysis")
         if other:
             raise NotImplementedError(
                 f"nolds measures {other} are not implemented: the reference ends them in a line fit that defaults to "
@@ -524,7 +574,19 @@ class PlanBuilder:
         d.nolds_tol_factor = NOLDS_TOL_FACTOR
         d.nolds_ddof = NOLDS_DDOF
         C_ = self.C
-        d.nolds_cols = _cols(col, 1, C_, 0)
+        # inside a series and a channel the measures stand in get_enabled() order: sample_entropy, then DFA
+        nf = len(feats)
+        if "sample_entropy" in feats:
+            d.nolds_cols = _cols(col + feats.index("sample_entropy"), nf, C_ * nf, 0)
+        if dfa:
+            scales = np.ascontiguousarray(dfa_scales(self.W), dtype=np.int32)   # (nolds' ValueError below four samples)
+            if len(scales) > NOLDS_DFA_MAX_SCALES:
+                raise ValueError(f"nolds: {len(scales)} DFA scales exceed the kernel's table of {NOLDS_DFA_MAX_SCALES}")
+            self._keep.append(scales)
+            d.nolds_dfa_fit = 1
+            d.nolds_dfa_n_scales = len(scales)
+            d.nolds_dfa_scales = scales.ctypes.data_as(C.POINTER(C.c_int32))
+            d.nolds_dfa_cols = _cols(col + feats.index("detrended_fluctuation_analysis"), nf, C_ * nf, 0)
         for sname in series:
             for ch in self.ch_names:
                 self.keys += [f"{ch}_nolds_{f}_{sname}" for f in feats]

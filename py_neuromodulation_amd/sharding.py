@@ -55,9 +55,10 @@ class ShardedStream:
 
     def __init__(self, sfreq, channels, settings=None, line_noise=50, rank: int = 0,
                  world_size: int = 1, device: int | None = None, lib=None, local_input: bool = False,
-                 resample_npad=None) -> None:
+                 resample_npad=None, nolds_fit=None) -> None:
         self.sfreq = sfreq
         self.resample_npad = resample_npad   # raw_resampling's padding: "auto" or samples per side (DataProcessor)
+        self.nolds_fit = nolds_fit           # "poly": nolds' DFA runs, fitted by least squares (DataProcessor)
         self.settings = NMSettings.load(settings)
         no_sharded_projection(self.settings)
         self.channels = chmod.load_channels(channels)
@@ -85,7 +86,8 @@ class ShardedStream:
                 "Stream(devices=[...]) (sharding.MultiDeviceProcessor) instead of one rank per GPU")
         return DataProcessor(self.sfreq, self.settings, self.channels, line_noise=self.line_noise, verbose=False,
                              device=self.device, window=window, lib=self._lib, channel_subset=self.shard,
-                             local_inputs=self.local_input, dry_run=dry_run, resample_npad=self.resample_npad)
+                             local_inputs=self.local_input, dry_run=dry_run, resample_npad=self.resample_npad,
+                             nolds_fit=self.nolds_fit)
 
     def _comm_device(self, group=None):
         """Where the tensors of a collective must live: this rank's GPU under the "nccl" backend (= RCCL, which
@@ -204,7 +206,7 @@ class MultiDeviceProcessor(UserViews):
 
     def __init__(self, sfreq, settings, channels, line_noise=None, devices=(0,), window=None, lib=None,
                  verbose: bool = False, resample_features_at_new_rate: bool = False, local_input: bool = True,
-                 resample_npad=None) -> None:
+                 resample_npad=None, nolds_fit=None) -> None:
         from concurrent.futures import ThreadPoolExecutor
 
         self.settings = NMSettings.load(settings)
@@ -215,7 +217,8 @@ class MultiDeviceProcessor(UserViews):
             raise ValueError("devices must name at least one GPU")
         names, _, _ = chmod.channel_info(self.channels)
         kw = dict(line_noise=line_noise, verbose=False, window=window, lib=lib,
-                  resample_features_at_new_rate=resample_features_at_new_rate, resample_npad=resample_npad)
+                  resample_features_at_new_rate=resample_features_at_new_rate, resample_npad=resample_npad,
+                  nolds_fit=nolds_fit)
         layout = DataProcessor(sfreq, self.settings, self.channels, dry_run=True, **kw)
         self.sfreq_raw = layout.sfreq_raw
         self.ch_names_used = layout.ch_names_used

@@ -16,7 +16,7 @@ import numpy as np
 from . import channels as chmod
 from .data_processor import DataProcessor, LengthTable
 from .generator import window_schedule
-from .plan_desc import resample_npad_arg
+from .plan_desc import nolds_fit_arg, resample_npad_arg
 from .settings import NMSettings
 
 _FREQ_FEATURES = ["bandpass_filter", "stft", "fft", "welch", "bursts", "coherence", "nolds", "bispectrum"]
@@ -27,9 +27,12 @@ class Stream:
                  line_noise: float | None = 50, sampling_rate_features_hz: float | None = None,
                  path_grids=None, coord_names=None, coord_list=None, verbose: bool = False,
                  device: int = 0, lib=None, resample_features_at_new_rate: bool = False,
-                 devices=None, resample_npad=None) -> None:
+                 devices=None, resample_npad=None, nolds_fit=None) -> None:
         """``resample_npad``: the padding of raw_resampling -- ``"auto"`` (the default: the next power of two) or an int >= 0
         samples per side; 100 is what the reference's call of ``mne.filter.resample`` gets.  None: NMX_RESAMPLE_NPAD.
+
+        ``nolds_fit``: ``"poly"`` lets nolds' detrended_fluctuation_analysis run (``nolds.dfa`` with its final line fitted by
+        least squares instead of the unseeded RANSAC default); None: NMX_NOLDS_FIT, and without it the measure raises.
 
         ``devices=[0, 1, ...]``: the channels are sharded in contiguous blocks over these GPUs inside this one
         process (one plan and one host thread per device, sharding.MultiDeviceProcessor); ``device`` otherwise."""
@@ -56,6 +59,7 @@ class Stream:
         self.devices = [int(d) for d in devices] if devices is not None else None
         self._resample_new_rate = resample_features_at_new_rate
         self._resample_npad = resample_npad_arg(resample_npad)
+        self._nolds_fit = nolds_fit_arg(nolds_fit)
         self._lib = lib  # None = the product library (libnmx.so); tests may inject a binding
         self.data = data
         self.path_grids, self.coord_names, self.coord_list = path_grids, coord_names, coord_list
@@ -77,7 +81,7 @@ class Stream:
 
         coords = None if self.coord_list is None else np.asarray(self.coord_list, dtype=np.float64).tobytes()
         return (settings_token if settings_token is not None else self._settings_token(), repr(self.line_noise),
-                repr(self.sfreq), bool(self._resample_new_rate), repr(self._resample_npad),
+                repr(self.sfreq), bool(self._resample_new_rate), repr(self._resample_npad), repr(self._nolds_fit),
                 int(self.device), tuple(self.devices or ()), id(self._lib),
                 tuple((k, id(v)) for k, v in user_features.items()),
                 None if self.coord_names is None else tuple(self.coord_names), coords,
@@ -90,7 +94,7 @@ class Stream:
             dp = MultiDeviceProcessor(self.sfreq, self.settings, self.channels, line_noise=self.line_noise,
                                       devices=self.devices, window=window, lib=self._lib, verbose=self.verbose,
                                       resample_features_at_new_rate=self._resample_new_rate,
-                                      resample_npad=self._resample_npad)
+                                      resample_npad=self._resample_npad, nolds_fit=self._nolds_fit)
         else:
             dp = DataProcessor(sfreq=self.sfreq, settings=self.settings, channels=self.channels,
                                coord_names=self.coord_names, coord_list=self.coord_list, path_grids=self.path_grids,
@@ -98,7 +102,7 @@ class Stream:
                                device=self.devices[0] if self.devices else self.device,
                                window=window, lib=self._lib,
                                resample_features_at_new_rate=self._resample_new_rate,
-                               resample_npad=self._resample_npad)
+                               resample_npad=self._resample_npad, nolds_fit=self._nolds_fit)
         dp.settings_token = self._processor_token()
         return dp
 
