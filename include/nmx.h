@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NMX_ABI_VERSION 16
+#define NMX_ABI_VERSION 17
 
 /* error codes */
 #define NMX_OK 0
@@ -59,7 +59,7 @@ extern "C" {
 #define NMX_F_NOLDS (1u << 10)     /* features/nolds.py (sample entropy)        */
 
 /* measures of the nolds family, NoldsFeatures field order (features/nolds.py:14-19); NMX_NOLDS_SAMPEN has a kernel, and
- * NMX_NOLDS_DFA one for the final fit "poly" (nolds_dfa_fit below) */
+ * NMX_NOLDS_DFA and NMX_NOLDS_HURST one each for the final fit "poly" (nolds_dfa_fit, nolds_hurst_fit below) */
 #define NMX_NOLDS_SAMPEN 1u
 #define NMX_NOLDS_CORR_DIM 2u
 #define NMX_NOLDS_LYAP 4u
@@ -240,8 +240,8 @@ typedef struct {
    *                     -- the reference reads data_filt[:, j, :] of the bank over ALL frequency_ranges_hz with j the position
    *                     in ITS OWN band list, so series j is global band j under the key of nolds band j: the host resolves
    *                     that and hands over the taps it means
-   *   nolds_measures    NMX_NOLDS_* bit mask; anything but NMX_NOLDS_SAMPEN, and NMX_NOLDS_DFA with nolds_dfa_fit = 1 (below),
-   *                     -> NMX_E_UNSUPPORTED
+   *   nolds_measures    NMX_NOLDS_* bit mask; anything but NMX_NOLDS_SAMPEN, NMX_NOLDS_DFA with nolds_dfa_fit = 1 and
+   *                     NMX_NOLDS_HURST with nolds_hurst_fit = 1 (below) -> NMX_E_UNSUPPORTED
    *   nolds_tol_factor  tol = nolds_tol_factor * std(x, ddof = nolds_ddof), both formed on the host
    *   nolds_cols        sample entropy: a = series (raw first, then the bands in list order) */
   int32_t nolds_raw;
@@ -287,6 +287,30 @@ typedef struct {
   int32_t nolds_dfa_n_scales;
   const int32_t* nolds_dfa_scales;
   nmx_cols nolds_dfa_cols;
+
+  /* nolds: Hurst exponent by rescaled range (NMX_NOLDS_HURST of nolds_measures) of the stage's series -- nolds.hurst_rs(x)
+   * with its defaults (nvals = logmid_n(N, 1/4, 15), corrected, unbiased) but the final log-log line fit "poly" instead of
+   * nolds' default "RANSAC".  All zero = off.
+   *   nolds_hurst_fit           0: no Hurst kernel (NMX_NOLDS_HURST in nolds_measures -> NMX_E_UNSUPPORTED); 1: "poly"
+   *   nolds_hurst_scales        [nolds_hurst_n_scales] chunk lengths n, ascending, 2 <= n < window, 2 .. 15 of them
+   *   nolds_hurst_log_expected  [nolds_hurst_n_scales] float64 ln E(n): the Anis-Lloyd-Peters expectation of (R/S)_n of white
+   *                             noise.  Both tables are FORMED ON THE HOST in float64 and copied at plan creation: the kernel
+   *                             bakes in neither the scale rule nor E.
+   *   per scale                 the window / n whole chunks x[q n : (q + 1) n] (the tail is dropped); per chunk d = x - mean,
+   *                             y = cumsum(d), r = max y - min y (over y_0 .. y_{n-1}, no leading 0), s = sqrt(sum d^2 /
+   *                             (n - 1)); chunks with r == 0 are left out; (R/S)_n = mean of r / s over the rest, NaN when
+   *                             none is left
+   *   value                     0.5 + slope of ln (R/S)_n - ln E(n) on ln n over the scales that are not NaN; NaN when fewer
+   *                             than TWO are left (nolds: NaN for none, the minimum-norm solution for one); 0 when the
+   *                             series' float64 sum is exactly 0 (the reference's wrapper)
+   *   nolds_hurst_cols          a = series, as nolds_cols.  Inside a series and a channel the measures stand in the
+   *                             reference's get_enabled() order: sample_entropy, hurst_exponent, DFA.
+   * Parity with nolds itself is unpinned (it is not installed where the tests run), as for the other two measures. */
+  int32_t nolds_hurst_fit;
+  int32_t nolds_hurst_n_scales;
+  nmx_cols nolds_hurst_cols;
+  const int32_t* nolds_hurst_scales;
+  const double* nolds_hurst_log_expected;
 } nmx_plan_desc;
 
 typedef struct nmx_plan nmx_plan;
@@ -379,7 +403,7 @@ int nmx_state_import(nmx_plan* plan, const void* src, int64_t n_bytes);
  * which = 0 whole batch, 1 pre-processing, 2 time/oscillatory kernel, 3 FIR-bank kernel,
  * 4 bursts kernels, 5 sharp-wave kernel, 6 second FIR-bank launch (the filters whose taps are too long for the
  * M = 1536 channel-pair kernel; 0 when there is none), 7 coherence kernel, 8 grid-projection kernel (attached nmx_proj),
- * 10 the nolds stage (its band filters, the sample-entropy kernel and the DFA kernel; 9 is no timer: see nmx_last_kernels).
+ * 10 the nolds stage (its band filters and the sample-entropy, Hurst and DFA kernels; 9 is no timer: see nmx_last_kernels).
  * Stages 1..10 are those of the first chunk of the batch.  Blocks until the events have completed. */
 int nmx_last_timing_ms(nmx_plan* plan, int which, float* ms);
 
@@ -414,6 +438,17 @@ int nmx_nolds_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_sampl
  * out and every array may be NULL.  NMX_E_INVALID for a plan without a DFA kernel. */
 int nmx_nolds_dfa_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
                         float* out, double* fluct, double* alpha, uint8_t* sum_zero, int32_t* n_kept, float* series);
+
+/* The same for the Hurst kernel of a plan with NMX_NOLDS_HURST, item by item ([n_windows][n_series][n_channels]):
+ *   rs        [...][nolds_hurst_n_scales] float64: (R/S)_n of every scale of the table, NaN where no chunk was kept
+ *   kept      [...][nolds_hurst_n_scales] int32: chunks with r != 0 of every scale
+ *   hurst     float64 H of the scales that are not NaN (NaN with fewer than two), BEFORE the sum rule
+ *   sum_zero  1 when the float64 sum of the series is exactly 0 (the row then holds 0)
+ *   n_kept    scales that are not NaN
+ *   series    [...][window] float32: the samples the kernel read
+ * out and every array may be NULL.  NMX_E_INVALID for a plan without a Hurst kernel. */
+int nmx_nolds_hurst_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                          float* out, double* rs, int32_t* kept, double* hurst, uint8_t* sum_zero, int32_t* n_kept, float* series);
 
 /* ---- Feature normalisation over a batch of hops (processing/normalization.py:31-111,150-163) ----
  * The reference post-processes every feature vector with a rolling normaliser (on by default,

@@ -12,7 +12,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-NMX_ABI_VERSION = 16
+NMX_ABI_VERSION = 17
 NMX_MAX_BANDS = 16
 NMX_MAX_FILTERS = 24
 NMX_MAX_SW_COMBOS = 48
@@ -83,6 +83,8 @@ class PlanDesc(C.Structure):
         ("resample_npad_mode", C.c_int32), ("resample_npad", C.c_int32),
         ("nolds_dfa_fit", C.c_int32), ("nolds_dfa_n_scales", C.c_int32), ("nolds_dfa_scales", C.POINTER(C.c_int32)),
         ("nolds_dfa_cols", Cols),
+        ("nolds_hurst_fit", C.c_int32), ("nolds_hurst_n_scales", C.c_int32), ("nolds_hurst_cols", Cols),
+        ("nolds_hurst_scales", C.POINTER(C.c_int32)), ("nolds_hurst_log_expected", C.POINTER(C.c_double)),
     ]
 
 
@@ -109,7 +111,7 @@ _EXPORTS = [
     "nmx_plan_carries_offsets", "nmx_plan_set_offsets", "nmx_plan_get_offsets", "nmx_plan_set_pipeline",
     "nmx_host_stage_rows", "nmx_host_group_sums", "nmx_host_stage_parts", "nmx_host_widen_rows",
     "nmx_proj_create", "nmx_proj_destroy", "nmx_proj_process", "nmx_plan_attach_proj", "nmx_nolds_probe",
-    "nmx_nolds_dfa_probe",
+    "nmx_nolds_dfa_probe", "nmx_nolds_hurst_probe",
 ]
 
 
@@ -184,6 +186,8 @@ class NmxLibrary:
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nmx_nolds_dfa_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nmx_nolds_hurst_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nmx_host_alloc.argtypes = [C.c_int64, C.POINTER(C.c_void_p)]
         L.nmx_host_free.argtypes = [C.c_void_p]
         L.nmx_device_pool_trim.argtypes = [C.c_int64, C.POINTER(C.c_int64)]

@@ -26,7 +26,7 @@
 #include "../../include/nmx.h"
 #include "nmx_k_coh.h"   // coherence kernel + its be_launch_coh (HIP launcher, or the emulator's loop)
 #include "nmx_k_proj.h"  // grid-projection kernel + its be_launch_proj (likewise)
-#include "nmx_k_nolds.h" // sample-entropy and DFA kernels of the nolds feature + be_launch_nolds / _nolds_dfa (likewise)
+#include "nmx_k_nolds.h" // sample-entropy, Hurst and DFA kernels of the nolds feature + be_launch_nolds / _hurst / _dfa (likewise)
 
 static thread_local std::string g_nmx_err;
 static int nmx_fail(int code, const std::string& msg) {
@@ -92,7 +92,7 @@ enum Stage {
   ST_COH = 7,
   ST_PROJ = 8,       // grid projection: launched by chunk_finalize, behind the stages of run_chunk
   ST_GEOM = 9,       // no stage: nmx_last_kernels(9) is the launch geometry of the channel-pair FIR kernels
-  ST_NOLDS = 10,     // nolds: its band filters, the sample-entropy kernel and the DFA kernel
+  ST_NOLDS = 10,     // nolds: its band filters and the sample-entropy, Hurst and DFA kernels
   ST_COUNT
 };
 
@@ -186,6 +186,11 @@ struct NoldsStage {
   NmxNoldsDfaArgs dfa{};      // argument template (scales: a plan table)
   double* h_dfa = nullptr;    // nmx_nolds_dfa_probe: [item][n_scales + 3] of the caller, as h_probe
   Buf d_dfa;
+  // Hurst exponent by rescaled range (NMX_NOLDS_HURST): its own kernel between the two, on the same series
+  bool have_hurst = false;
+  NmxNoldsHurstArgs hurst{};  // argument template (scales, log_e: plan tables)
+  double* h_hurst = nullptr;  // nmx_nolds_hurst_probe: [item][2 n_scales + 3] of the caller, as h_probe
+  Buf d_hurst;
 };
 
 // The bursts chain -- Hilbert envelope (where the bank leaves band series), threshold walk, run statistics -- with its kernels

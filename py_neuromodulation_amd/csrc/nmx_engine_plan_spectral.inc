@@ -584,7 +584,7 @@ static void launch_coh_stage(Plan& P, const WinView& v, int nw, float* d_out, be
   if (tev) be_timer_stop(P.timers[ST_COH], s);
 }
 
-// ---- nolds: sample entropy and DFA of the window and of band series of it (nmx_k_nolds.h) ----------------------------------------
+// ---- nolds: sample entropy, Hurst exponent and DFA of the window and of band series of it (nmx_k_nolds.h) ----------------------------------------
 int build_nolds_bands(Plan& P);   // the band filters: nmx_engine_plan_fir.inc, beside the other FIR stages
 static int launch_nolds_bands(Plan& P, const WinView& v, int nw, be_stream_t s, bool& dc_made);
 
@@ -596,7 +596,9 @@ int build_nolds(Plan& P) {
   if (n_series == 0 || d.nolds_measures == 0) return 0;   // (nothing to compute: the reference emits no key either)
   const bool dfa = (d.nolds_measures & NMX_NOLDS_DFA) && d.nolds_dfa_fit == 1;
   NMX_REQUIRE(d.nolds_dfa_fit == 0 || d.nolds_dfa_fit == 1, "nolds: nolds_dfa_fit must be 0 (off) or 1 (\"poly\")");
-  if (d.nolds_measures & ~(NMX_NOLDS_SAMPEN | (dfa ? NMX_NOLDS_DFA : 0u)))
+  const bool hurst = (d.nolds_measures & NMX_NOLDS_HURST) && d.nolds_hurst_fit == 1;
+  NMX_REQUIRE(d.nolds_hurst_fit == 0 || d.nolds_hurst_fit == 1, "nolds: nolds_hurst_fit must be 0 (off) or 1 (\"poly\")");
+  if (d.nolds_measures & ~(NMX_NOLDS_SAMPEN | (dfa ? NMX_NOLDS_DFA : 0u) | (hurst ? NMX_NOLDS_HURST : 0u)))
     return nmx_fail(NMX_E_UNSUPPORTED, "nolds: only sample_entropy has a kernel (correlation_dimension, lyapunov_exponent, "
                     "hurst_exponent and detrended_fluctuation_analysis end in the reference's unseeded RANSAC line fit)");
   NMX_REQUIRE(d.window <= NMX_NOLDS_MAX_N, "nolds: a series holds at most 40 000 samples (it has to fit the CU's LDS)");
@@ -639,6 +641,34 @@ int build_nolds(Plan& P) {
     P.d.nolds_dfa_scales = nullptr;   // (copied: the caller's array may go)
     P.nolds.have_dfa = true;
   }
+  if (hurst) {
+    const int S = d.nolds_hurst_n_scales;
+    NMX_REQUIRE(d.nolds_hurst_scales && d.nolds_hurst_log_expected && S >= 2 && S <= NMX_NOLDS_HURST_MAX_SCALES,
+                "nolds: the Hurst exponent needs tables of 2 .. 15 scales");
+    for (int k = 0; k < S; ++k) {
+      NMX_REQUIRE(d.nolds_hurst_scales[k] >= 2 && d.nolds_hurst_scales[k] < d.window &&
+                  (k == 0 || d.nolds_hurst_scales[k] > d.nolds_hurst_scales[k - 1]),
+                  "nolds: Hurst scales must ascend within [2, window - 1]");
+      NMX_REQUIRE(std::isfinite(d.nolds_hurst_log_expected[k]), "nolds: Hurst ln E(n) must be finite");
+    }
+    NmxNoldsHurstArgs& H = P.nolds.hurst;
+    H = NmxNoldsHurstArgs{};
+    H.s = A;
+    H.s.cols = cv(d.nolds_hurst_cols);
+    const long long hlast = (long long)H.s.cols.base + (long long)(d.n_channels - 1) * H.s.cols.ch_stride +
+                            (long long)(n_series - 1) * H.s.cols.a_stride;
+    NMX_REQUIRE(H.s.cols.base >= 0 && H.s.cols.ch_stride >= 0 && H.s.cols.a_stride >= 0 && hlast < d.n_outputs,
+                "nolds: Hurst output columns outside the row");
+    H.n_scales = S;
+    H.lanes = nmx_nolds_hurst_lanes(d.window);
+    H.scales = (const int*)upload(P, d.nolds_hurst_scales, (size_t)S * sizeof(int));
+    H.log_e = (const double*)upload(P, d.nolds_hurst_log_expected, (size_t)S * sizeof(double));
+    if (!H.scales || !H.log_e) return nmx_fail(NMX_E_NOMEM, "nolds: Hurst tables");
+    H.lds_floats = al4(d.window) + 64 + 2 * S + al4(S);
+    P.d.nolds_hurst_scales = nullptr;   // (copied: the caller's arrays may go)
+    P.d.nolds_hurst_log_expected = nullptr;
+    P.nolds.have_hurst = true;
+  }
   int rc = build_nolds_bands(P);
   if (rc) return rc;
   P.have_nolds = true;
@@ -668,6 +698,25 @@ static int launch_nolds_stage(Plan& P, const WinView& v, int nw, float* d_out, b
     be_d2h_async(N.h_probe + (size_t)N.probe_w0 * per_hop * 4, A.probe, (size_t)n_items * 4 * sizeof(unsigned), s);
     if (A.series_out)
       be_d2h_async(N.h_series + (size_t)N.probe_w0 * per_hop * A.W, A.series_out, (size_t)n_items * A.W * sizeof(float), s);
+  }
+  if (!rc && N.have_hurst) {   // the same series, the Hurst columns
+    NmxNoldsHurstArgs H = N.hurst;
+    const NmxCols hcols = H.s.cols;
+    H.s = A;
+    H.s.cols = hcols;
+    H.s.probe = nullptr;
+    H.s.series_out = nullptr;
+    const size_t per_item = 2 * (size_t)H.n_scales + 3, per_hop = (size_t)(A.raw + A.n_band) * A.n_channels;
+    if (N.h_hurst) {   // (nmx_nolds_hurst_probe)
+      if (!(rc = ensure(N.d_hurst, (size_t)n_items * per_item * sizeof(double)))) H.probe = (double*)N.d_hurst.p;
+      if (!rc && N.h_series && !(rc = ensure(N.d_series, (size_t)n_items * A.W * sizeof(float)))) H.s.series_out = (float*)N.d_series.p;
+    }
+    if (!rc) be_launch_nolds_hurst(H, n_items, s);
+    if (!rc && N.h_hurst) {
+      be_d2h_async(N.h_hurst + (size_t)N.probe_w0 * per_hop * per_item, H.probe, (size_t)n_items * per_item * sizeof(double), s);
+      if (H.s.series_out)
+        be_d2h_async(N.h_series + (size_t)N.probe_w0 * per_hop * A.W, H.s.series_out, (size_t)n_items * A.W * sizeof(float), s);
+    }
   }
   if (!rc && N.have_dfa) {   // the same series, the DFA columns
     NmxNoldsDfaArgs D = N.dfa;

@@ -734,3 +734,33 @@ int nmx_nolds_dfa_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_s
   }
   return 0;
 }
+
+// ---- nolds: the same for the Hurst kernel (include/nmx.h) ------------------------------------------------------------------
+int nmx_nolds_hurst_probe(nmx_plan* plan, const float* x, int64_t ldx, int64_t n_samples, const int64_t* starts, int64_t n_windows,
+                          float* out, double* rs, int32_t* kept, double* hurst, uint8_t* sum_zero, int32_t* n_kept, float* series) {
+  Plan* Pp = (Plan*)plan;
+  if (!Pp) return nmx_fail(NMX_E_INVALID, "null argument");
+  Plan& P = *Pp;
+  NMX_REQUIRE(P.have_nolds && P.nolds.have_hurst, "nmx_nolds_hurst_probe: the plan has no Hurst kernel");
+  NMX_REQUIRE(n_windows >= 1 && n_windows <= (1 << 20), "nmx_nolds_hurst_probe: 1 <= n_windows <= 2^20");
+  const size_t S = (size_t)P.nolds.hurst.n_scales, per_item = 2 * S + 3;
+  const size_t n = (size_t)n_windows * (size_t)(P.nolds.a.raw + P.nolds.a.n_band) * P.d.n_channels;
+  std::vector<double> hp(n * per_item);
+  std::vector<float> rows;
+  if (!out) { rows.resize((size_t)n_windows * (P.d.n_outputs + P.d.n_extra_cols)); out = rows.data(); }
+  P.nolds.h_hurst = hp.data();
+  P.nolds.h_series = series;
+  const int rc = process_batch_impl(plan, x, ldx, n_samples, starts, n_windows, out, nullptr, 0, nullptr, nullptr);
+  P.nolds.h_hurst = nullptr;
+  P.nolds.h_series = nullptr;
+  if (rc) return rc;
+  for (size_t i = 0; i < n; ++i) {
+    const double* p = hp.data() + i * per_item;
+    if (rs) memcpy(rs + i * S, p, S * sizeof(double));
+    if (kept) for (size_t k = 0; k < S; ++k) kept[i * S + k] = (int32_t)p[S + k];
+    if (hurst) hurst[i] = p[2 * S];
+    if (sum_zero) sum_zero[i] = (uint8_t)(p[2 * S + 1] != 0.0);
+    if (n_kept) n_kept[i] = (int32_t)p[2 * S + 2];
+  }
+  return 0;
+}

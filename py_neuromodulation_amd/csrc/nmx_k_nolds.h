@@ -1,5 +1,5 @@
-// nmx_k_nolds.h -- sample entropy and detrended fluctuation analysis (below: nmx_nolds_dfa_item) of the nolds feature
-// (features/nolds.py): one workgroup per (window, series, channel).
+// nmx_k_nolds.h -- sample entropy, detrended fluctuation analysis (below: nmx_nolds_dfa_item) and the rescaled-range Hurst
+// exponent (nmx_nolds_hurst_item) of the nolds feature (features/nolds.py): one workgroup per (window, series, channel).
 //
 // Reference arithmetic (Nolds.calc_nolds -> nolds.sampen with its defaults: emb_dim = 2, lag = 1, Chebyshev distance, open
 // comparison), for a series x of N samples:
@@ -275,6 +275,148 @@ NMX_DEV void nmx_nolds_dfa_item(const NmxNoldsDfaArgs& D, int item, float* smem)
 // a wave per scale: no more waves than scales
 static inline int nmx_nolds_dfa_threads(int n, int n_scales) { return std::min(nmx_nolds_threads(n), 64 * std::max(n_scales, 1)); }
 
+// ---- Hurst exponent by rescaled range (nolds.hurst_rs with nvals = logmid_n(N, 1/4, 15), corrected, unbiased, fit = "poly") --
+// For a series x of N samples and the plan's tables n_0 .. n_{S-1}, ln E(n_k) (formed on the host: plan_desc.hurst_scales,
+// plan_desc.hurst_expected_rs):
+//   per scale n the N / n whole chunks x[q n : (q + 1) n] (the tail is dropped); per chunk d = x - mean(chunk), y = cumsum(d),
+//   r = max y - min y over y_0 .. y_{n-1}, s = sqrt(sum d^2 / (n - 1)); chunks with r == 0 are left out; (R/S)_n = mean of
+//   r / s over the rest, NaN when none is left;
+//   H = 0.5 + least-squares slope of ln (R/S)_n - ln E(n) on ln n over the scales that are not NaN -- NaN with fewer than
+//   two of them (nolds would hand back the minimum-norm solution for exactly one); 0 when x.sum() is exactly zero.
+// One workgroup per (window, series, channel), the series in LDS as for the other two kernels.  Every scale visits the same
+// N - N % n samples, so the work is split evenly BY SCALE: the workgroup is cut into teams of L = threads / 16 adjacent lanes
+// (4, 16 or 64: nmx_nolds_hurst_lanes), team k owns scale k and lane l of it the chunks l, l + L, ...  A whole wave per scale
+// (as the DFA kernel has it, whose chunks overlap and number 2 N / n) would leave most lanes idle: at N = 1000 thirteen of
+// the fifteen scales have fewer than 64 chunks.  A lane walks its chunks in ONE loop over (chunk, pass, sample) -- two passes
+// per chunk: the mean, then walk, extrema and sum of squares together -- so that teams with different n in one wave do not
+// wait on each other's inner loops: every lane runs about 2 N / L iterations.  All of it in float64; r == 0 is an exact
+// comparison (a constant chunk of float32 samples has an exact float64 mean).  A lane adds its chunks in ascending order,
+// the lanes' sums and kept counts meet in the team's butterfly, (R/S)_n lands in LDS: every sum has one fixed order, the
+// count is an integer sum, and a result does not depend on the batch around it.  Thread 0 fits the <= 15 points.
+#define NMX_NOLDS_HURST_MAX_SCALES 15
+
+struct NmxNoldsHurstArgs {
+  NmxNoldsArgs s;           // the series and the row as for the sample entropy; cols: the Hurst columns; probe unused
+  const int* scales;        // [n_scales] chunk lengths, 2 <= n < W
+  const double* log_e;      // [n_scales] ln E(n)
+  int n_scales;
+  int lanes;                // lanes per team (a power of two <= 64 that divides the workgroup)
+  double* probe;            // [item][2 n_scales + 3]: (R/S)_n, kept chunks per scale, H, sum == 0, scales kept -- or NULL
+  int lds_floats;           // series + 64 floats of reduction scratch + n_scales doubles + n_scales ints
+};
+
+#ifdef NMX_HOST_EMU
+#define NMX_HURST_LANE(L) 0
+#define NMX_HURST_LANES(L) 1
+#define NMX_HURST_TEAM(L) 0
+#define NMX_HURST_TEAMS(L) 1
+NMX_DEV double nmx_nolds_team_sum_d(double v, int) { return v; }
+NMX_DEV int nmx_nolds_team_sum_i(int v, int) { return v; }
+#else
+#define NMX_HURST_LANE(L) ((int)(threadIdx.x & ((L) - 1)))
+#define NMX_HURST_LANES(L) (L)
+#define NMX_HURST_TEAM(L) ((int)(threadIdx.x / (L)))
+#define NMX_HURST_TEAMS(L) ((int)(blockDim.x / (L)))
+// sums over the L adjacent lanes of a team (L a power of two <= 64: the exchanges stay inside the team)
+NMX_DEV double nmx_nolds_team_sum_d(double v, int L) {
+  for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+NMX_DEV int nmx_nolds_team_sum_i(int v, int L) {
+  for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+#endif
+
+NMX_DEV void nmx_nolds_hurst_item(const NmxNoldsHurstArgs& D, int item, float* smem) {
+  const NmxNoldsArgs& A = D.s;
+  const int n_series = A.raw + A.n_band, C = A.n_channels, N = A.W, S = D.n_scales, L = D.lanes;
+  const int c = item % C, s = (item / C) % n_series, w = item / (C * n_series);
+  float* xs = smem;
+  float* red = smem + ((N + 3) & ~3);
+  double* RS = (double*)(red + 64);
+  int* kept_chunks = (int*)(RS + S);
+  const double dc = nmx_nolds_load(A, item, xs);
+
+  double sum = 0.0;
+  for (int i = NMX_TID; i < N; i += NMX_NT) sum += (double)xs[i];
+  sum = nmx_nolds_sum_d(sum, red);
+  const bool zero = sum + (double)N * dc == 0.0;
+
+  // (k is the same for the whole team, and the butterfly exchanges inside the team only)
+  for (int k = NMX_HURST_TEAM(L); k < S; k += NMX_HURST_TEAMS(L)) {
+    const int n = D.scales[k], m = N / n;   // (q n + j <= m n - 1 <= N - 1)
+    const double dn = (double)n, dn1 = (double)(n - 1);
+    double acc = 0.0;
+    int cnt = 0;
+    int q = NMX_HURST_LANE(L), j = 0, pass = 0;
+    double csum = 0.0, mean = 0.0, y = 0.0, ss = 0.0, hi = 0.0, lo = 0.0;
+    while (q < m) {
+      const double v = (double)xs[q * n + j];
+      if (pass == 0) {
+        csum += v;
+      } else {
+        const double d = v - mean;
+        y += d;
+        ss += d * d;
+        hi = (j == 0 || y > hi) ? y : hi;
+        lo = (j == 0 || y < lo) ? y : lo;
+      }
+      if (++j == n) {
+        j = 0;
+        if (pass == 0) {
+          mean = csum / dn;   // (a division: n equal float32 samples sum exactly, and the quotient is then the sample)
+          y = 0.0; ss = 0.0;
+          pass = 1;
+        } else {
+          const double r = hi - lo;
+          if (r != 0.0) { acc += r / sqrt(ss / dn1); ++cnt; }
+          csum = 0.0;
+          pass = 0;
+          q += NMX_HURST_LANES(L);
+        }
+      }
+    }
+    acc = nmx_nolds_team_sum_d(acc, L);
+    cnt = nmx_nolds_team_sum_i(cnt, L);
+    if (NMX_HURST_LANE(L) == 0) { RS[k] = cnt > 0 ? acc / (double)cnt : (double)NAN; kept_chunks[k] = cnt; }
+  }
+  NMX_SYNC();
+
+  if (NMX_TID == 0) {
+    int kept = 0;
+    double mx = 0.0, my = 0.0;
+    for (int k = 0; k < S; ++k)
+      if (kept_chunks[k] > 0) { ++kept; mx += log((double)D.scales[k]); my += log(RS[k]) - D.log_e[k]; }
+    double h = NAN;
+    if (kept >= 2) {
+      mx /= (double)kept;
+      my /= (double)kept;
+      double sxx = 0.0, sxy = 0.0;
+      for (int k = 0; k < S; ++k)
+        if (kept_chunks[k] > 0) {
+          const double dx = log((double)D.scales[k]) - mx;
+          sxx += dx * dx;
+          sxy += dx * (log(RS[k]) - D.log_e[k] - my);
+        }
+      h = sxy / sxx + 0.5;
+    }
+    A.out[(long long)w * A.n_outputs + A.cols.base + c * A.cols.ch_stride + s * A.cols.a_stride] = zero ? 0.f : (float)h;
+    if (D.probe) {
+      double* p = D.probe + (long long)item * (2 * S + 3);
+      for (int k = 0; k < S; ++k) { p[k] = RS[k]; p[S + k] = (double)kept_chunks[k]; }
+      p[2 * S] = h; p[2 * S + 1] = zero ? 1.0 : 0.0; p[2 * S + 2] = (double)kept;
+    }
+  }
+}
+
+// sixteen teams in the workgroup the other kernels would use -- 4, 16 or 64 lanes each -- and no more waves than the table
+// has teams for
+static inline int nmx_nolds_hurst_lanes(int n) { return nmx_nolds_threads(n) / 16; }
+static inline int nmx_nolds_hurst_threads(int n, int n_scales) {
+  return std::min(nmx_nolds_threads(n), (std::max(n_scales, 1) * nmx_nolds_hurst_lanes(n) + 63) & ~63);
+}
+
 #ifdef NMX_HOST_EMU
 static void be_launch_nolds(const NmxNoldsArgs& A, int n_items, be_stream_t st) {
 #ifdef NMX_TR
@@ -292,6 +434,14 @@ static void be_launch_nolds_dfa(const NmxNoldsDfaArgs& D, int n_items, be_stream
   std::vector<float> sm((size_t)D.lds_floats + 16);
   for (int it = 0; it < n_items; ++it) nmx_nolds_dfa_item(D, it, sm.data());
 }
+static void be_launch_nolds_hurst(const NmxNoldsHurstArgs& D, int n_items, be_stream_t st) {
+#ifdef NMX_TR
+  NMX_TR(st);
+#endif
+  (void)st;
+  std::vector<float> sm((size_t)D.lds_floats + 16);
+  for (int it = 0; it < n_items; ++it) nmx_nolds_hurst_item(D, it, sm.data());
+}
 #else
 extern __shared__ __attribute__((aligned(16))) float nmx_smem[];
 __global__ void __launch_bounds__(1024) nmx_kern_nolds_sampen(const NmxNoldsArgs A) {
@@ -305,5 +455,11 @@ __global__ void __launch_bounds__(1024) nmx_kern_nolds_dfa(const NmxNoldsDfaArgs
 }
 static void be_launch_nolds_dfa(const NmxNoldsDfaArgs& D, int n_items, be_stream_t s) {
   NMX_LAUNCH(nmx_kern_nolds_dfa, dim3(n_items), dim3(nmx_nolds_dfa_threads(D.s.W, D.n_scales)), (size_t)D.lds_floats * 4, s, D);
+}
+__global__ void __launch_bounds__(1024) nmx_kern_nolds_hurst(const NmxNoldsHurstArgs D) {
+  nmx_nolds_hurst_item(D, (int)blockIdx.x, nmx_smem);
+}
+static void be_launch_nolds_hurst(const NmxNoldsHurstArgs& D, int n_items, be_stream_t s) {
+  NMX_LAUNCH(nmx_kern_nolds_hurst, dim3(n_items), dim3(nmx_nolds_hurst_threads(D.s.W, D.n_scales)), (size_t)D.lds_floats * 4, s, D);
 }
 #endif

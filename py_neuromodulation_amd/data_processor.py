@@ -319,8 +319,9 @@ class DataProcessor(UserViews):
         """``resample_npad``: the padding of raw_resampling, ``"auto"`` (the default) or an int >= 0 samples per side; 100 is
         what the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
 
-        ``nolds_fit``: ``"poly"`` lets nolds' detrended_fluctuation_analysis run, its final line fitted by least squares
-        (plan_desc.nolds_fit_arg; None: NMX_NOLDS_FIT, and without it the measure raises as the unseeded RANSAC fit has it).
+        ``nolds_fit``: ``"poly"`` lets nolds' detrended_fluctuation_analysis run, its final line fitted by least squares;
+        a mapping ``{measure: "poly" | "RANSAC" | None}`` says it per measure and is what lets hurst_exponent run
+        (plan_desc.nolds_fit_arg; None: NMX_NOLDS_FIT, and without it the measures raise as the unseeded RANSAC fit has it).
 
         ``_family``: (PrepPlan, PostChain, LengthTable) of the processor this one is the twin of for another window
         length (`_twin`): the twin takes them instead of building its own.

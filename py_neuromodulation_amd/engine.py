@@ -80,9 +80,10 @@ class HotPathEngine:
         the reference's call of ``mne.filter.resample`` gets (plan_desc.resample_npad_arg; None: NMX_RESAMPLE_NPAD).
 
         ``nolds_fit``: ``"poly"`` lets ``nolds_settings.features.detrended_fluctuation_analysis`` run -- ``nolds.dfa`` with
-        its final log-log line fitted by least squares instead of nolds' default, an unseeded RANSAC.  ``None`` (the default;
-        NMX_NOLDS_FIT where it is not given) and ``"RANSAC"`` keep the measure's NotImplementedError
-        (plan_desc.nolds_fit_arg).
+        its final log-log line fitted by least squares instead of nolds' default, an unseeded RANSAC -- and that measure only.
+        A mapping names the fit measure by measure: ``{"hurst_exponent": "poly", "detrended_fluctuation_analysis": "poly"}``
+        lets ``nolds.hurst_rs(x, fit="poly")`` run as well.  ``None`` (the default; NMX_NOLDS_FIT where it is not given)
+        and ``"RANSAC"`` keep the measures' NotImplementedError (plan_desc.nolds_fit_arg).
 
         ``dry_run=True`` only derives the plan description and the key list (no library, no
         GPU) -- used to lay out the global column order when channels are sharded over GPUs.
@@ -513,6 +514,35 @@ class HotPathEngine:
         return {"out": out, "scales": scales, "F": fluct, "alpha": alpha, "sum_zero": zero.astype(bool), "n_kept": kept,
                 "series": series}
 
+    def nolds_hurst_probe(self, data: np.ndarray, starts: np.ndarray, want_series: bool = True) -> dict:
+        """``process_batch`` of a plan with the rescaled-range Hurst exponent that also hands back what the Hurst kernel
+        formed (nmx_nolds_hurst_probe): ``"out"`` float32[n, row_width]; ``"scales"`` int[S] and ``"log_expected"``
+        float64[S], the plan's tables; ``"RS"`` float64[n, n_series, C, S], (R/S)_n (NaN where no chunk was kept) and
+        ``"kept"`` int32 of the same shape, the chunks kept; ``"hurst"`` float64 (H, before the sum rule), ``"sum_zero"``
+        (bool) and ``"n_kept"`` (scales that are not NaN), each [n, n_series, C]; ``"series"`` float32[n, n_series, C, W]:
+        the samples the kernel read."""
+        data = np.asarray(data)
+        if data.ndim != 2 or data.shape[0] != self.C_in:
+            raise ValueError(f"expected data with {self.C_in} rows, got {data.shape}")
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        dc = self._host_offsets(data)
+        x = np.ascontiguousarray(data if dc is None else np.asarray(data, np.float64) - dc[:, None], dtype=np.float32)
+        n, S = len(starts), int(self.desc.nolds_raw) + int(self.desc.nolds_n_bands)
+        K = int(self.desc.nolds_hurst_n_scales)
+        out = np.empty((n, self.row_width), np.float32)
+        rs, hurst = np.zeros((n, S, self.C, K), np.float64), np.zeros((n, S, self.C), np.float64)
+        kept_chunks = np.zeros((n, S, self.C, K), np.int32)
+        zero, kept = np.zeros((n, S, self.C), np.uint8), np.zeros((n, S, self.C), np.int32)
+        series = np.zeros((n, S, self.C, self.W), np.float32) if want_series else None
+        self.lib.check(self.lib.lib.nmx_nolds_hurst_probe(
+            self._plan, x.ctypes.data, _ld(x), x.shape[1], starts.ctypes.data, n, out.ctypes.data, rs.ctypes.data,
+            kept_chunks.ctypes.data, hurst.ctypes.data, zero.ctypes.data, kept.ctypes.data,
+            series.ctypes.data if series is not None else None))
+        scales = np.array([self.desc.nolds_hurst_scales[k] for k in range(K)], np.int64)
+        log_e = np.array([self.desc.nolds_hurst_log_expected[k] for k in range(K)], np.float64)
+        return {"out": out, "scales": scales, "log_expected": log_e, "RS": rs, "kept": kept_chunks, "hurst": hurst,
+                "sum_zero": zero.astype(bool), "n_kept": kept, "series": series}
+
     def timing_ms(self, which: int = 0) -> float:
         ms = C.c_float()
         self.lib.check(self.lib.lib.nmx_last_timing_ms(self._plan, which, C.byref(ms)))
@@ -521,7 +551,7 @@ class HotPathEngine:
     def kernels(self, which: int) -> str:
         """Kernels the last batch -- or the last ``preprocess_window`` / ``filter_window`` call -- launched in stage ``which`` (1 prep, 2 time/osc, 3 FIR bank, 4 bursts,
         5 sharp waves, 6 the FIR-bank filters left to a second launch: taps too long for the M = 1536 kernel,
-        7 coherence, 8 grid projection, 10 nolds: its band filters, the sample-entropy kernel and the DFA kernel), named as rocprofv3
+        7 coherence, 8 grid projection, 10 nolds: its band filters and the sample-entropy, Hurst and DFA kernels), named as rocprofv3
         prints them.  ``which = 9``: the launch geometry of the
         channel-pair FIR kernels of that launch sequence, ``"<kernel>: <n> pairs, <workgroups> x <waves> waves"``."""
         buf = C.create_string_buffer(512)

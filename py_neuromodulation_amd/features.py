@@ -132,8 +132,10 @@ class Coherence(_EngineFeature):
 class Nolds(_EngineFeature):
     """features/nolds.py:32-100: sample entropy of every channel's window ("raw") and of band-pass series of it, and --
     with ``Nolds(settings, ch_names, sfreq, nolds_fit="poly")`` or NMX_NOLDS_FIT=poly in the environment -- detrended
-    fluctuation analysis with its final line fitted by least squares.  Without that, and for the three other nolds
-    measures always, ``NotImplementedError`` (the reference fits them with an unseeded RANSAC)."""
+    fluctuation analysis with its final line fitted by least squares.  The per-measure form ``nolds_fit={"hurst_exponent":
+    "poly", "detrended_fluctuation_analysis": "poly"}`` (NMX_NOLDS_FIT=hurst_exponent:poly,...) lets the rescaled-range
+    Hurst exponent run the same way.  Without the opt-in, and for correlation_dimension and lyapunov_exponent always,
+    ``NotImplementedError`` (the reference fits them with an unseeded RANSAC)."""
     feature_name = "nolds"
 
 

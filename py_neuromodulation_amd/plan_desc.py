@@ -10,8 +10,10 @@ sharpwaves.py:169-197,302-326, bursts.py:119-125,262-298, linelength.py:17-19).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
+from collections.abc import Mapping
 
 import numpy as np
 
@@ -36,6 +38,10 @@ NOLDS_MAX_SAMPLES = 40000   # nmx_k_nolds.h: a series sits in the CU's LDS
 # and the plan description carries it -- the kernel bakes in neither the table nor the rule.
 NOLDS_DFA_MIN_SCALE, NOLDS_DFA_MAX_SHARE, NOLDS_DFA_FACTOR = 4, 0.1, 1.2
 NOLDS_DFA_MAX_SCALES = 64   # nmx_k_nolds.h: NMX_NOLDS_DFA_MAX_SCALES
+# nolds.hurst_rs's default scale rule, recalled likewise: logmid_n(N, ratio = 1/4, nsteps = 15); its expected R/S switches
+# from the gamma quotient to the asymptote above n = 340.  `hurst_scales` / `hurst_expected_rs` form both tables here.
+NOLDS_HURST_RATIO, NOLDS_HURST_STEPS, NOLDS_HURST_GAMMA_MAX = 0.25, 15, 340
+NOLDS_HURST_MAX_SCALES = 15   # nmx_k_nolds.h: NMX_NOLDS_HURST_MAX_SCALES
 COH_MAX_NPERSEG = 4096   # nmx_k_coh.h: segment length bound of the coherence kernel, at every window (above 16 384 samples too: NMX_LONG_COHERENCE)
 _BURST_SLOTS = [("duration", ["duration_mean", "duration_max"]),
                 ("amplitude", ["amplitude_mean", "amplitude_max"]),
@@ -72,21 +78,53 @@ def resample_npad_arg(value=None):
 
 
 def nolds_fit_arg(value=None):
-    """The final line fit of the nolds measures as the keyword ``nolds_fit`` states it: ``None`` (the default: the
-    reference's, ``fit="RANSAC"``, which has no kernel -- every measure that ends in it raises), ``"RANSAC"`` (the same,
-    said aloud) or ``"poly"`` (least squares: ``nolds.dfa(x, fit_exp="poly")`` runs on the device).  ``None`` reads the
-    environment variable NMX_NOLDS_FIT (``poly`` or ``RANSAC``).  Anything else: ValueError.  -> None or "poly"."""
+    """The final line fit of the nolds measures as the keyword ``nolds_fit`` states it.
+
+    * ``None`` (the default: the reference's, ``fit="RANSAC"``, which has no kernel -- every measure that ends in it
+      raises) and ``"RANSAC"`` (the same, said aloud);
+    * ``"poly"``: shorthand for ``{"detrended_fluctuation_analysis": "poly"}`` AND NOTHING MORE -- least squares for
+      ``nolds.dfa(x, fit_exp="poly")``, which then runs on the device; the other measures keep raising;
+    * a mapping ``{measure name: "poly" | "RANSAC" | None}`` over the five names of ``NoldsFeatures``, one entry per
+      measure: ``{"hurst_exponent": "poly", "detrended_fluctuation_analysis": "poly"}`` lets ``nolds.hurst_rs(x,
+      fit="poly")`` and ``nolds.dfa(x, fit_exp="poly")`` run.  ``"poly"`` for correlation_dimension and lyapunov_exponent
+      parses, but they have no kernel and keep raising; sample_entropy has no line fit and needs no entry.
+
+    ``None`` reads the environment variable NMX_NOLDS_FIT: ``poly``, ``RANSAC``, or the mapping as
+    ``hurst_exponent:poly,detrended_fluctuation_analysis:poly``.  Anything else: ValueError naming the keyword or the
+    variable.  -> None, "poly", or the mapping as a dict in measure order (a value given again comes back unchanged)."""
     name = "nolds_fit"
     if value is None:
         value = os.environ.get("NMX_NOLDS_FIT", "").strip()
         name = "NMX_NOLDS_FIT"
         if value == "":
             return None
+        if ":" in value:
+            pairs = [item.split(":") for item in value.split(",")]
+            if any(len(kv) != 2 for kv in pairs) or len({kv[0].strip() for kv in pairs}) != len(pairs):
+                raise ValueError(f"{name} must be 'poly', 'RANSAC' or '<measure>:<fit>,...', not {value!r}")
+            value = {k.strip(): v.strip() for k, v in pairs}
     if isinstance(value, str) and value == "poly":
         return "poly"
     if isinstance(value, str) and value == "RANSAC":
         return None
-    raise ValueError(f"{name} must be 'poly' or 'RANSAC' (or unset), not {value!r}")
+    if isinstance(value, Mapping):
+        for k, v in value.items():
+            if not isinstance(k, str) or k not in _lib.NOLDS_MEASURES:
+                raise ValueError(f"{name}: {k!r} is not a nolds measure (one of {_lib.NOLDS_MEASURES})")
+            if not (v is None and name == "nolds_fit") and not (isinstance(v, str) and v in ("poly", "RANSAC")):
+                raise ValueError(f"{name}: the fit of {k} must be 'poly' or 'RANSAC'"
+                                 f"{' (or None)' if name == 'nolds_fit' else ''}, not {v!r}")
+        return {k: value[k] for k in _lib.NOLDS_MEASURES if k in value}
+    raise ValueError(f"{name} must be 'poly' or 'RANSAC' (or unset), or a mapping of measure names to them, not {value!r}")
+
+
+def nolds_poly_measures(fit) -> tuple:
+    """The measures whose final fit is least squares under ``fit``, a value ``nolds_fit_arg`` returned."""
+    if fit == "poly":
+        return ("detrended_fluctuation_analysis",)
+    if isinstance(fit, Mapping):
+        return tuple(k for k in _lib.NOLDS_MEASURES if fit.get(k) == "poly")
+    return ()
 
 
 def dfa_scales(n_samples: int) -> list[int]:
@@ -112,6 +150,38 @@ def dfa_scales(n_samples: int) -> list[int]:
     return nvals
 
 
+def hurst_scales(n_samples: int) -> list[int]:
+    """The chunk lengths ``nolds.hurst_rs`` chooses for a series of ``n_samples`` (its default ``nvals``):
+    ``logmid_n(N, ratio=1/4, nsteps=15)`` -- 15 logarithmically spaced values over the middle quarter of [ln 1, ln N],
+    rounded half to even and made unique; never more than 15.  Below five samples fewer than two scales are left, or the
+    scale 1 among them (whose expected R/S is a gamma(0) domain error in nolds): ValueError."""
+    N = int(n_samples)
+    if N < 1:
+        raise ValueError(f"nolds: hurst_exponent of a {N}-sample series")
+    ln = np.log(N)
+    mid = ln * (1.0 - NOLDS_HURST_RATIO) * 0.5 + np.arange(NOLDS_HURST_STEPS) * (1.0 / NOLDS_HURST_STEPS) * ln * NOLDS_HURST_RATIO
+    nvals = [int(n) for n in np.unique(np.round(np.exp(mid)).astype("int32"))]
+    if len(nvals) < 2 or min(nvals) < 2 or max(nvals) >= N:
+        raise ValueError(f"nolds: hurst_exponent needs at least two chunk lengths 2 <= n < N; a {N}-sample series gives "
+                         f"{nvals} (windows below 5 samples are not supported)")
+    return nvals
+
+
+def hurst_expected_rs(n: int) -> float:
+    """nolds.expected_rs(n): the Anis-Lloyd-Peters expectation of (R/S)_n of white noise -- the exact gamma quotient up to
+    n = 340 and its asymptote above (nolds' own switch; the two do not meet: E(340) = 21.9607..., E(341) = 21.9462...)."""
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"nolds: the expected R/S of chunk length {n} is undefined")
+    i = np.arange(1, n, dtype=np.float64)
+    back = float(np.sum(np.sqrt((n - i) / i)))
+    if n <= NOLDS_HURST_GAMMA_MAX:
+        middle = math.gamma((n - 1) * 0.5) / math.sqrt(math.pi) / math.gamma(n * 0.5)
+    else:
+        middle = 1.0 / math.sqrt(n * math.pi * 0.5)
+    return (n - 0.5) / n * middle * back
+
+
 class PlanBuilder:
     """The window geometry of one plan (``W`` samples the features see, ``W_in`` incoming, ``resample_ratio``), then
     ``build`` -> (PlanDesc, keys, coh_pairs, filter_taps, the arrays the struct points into).  HotPathEngine's arguments."""
@@ -120,7 +190,8 @@ class PlanBuilder:
                  resample_to=None, pre_taps=None, raw_norm=None, resample_npad=None, nolds_fit=None) -> None:
         self.settings = settings
         self.resample_npad = resample_npad_arg(resample_npad)
-        self.nolds_fit = nolds_fit_arg(nolds_fit)   # None, or "poly": detrended_fluctuation_analysis runs (keyword, else NMX_NOLDS_FIT)
+        # None, "poly" (detrended_fluctuation_analysis runs) or a mapping measure -> fit (keyword, else NMX_NOLDS_FIT)
+        self.nolds_fit = nolds_fit_arg(nolds_fit)
         self.ch_names = list(ch_names)
         self.sfreq = float(sfreq)
         self.C = len(self.ch_names)
@@ -531,9 +602,13 @@ class PlanBuilder:
         ns = st.nolds_settings
         feats = _enabled(ns.features)
         other = [f for f in feats if f != "sample_entropy"]
-        dfa = self.nolds_fit == "poly" and "detrended_fluctuation_analysis" in feats
-        if dfa:   # (nolds_fit="poly": nolds.dfa(x, fit_exp="poly") has a kernel; the other three keep raising)
+        poly = nolds_poly_measures(self.nolds_fit)
+        dfa = "detrended_fluctuation_analysis" in poly and "detrended_fluctuation_analysis" in feats
+        hurst = "hurst_exponent" in poly and "hurst_exponent" in feats
+        if dfa:   # (nolds.dfa(x, fit_exp="poly") has a kernel; the string "poly" means this measure alone)
             other.remove("detrended_fluctuation_analysis")
+        if hurst:   # (nolds.hurst_rs(x, fit="poly") has one too; correlation_dimension and lyapunov_exponent keep raising)
+            other.remove("hurst_exponent")
         if other:
             raise NotImplementedError(
                 f"nolds measures {other} are not implemented: the reference ends them in a line fit that defaults to "
@@ -574,7 +649,7 @@ class PlanBuilder:
         d.nolds_tol_factor = NOLDS_TOL_FACTOR
         d.nolds_ddof = NOLDS_DDOF
         C_ = self.C
-        # inside a series and a channel the measures stand in get_enabled() order: sample_entropy, then DFA
+        # inside a series and a channel the measures stand in get_enabled() order: sample_entropy, hurst_exponent, DFA
         nf = len(feats)
         if "sample_entropy" in feats:
             d.nolds_cols = _cols(col + feats.index("sample_entropy"), nf, C_ * nf, 0)
@@ -587,6 +662,15 @@ class PlanBuilder:
             d.nolds_dfa_n_scales = len(scales)
             d.nolds_dfa_scales = scales.ctypes.data_as(C.POINTER(C.c_int32))
             d.nolds_dfa_cols = _cols(col + feats.index("detrended_fluctuation_analysis"), nf, C_ * nf, 0)
+        if hurst:
+            scales = np.ascontiguousarray(hurst_scales(self.W), dtype=np.int32)   # (ValueError below five samples)
+            log_e = np.ascontiguousarray([math.log(hurst_expected_rs(n)) for n in scales], dtype=np.float64)
+            self._keep += [scales, log_e]
+            d.nolds_hurst_fit = 1
+            d.nolds_hurst_n_scales = len(scales)
+            d.nolds_hurst_scales = scales.ctypes.data_as(C.POINTER(C.c_int32))
+            d.nolds_hurst_log_expected = log_e.ctypes.data_as(C.POINTER(C.c_double))
+            d.nolds_hurst_cols = _cols(col + feats.index("hurst_exponent"), nf, C_ * nf, 0)
         for sname in series:
             for ch in self.ch_names:
                 self.keys += [f"{ch}_nolds_{f}_{sname}" for f in feats]

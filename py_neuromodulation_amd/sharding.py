@@ -58,7 +58,7 @@ class ShardedStream:
                  resample_npad=None, nolds_fit=None) -> None:
         self.sfreq = sfreq
         self.resample_npad = resample_npad   # raw_resampling's padding: "auto" or samples per side (DataProcessor)
-        self.nolds_fit = nolds_fit           # "poly": nolds' DFA runs, fitted by least squares (DataProcessor)
+        self.nolds_fit = nolds_fit           # "poly": nolds' DFA runs, fitted by least squares; or a mapping per measure (DataProcessor)
         self.settings = NMSettings.load(settings)
         no_sharded_projection(self.settings)
         self.channels = chmod.load_channels(channels)

@@ -32,7 +32,9 @@ class Stream:
         samples per side; 100 is what the reference's call of ``mne.filter.resample`` gets.  None: NMX_RESAMPLE_NPAD.
 
         ``nolds_fit``: ``"poly"`` lets nolds' detrended_fluctuation_analysis run (``nolds.dfa`` with its final line fitted by
-        least squares instead of the unseeded RANSAC default); None: NMX_NOLDS_FIT, and without it the measure raises.
+        least squares instead of the unseeded RANSAC default), and that measure only; a mapping ``{measure: "poly" |
+        "RANSAC" | None}`` says it per measure -- ``{"hurst_exponent": "poly"}`` lets ``nolds.hurst_rs`` run the same way.
+        None: NMX_NOLDS_FIT, and without it the measures raise.
 
         ``devices=[0, 1, ...]``: the channels are sharded in contiguous blocks over these GPUs inside this one
         process (one plan and one host thread per device, sharding.MultiDeviceProcessor); ``device`` otherwise."""
